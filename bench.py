@@ -25,6 +25,14 @@ WORLD_SIZE == N.  Each rank needs a GPU of its own (`--shared-gpu` rehearses
 several ranks on one GPU); `n_gpus` counts distinct devices (PCI ids), `ranks`
 the processes.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps and prints the line.  `--full` adds everything else the
+benchmark measures or checks after the timed steps: the oracle CPU baseline
+and the parity check against it, the bandwidth probes, and for c4 the e2e,
+c2, c3 and secondary c5 fields.  `--dump-outputs DIR` writes what the last
+timed step computed (realign scores, the proposals' totals) as DIR/*.npy;
+the inputs are seeded, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0 (contract in the task statement); metric
 value = GCUPS = in-band DP cells (forward + backward) per second over the
 whole step; proposals/s and (proposal x read) pairs/s are reported beside it.
@@ -266,14 +274,21 @@ def cpu_baseline(clusters, budget_s=12.0):
                               "sample": f"{d1} cluster(s), {dt1:.1f} s"}}, totals
 
 
+def proposal_mask(t):
+    """(m+1, 9) mask of the dense slots that are STAGE_SCORE proposals of
+    template t: 8m+4 of them, in (position, slot) order."""
+    mask = np.ones((len(t) + 1, 9), bool)
+    mask[0, :5] = False                                  # p = 0: no sub / del
+    mask[np.arange(1, len(t) + 1), np.asarray(t, np.int64)] = False   # the consensus base
+    return mask
+
+
 def parity_check(got, expected, templates):
     """Bench self-check: GPU dense totals vs the oracle's for the clusters the
     CPU baseline ran (every STAGE_SCORE proposal slot, bit for bit)."""
     bad = checked = 0
     for g, e, t in zip(got, expected, templates):
-        mask = np.ones(e.shape, bool)
-        mask[0, :5] = False                                  # p = 0: no sub / del
-        mask[np.arange(1, len(t) + 1), np.asarray(t, np.int64)] = False   # the consensus base
+        mask = proposal_mask(t)
         a, b = np.asarray(g)[mask], e[mask]
         bad += int(np.sum(~((a == b) | (np.isnan(a) & np.isnan(b)))))
         checked += int(mask.sum())
@@ -370,6 +385,16 @@ def main():
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
     ap.add_argument("--clusters", type=int, default=None, help="clusters per rank (override)")
     ap.add_argument("--seed", type=int, default=2024)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures or checks: the CPU "
+                         "baseline and the parity check against the oracle, the bandwidth probes, and for c4 the "
+                         "e2e, c2, c3 and secondary c5 fields (the --no-* / --e2e-* options below select among "
+                         "them); without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                         "(float64; rank 0): realign_scores of every read and proposal_totals, the total "
+                         "of every STAGE_SCORE proposal, 8m+4 per cluster in (position, slot) order (c4: of a fixed "
+                         "seeded sample of clusters, listed in proposal_totals_clusters.npy)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
                     help="c4 only: skip the secondary c5 (10 kb, band doubling) workload")
@@ -454,19 +479,21 @@ def main():
         result = run_read_sharded(args, rank, world, gpu, dist, torch, coll)
     else:
         result = run_clusters(args, rank, world, gpu, dist, torch, coll)
-        if args.config == "c4" and args.e2e_clusters > 0:
+        # the fields beside the headline line are runs of their own: --full only
+        c4_full = args.full and args.config == "c4"
+        if c4_full and args.e2e_clusters > 0:
             result["e2e"] = run_e2e(args, rank, world, gpu, dist, coll)
         # the rank-0 legs below report a failure in their own field (the
         # other ranks are already on their way to the next collective)
-        if args.config == "c4" and not args.no_c2 and rank == 0:
+        if c4_full and not args.no_c2 and rank == 0:
             # configs[1] beside the headline line: whole runs of the 1 kb
             # cluster, latency mode, checked against the oracle's runs
             result["c2"] = rank0_leg(run_c2, args, gpu)
-        if args.config == "c4" and not args.no_c3 and rank == 0:
+        if c4_full and not args.no_c3 and rank == 0:
             # configs[2] beside the headline line: the reference-informed path
             # (FRAME, codon moves) end to end, rank 0 only (one cluster)
             result["c3"] = rank0_leg(run_c3, args, gpu)
-        if args.config == "c4" and not args.no_secondary:
+        if c4_full and not args.no_secondary:
             # configs[4] beside the headline line: driver-measured 10 kb reads
             # with band doubling, read-sharded over the same ranks
             result["secondary"] = run_read_sharded(args, rank, world, gpu, dist, torch, coll)
@@ -506,7 +533,7 @@ def run_dry(args, rank, world, gpu, dist, coll, n_dev):
         elapsed, units = aggregate(elapsed, units, coll)
         cspread = spread(float(cells), coll)
     hand_out = None
-    if args.config == "c4" and args.e2e_clusters > 0:
+    if args.full and args.config == "c4" and args.e2e_clusters > 0:
         hand_out = dry_hand_out(args, rank, world, dist)
     return {"metric": "banded fwd/bwd GCUPS + candidate proposals scored/sec, 1/2/4/8 MI355X",
             "value": None, "unit": "GCUPS", "dry_run": True, "steps": args.steps, "warmup": args.warmup,
@@ -923,6 +950,19 @@ def unpin_threads(saved):
             pass
 
 
+DUMP_CLUSTERS = 256    # c4: clusters whose proposal totals --dump-outputs keeps (256 x 12,004 doubles = 25 MB)
+
+
+def dump_outputs(args, rank, arrays, prefix=""):
+    """--dump-outputs DIR: rank 0 writes each array as DIR/<prefix><name>.npy
+    in float64 (the engine's own precision)."""
+    if not args.dump_outputs or rank != 0:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(args.dump_outputs, f"{prefix}{name}.npy"), np.ascontiguousarray(a, np.float64))
+
+
 def _sync_fn(torch):
     if torch is not None and torch.cuda.is_available():
         return lambda: torch.cuda.synchronize()
@@ -972,8 +1012,10 @@ def run_clusters(args, rank, world, gpu, dist, torch, coll):
 
     dp_flags = RF_FWD | RF_BWD
 
+    last = {}     # what the latest step handed back (--dump-outputs)
+
     def step():
-        eng.realign(slots, slots, tpl_of, bws, dp_flags)
+        last["realign_scores"] = eng.realign(slots, slots, tpl_of, bws, dp_flags)
         dp_ms, _, _ = eng.last_timing()
         eng.score_dense(packed, to_host=False)
         _, sc_ms, _ = eng.last_timing()
@@ -1052,9 +1094,22 @@ def run_clusters(args, rank, world, gpu, dist, torch, coll):
                                        "bytes": score_bytes, "ms": sc_ms}},
         "setup_s": gen_s,
     }
-    if rank == 0:
-        # the timed launch's totals (same plan: downloaded, not recomputed)
-        dense = eng.score_dense(groups, rows=[len(t) + 1 for t, _ in clusters])
+    if rank == 0 and (args.full or args.dump_outputs):
+        # the last timed step's scoring launch once more (same plan, over the
+        # bands that step filled), this time with the totals downloaded
+        dense = eng.score_dense(packed, rows=[len(t) + 1 for t, _ in clusters])
+    if rank == 0 and args.dump_outputs:
+        # every read's realign score; the totals of every STAGE_SCORE proposal
+        # (8m+4 per cluster, (position, slot) order: the dense slots that are
+        # no proposal are left out) of a fixed, seeded sample of clusters (all
+        # of them are 135 MB at the default size)
+        pick = np.sort(np.random.default_rng([args.seed, 0x64756D70]).choice(
+            len(clusters), size=min(len(clusters), DUMP_CLUSTERS), replace=False))
+        dump_outputs(args, rank, {"realign_scores": last["realign_scores"],
+                                  "proposal_totals": np.concatenate(
+                                      [dense[c][proposal_mask(clusters[c][0])] for c in pick]),
+                                  "proposal_totals_clusters": pick})
+    if rank == 0 and args.full:
         if world == 1 and not args.no_cpu:
             result["cpu_baseline"], ref = cpu_baseline(clusters, budget_s=args.cpu_budget)
         else:
@@ -1064,7 +1119,8 @@ def run_clusters(args, rank, world, gpu, dist, torch, coll):
             ref = [oracle.cpu_pass(t, rs, nthreads=cpu_threads())[0] for t, rs in clusters[:2]]
         result["parity"] = parity_check(dense[:len(ref)], ref, [t for t, _ in clusters[:len(ref)]])
     eng.close()
-    result["stream_read_gbs"], result["stream_write_gbs"] = probe_bandwidth(gpu, band_bytes)
+    if args.full:
+        result["stream_read_gbs"], result["stream_write_gbs"] = probe_bandwidth(gpu, band_bytes)
     return result
 
 
@@ -1506,12 +1562,15 @@ def run_read_sharded(args, rank, world, local, dist, torch, coll=None):
     smart_forward_moves(SimpleNamespace(e=timed), [(k, k) for k in range(nloc)], reads, length, 0.1)
     dbl_s = time.perf_counter() - t_dbl
     # alignment_proposals (model.jl:483-497) over the doubled forward bands:
-    # the walk + proposal marking of every read, one launch
-    sl_all = np.arange(nloc, dtype=np.int32)
-    bws0 = np.array([r.bandwidth for r in reads], np.int32)
-    eng.realign(sl_all, sl_all, 0, bws0, RF_FWD)
-    eng.alignment_proposals([sl_all], True)
-    aln_ms = eng.last_backtrace_ms()
+    # the walk + proposal marking of every read, one launch (a measurement
+    # of its own: --full)
+    aln_ms = None
+    if args.full:
+        sl_all = np.arange(nloc, dtype=np.int32)
+        bws0 = np.array([r.bandwidth for r in reads], np.int32)
+        eng.realign(sl_all, sl_all, 0, bws0, RF_FWD)
+        eng.alignment_proposals([sl_all], True)
+        aln_ms = eng.last_backtrace_ms()
     eng.close()
     eng = Engine(local)
     from rifraf_amd.bandedarrays import BAND_PAD_H
@@ -1530,8 +1589,10 @@ def run_read_sharded(args, rank, world, local, dist, torch, coll=None):
     if world > 1:
         partial = torch.zeros((length + 1) * 9, dtype=torch.float64, device=coll)
 
+    last = {}     # what the latest step handed back (--dump-outputs)
+
     def step():
-        eng.realign(slots, slots, 0, bws, RF_FWD | RF_BWD)
+        last["realign_scores"] = eng.realign(slots, slots, 0, bws, RF_FWD | RF_BWD)
         dp_ms, _, _ = eng.last_timing()
         if partial is None:
             eng.score_dense([slots], to_host=False)
@@ -1562,7 +1623,7 @@ def run_read_sharded(args, rank, world, local, dist, torch, coll=None):
     elapsed = time.perf_counter() - t0
     doubled = int(np.sum(bws > bw))
     units = [cells * args.steps, nloc * nprops * args.steps, doubled, nloc, timed.cells, dbl_s,
-             timed.dp_ms, timed.bt_ms, aln_ms]
+             timed.dp_ms, timed.bt_ms, aln_ms or 0.0]
     if dist is not None:
         elapsed, units = aggregate(elapsed, units, coll)
     tot_cells, tot_pairs, tot_doubled, tot_reads, dbl_cells, _, _, _, _ = units
@@ -1621,9 +1682,18 @@ def run_read_sharded(args, rank, world, local, dist, torch, coll=None):
                                        "bytes": score_bytes, "ms": sc_ms}},
         "setup_s": gen_s,
     }
-    if world > 1 and not args.no_sharded_rifraf:
+    if args.dump_outputs and rank == 0:
+        # this rank's reads' realign scores; every proposal's total over all
+        # reads: the exchanged fold at N > 1, else the step's scoring launch
+        # once more (same plan, same bands) with the totals downloaded
+        # (8m+4 STAGE_SCORE proposals, (position, slot) order)
+        tot = partial.cpu().numpy().reshape(-1, 9) if partial is not None else eng.score_dense([slots])[0]
+        dump_outputs(args, rank, {"realign_scores": last["realign_scores"],
+                                  "proposal_totals": tot[proposal_mask(t)]},
+                     prefix="" if args.config == "c5" else "secondary_")
+    if args.full and world > 1 and not args.no_sharded_rifraf:
         result["sharded_rifraf"] = run_sharded_rifraf(args, rank, world, local, dist)
-    if rank == 0:
+    if rank == 0 and args.full:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         if world == 1 and not args.no_cpu:
             result["cpu_baseline"], first = cpu_baseline_reads(t, reads, budget_s=args.cpu_budget)

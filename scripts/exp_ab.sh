@@ -21,7 +21,7 @@ for rep in 1 2; do
       IFS=: read name lib vars <<< "$spec"
       f=$D/${cfg}_${name}_$rep
       extra="--no-secondary --e2e-clusters 0"; [ $cfg = c5 ] && extra=""
-      env $(echo $vars | tr ',' ' ') RIFRAF_HIP_LIB=$PWD/rifraf.jl_amd/librifraf_$lib.so timeout -k 10 200 python bench.py \
+      env $(echo $vars | tr ',' ' ') RIFRAF_HIP_LIB=$PWD/rifraf.jl_amd/librifraf_$lib.so timeout -k 10 200 python bench.py --full \
         --config $cfg --no-cpu $extra --steps 5 --warmup 2 > $f.json 2> $f.err \
         || { echo "$name $cfg bench failed"; tail -10 $f.err; exit 1; }
       python -c "import json; d=json.load(open('$f.json')); print('$cfg $name $rep', 'dp', round(d['dp_ms'],2), 'score', round(d['score_ms'],2), 'step', round(d['ms_per_step'],2), d['parity']['bitexact'])"

@@ -15,6 +15,6 @@ run() {   # name, -- command
     > $D/$name.log 2>&1 || { echo "pass $name failed"; tail -5 $D/$name.log; exit 1; }
   echo "pass $name done"
 }
-run c4_F python3 bench.py --no-cpu --no-secondary --no-c3 --e2e-clusters 0 --steps 1 --warmup 0
-run c5_F python3 bench.py --config c5 --no-cpu --steps 1 --warmup 0
+run c4_F python3 bench.py --full --no-cpu --no-secondary --no-c3 --e2e-clusters 0 --steps 1 --warmup 0
+run c5_F python3 bench.py --full --config c5 --no-cpu --steps 1 --warmup 0
 run c3_F python3 scripts/c3_run.py

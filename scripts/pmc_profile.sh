@@ -21,7 +21,7 @@ for p in $PASSES; do
     *) echo "unknown pass $p"; exit 2 ;;
   esac
   timeout -k 10 240 rocprofv3 --kernel-trace --pmc $C -d gpurun_out/pmc/${TAG}_$p -o p \
-    --output-format csv -- python3 bench.py --steps 1 --warmup 1 --no-cpu --clusters $CLU \
+    --output-format csv -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu --clusters $CLU \
     > gpurun_out/pmc/${TAG}_$p.log 2>&1
   echo "pass $p done"
 done

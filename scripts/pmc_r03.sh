@@ -14,7 +14,7 @@ F="SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VA
 run() {   # name, counters, env..., -- args
   local name=$1 ctr=$2; shift 2
   env "$@" timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $ctr -d $D/$name -o p --output-format csv -- \
-    python3 bench.py --no-cpu --e2e-clusters 0 $BARGS > $D/$name.log 2>&1 || { echo "pass $name failed"; tail -5 $D/$name.log; exit 1; }
+    python3 bench.py --full --no-cpu --e2e-clusters 0 $BARGS > $D/$name.log 2>&1 || { echo "pass $name failed"; tail -5 $D/$name.log; exit 1; }
   echo "pass $name done"
 }
 BARGS="--no-secondary --clusters 400 --steps 1 --warmup 0"

@@ -11,8 +11,8 @@ CTRS=${3:-"FETCH_SIZE WRITE_SIZE"}
 D=gpurun_out/$TAG
 export TMPDIR=/tmp
 mkdir -p $D
-C4="python3 bench.py --no-cpu --no-secondary --no-c3 --e2e-clusters 0 --steps 5 --warmup 2"
-C5="python3 bench.py --config c5 --no-cpu --steps 5 --warmup 2"
+C4="python3 bench.py --full --no-cpu --no-secondary --no-c3 --e2e-clusters 0 --steps 5 --warmup 2"
+C5="python3 bench.py --full --config c5 --no-cpu --steps 5 --warmup 2"
 run() {   # name, rocprof args..., -- command
   local name=$1; shift
   timeout -k 10 300 rocprofv3 "$@" > $D/$name.log 2>&1 || { echo "$name failed"; tail -5 $D/$name.log; exit 1; }

@@ -15,9 +15,9 @@ if [ "$2" != "skip-tests" ]; then
     || { echo "smoke failed"; tail -20 $D/smoke.txt; exit 1; }
   cat $D/smoke.txt
 fi
-timeout -k 10 600 python bench.py > $D/bench.json 2> $D/bench.err || { echo "bench failed"; tail -30 $D/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $D/bench.json 2> $D/bench.err || { echo "bench failed"; tail -30 $D/bench.err; exit 1; }
 cat $D/bench.json
-timeout -k 10 300 python bench.py --gpus 2 --shared-gpu --backend gloo --clusters 200 --e2e-clusters 32 --no-cpu \
+timeout -k 10 300 python bench.py --full --gpus 2 --shared-gpu --backend gloo --clusters 200 --e2e-clusters 32 --no-cpu \
   > $D/bench_2ranks.json 2> $D/bench_2ranks.err || { echo "2-rank bench failed"; tail -30 $D/bench_2ranks.err; exit 1; }
 cat $D/bench_2ranks.json
 timeout -k 10 120 rocprofv3 --list-avail > $D/list_avail.txt 2>&1 || true

@@ -12,6 +12,6 @@ tail -2 $D/gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $D/smoke.txt 2>&1 \
   || { echo "smoke failed"; tail -20 $D/smoke.txt; exit 1; }
 cat $D/smoke.txt
-timeout -k 10 600 python bench.py > $D/bench.json 2> $D/bench.err || { echo "bench failed"; tail -30 $D/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $D/bench.json 2> $D/bench.err || { echo "bench failed"; tail -30 $D/bench.err; exit 1; }
 cat $D/bench.json
 bash scripts/prof_round.sh $TAG

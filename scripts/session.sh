@@ -6,7 +6,7 @@
 # usage: scripts/session.sh TAG STEP [STEP ...]
 #   tests[:K]      pytest -m gpu (optional -k filter K, ',' -> ' or ')
 #   smoke          __graft_entry__.smoke()
-#   bench[:ARGS]   python bench.py ARGS (',' -> ' '), line in TAG/bench.json
+#   bench[:ARGS]   python bench.py --full ARGS (',' -> ' '), line in TAG/bench.json
 #   stats:CFG      rocprofv3 --kernel-trace --stats of the CFG command (c3|c4|c5)
 #   pmc:CFG:CTR    one rocprofv3 --pmc pass (counters ',' separated) of CFG
 #   py:SCRIPT[:ARGS] python3 SCRIPT ARGS (',' -> ' '), stdout in TAG/<name>.out
@@ -16,8 +16,8 @@ TAG=$1; shift
 D=gpurun_out/$TAG
 export TMPDIR=/tmp
 mkdir -p $D
-C4="python3 bench.py --no-cpu --no-secondary --no-c3 --e2e-clusters 0 --steps 5 --warmup 2"
-C5="python3 bench.py --config c5 --no-cpu --steps 5 --warmup 2"
+C4="python3 bench.py --full --no-cpu --no-secondary --no-c3 --e2e-clusters 0 --steps 5 --warmup 2"
+C5="python3 bench.py --full --config c5 --no-cpu --steps 5 --warmup 2"
 C3="python3 scripts/c3_run.py"
 cfgcmd() { case $1 in c3) echo "$C3";; c4) echo "$C4";; c5) echo "$C5";; *) echo "bad cfg $1" >&2; exit 2;; esac; }
 fail() { echo "$1 failed"; tail -${3:-30} $2; exit 1; }
@@ -33,7 +33,7 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $D/smoke.txt 2>&1 || fail smoke $D/smoke.txt
       cat $D/smoke.txt ;;
     bench)
-      timeout -k 10 900 python bench.py ${a1//,/ } > $D/bench.json 2> $D/bench.err || fail bench $D/bench.err
+      timeout -k 10 900 python bench.py --full ${a1//,/ } > $D/bench.json 2> $D/bench.err || fail bench $D/bench.err
       python3 scripts/bench_summary.py $D/bench.json ;;
     stats)
       cmd=$(cfgcmd $a1) || exit 2

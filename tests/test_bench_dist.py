@@ -72,7 +72,7 @@ def test_bench_self_launches_ranks(world):
     line (rank 0) whose reduction covers every rank's shard (N = 8: the
     driver's scaling run on one node, rehearsed with gloo)."""
     p, lines = _bench(["--gpus", str(world), "--backend", "gloo", "--config", "c4", "--clusters", "2",
-                       "--e2e-clusters", "3", "--no-cpu", "--dry-run"])
+                       "--full", "--e2e-clusters", "3", "--no-cpu", "--dry-run"])
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1
     # stdout carries the JSON line only (gloo's connection report goes to stderr)
