@@ -166,7 +166,16 @@ int rf_code_stats(const rf_ctx *ctx, int64_t *entries3, int64_t *entries1, int64
                   int64_t *resets);
 
 /* Sequences (reads or a reference): ids [first, first+nseq).  Replaces any
- * previous content of those ids.  Per sequence k (n_k = off[k+1]-off[k]):
+ * previous content of those ids.  Every upload of an id (this call,
+ * rf_set_sequences_codes, rf_set_sequences_codes_prep; identical content
+ * included) makes the bands that were filled from it stale, like a template
+ * upload does (rf_set_templates): rf_score, rf_score_dense(_dev),
+ * rf_backtrace, rf_alignment_proposals, rf_aln_error_sums and rf_qv_probs
+ * refuse such a slot, the reference slot included, with RF_ERR_STATE
+ * ("sequence changed since the bands were computed") until rf_realign fills
+ * it again; a fill of only one of its two bands leaves the other stale.
+ * rf_download_band still returns the old cells.
+ * Per sequence k (n_k = off[k+1]-off[k]):
  *   bases    off[k]..off[k+1]                    (n_k codes)
  *   match, mismatch, ins at off[k]..off[k+1]     (rifrafsequences.jl:45-47)
  *   del      at off[k]+k .. off[k+1]+k+1         (n_k+1, :49-53)
@@ -205,7 +214,10 @@ int rf_set_sequences_codes_prep(rf_ctx *ctx, int32_t first, int32_t nseq, const 
                                 double s_ins, double s_del, const double *p10_t, const double *grid, double *est,
                                 int32_t *ucode, double *tsum);
 
-/* Templates (consensus sequences, one per cluster): ids [first, first+n). */
+/* Templates (consensus sequences, one per cluster): ids [first, first+n).
+ * Every upload of an id makes the bands filled against it stale: the calls
+ * listed at rf_set_sequences refuse them with RF_ERR_STATE ("template changed
+ * since the bands were computed") until rf_realign fills them again. */
 int rf_set_templates(rf_ctx *ctx, int32_t first, int32_t ntpl,
                      const uint8_t *bases, const int64_t *off);
 

@@ -4439,6 +4439,7 @@ struct SeqObj {
     bool finite = false;   // match / mismatch / ins / del tables hold no -Inf (lean DP eligible)
     bool coded = false;    // row codes written after the tables (RF_TASK_CODED)
     int32_t n = 0, ncins = 0, ncdel = 0;
+    uint64_t version = 0;   // bumped by every upload of this id (tables, codes, codes_prep)
     Region bases, tabs;
 };
 
@@ -4454,6 +4455,7 @@ struct Band {
     int32_t seq = -1, tpl = -1, bw = 0, n = 0, m = 0, H = 0, flags = 0;
     int32_t P = 0;   // kappa row stride (band_stride at the fill)
     uint64_t tplver = 0;
+    uint64_t seqver = 0;   // SeqObj::version at the fill
     Region r;
 };
 
@@ -4657,6 +4659,7 @@ struct rf_ctx {
     std::vector<TplObj> tpls;
     std::vector<Slot> slots;
     uint64_t tpl_counter = 0;
+    uint64_t seq_counter = 0;
     uint64_t layout_gen = 1;   // bumped whenever a device offset / length may change
     int64_t arena_grows = 0;   // arena_grow calls and their wall seconds (RIFRAF_BATCH_TIMING)
     double arena_grow_s = 0.0;
@@ -4746,6 +4749,13 @@ int fail(rf_ctx *ctx, int code, const std::string &msg)
     if (ctx)
         ctx->err = msg;
     return code;
+}
+
+// A band filled from a sequence id that was uploaded again since: its cells
+// belong to the old content (and length), the id's tables and bases to the new.
+bool seq_stale(const rf_ctx *ctx, const Band &b)
+{
+    return b.seq < 0 || b.seq >= (int32_t)ctx->seqs.size() || ctx->seqs[b.seq].version != b.seqver;
 }
 
 #define HIPCHK(ctx, call)                                                          \
@@ -5551,6 +5561,10 @@ int rf_set_sequences(rf_ctx *ctx, int32_t first, int32_t nseq, const uint8_t *ba
     ++ctx->state_epoch;
     if ((int64_t)first + nseq > (int64_t)ctx->seqs.size())
         ctx->seqs.resize(first + nseq);
+    // bands filled from these ids are stale from here on, also when the
+    // upload fails half way
+    for (int32_t k = 0; k < nseq; ++k)
+        ctx->seqs[first + k].version = ++ctx->seq_counter;
     // a fresh code dictionary when no coded sequence outside this upload is
     // still valid (nothing references the old codes)
     {
@@ -5718,6 +5732,8 @@ static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, co
     }
     if ((int64_t)first + nseq > (int64_t)ctx->seqs.size())
         ctx->seqs.resize(first + nseq);
+    for (int32_t k = 0; k < nseq; ++k)   // as rf_set_sequences: bands of these ids are stale
+        ctx->seqs[first + k].version = ++ctx->seq_counter;
     // regions: bases + tables [match|mismatch|ins|del|row codes] (arena growth
     // at most once per arena; offsets are read after every allocation)
     {
@@ -5983,9 +5999,10 @@ static int realign_impl(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const i
                     if (!(jf[k] & (dir == 0 ? RF_FWD : RF_BWD)))
                         continue;
                     Band &b = dir == 0 ? ctx->slots[slot[k]].a : ctx->slots[slot[k]].b;
-                    const uint64_t v = ctx->tpls[tpl[k]].version;
-                    changed = changed || b.tplver != v;
+                    const uint64_t v = ctx->tpls[tpl[k]].version, sv = ctx->seqs[seq[k]].version;
+                    changed = changed || b.tplver != v || b.seqver != sv;
                     b.tplver = v;
+                    b.seqver = sv;
                 }
             }
             if (changed)
@@ -6023,7 +6040,8 @@ static int realign_impl(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const i
                 // may differ in pad_call
                 const Band &o = dir == 0 ? ctx->slots[slot[k]].b : ctx->slots[slot[k]].a;
                 const bool partner = o.valid && o.seq == seq[k] && o.tpl == tpl[k] && o.bw == bw[k] &&
-                                     o.n == S.n && o.m == T.m && o.H == H && o.tplver == T.version;
+                                     o.n == S.n && o.m == T.m && o.H == H && o.tplver == T.version &&
+                                     o.seqver == S.version;
                 const int P = partner ? o.P : band_stride(H, pad_call ? 1 : 0);
                 if (int e = region_ensure(ctx, ctx->band_arena, b.r, band_K(H, T.m) * P * 8))
                     return e;
@@ -6039,6 +6057,7 @@ static int realign_impl(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const i
                 b.H = H;
                 b.flags = dir == 0 ? (jf[k] & (RF_SKEW | RF_TRIM)) : 0;
                 b.tplver = T.version;
+                b.seqver = S.version;
             }
         }
         // scorer descriptors (rf_score_dense's plan) hold band geometry and
@@ -6512,6 +6531,8 @@ static int build_bt_tasks(rf_ctx *ctx, int32_t nslots, const int32_t *slot, std:
         if (slot[k] < 0 || slot[k] >= (int32_t)ctx->slots.size() || !ctx->slots[slot[k]].a.valid)
             return fail(ctx, RF_ERR_STATE, "rf_backtrace: slot has no A band");
         const Band &b = ctx->slots[slot[k]].a;
+        if (seq_stale(ctx, b))
+            return fail(ctx, RF_ERR_STATE, "rf_backtrace: sequence changed since the bands were computed");
         const SeqObj &S = ctx->seqs[b.seq];
         const TplObj &T = ctx->tpls[b.tpl];
         if (T.version != b.tplver)
@@ -6657,7 +6678,7 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
             return false;
         }
         if (S.a.seq != S.b.seq || S.a.tpl != S.b.tpl || S.a.bw != S.b.bw || S.a.tplver != S.b.tplver ||
-            S.a.m != S.b.m) {
+            S.a.m != S.b.m || S.a.seqver != S.b.seqver || S.a.n != S.b.n) {
             why = "A and B bands were computed for different alignments";
             return false;
         }
@@ -6667,6 +6688,10 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
         }
         if (ctx->tpls[S.a.tpl].version != S.a.tplver) {
             why = "template changed since the bands were computed";
+            return false;
+        }
+        if (seq_stale(ctx, S.a)) {
+            why = "sequence changed since the bands were computed";
             return false;
         }
         return true;
@@ -6959,12 +6984,15 @@ static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_of
                 return fail(ctx, RF_ERR_ARG, "rf_score_dense: unknown slot");
             const Slot &S = ctx->slots[sl];
             if (!S.a.valid || !S.b.valid || S.a.seq != S.b.seq || S.a.tpl != S.b.tpl ||
-                S.a.bw != S.b.bw || S.a.tplver != S.b.tplver || S.a.m != S.b.m)
+                S.a.bw != S.b.bw || S.a.tplver != S.b.tplver || S.a.m != S.b.m || S.a.seqver != S.b.seqver ||
+                S.a.n != S.b.n)
                 return fail(ctx, RF_ERR_STATE, "rf_score_dense: A and B bands were computed for different alignments");
             if (S.a.P != S.b.P)
                 return fail(ctx, RF_ERR_STATE, "rf_score_dense: A and B bands have different row strides");
             if (ctx->tpls[S.a.tpl].version != S.a.tplver)
                 return fail(ctx, RF_ERR_STATE, "rf_score_dense: template changed since the bands were computed");
+            if (seq_stale(ctx, S.a))
+                return fail(ctx, RF_ERR_STATE, "rf_score_dense: sequence changed since the bands were computed");
             const SeqObj &Q = ctx->seqs[S.a.seq];
             if (Q.ncins > 0 || Q.ncdel > 0)
                 return fail(ctx, RF_ERR_ARG, "error model cannot allow codon indels");
@@ -7175,6 +7203,8 @@ int rf_internal_aln_sums_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_o
     for (int32_t k = 0; k < ns; ++k) {
         if (slots[k] < 0 || slots[k] >= (int32_t)ctx->slots.size() || !ctx->slots[slots[k]].a.valid)
             return fail(ctx, RF_ERR_STATE, "rf_aln_error_sums: slot has no A band");
+        if (seq_stale(ctx, ctx->slots[slots[k]].a))
+            return fail(ctx, RF_ERR_STATE, "rf_aln_error_sums: sequence changed since the bands were computed");
         const SeqObj &S = ctx->seqs[ctx->slots[slots[k]].a.seq];
         if (!S.coded)
             return 1;

@@ -192,6 +192,18 @@ class Engine:
         bases = np.ascontiguousarray(np.concatenate([np.asarray(t, np.uint8) for t in tpls]), np.uint8)
         self._check(self.lib.rf_set_templates(self.ctx, int(first), len(tpls), ptr(bases), ptr(off)))
 
+    def set_templates_ids(self, ids, tpls):
+        """rf_set_templates_ids: tpls[k] becomes template ids[k] (a sparse set)."""
+        if not tpls:
+            return
+        ids = np.ascontiguousarray(ids, np.int32)
+        if ids.shape != (len(tpls),):
+            raise ValueError("set_templates_ids: one id per template")
+        off = np.zeros(len(tpls) + 1, np.int64)
+        np.cumsum([len(t) for t in tpls], out=off[1:])
+        bases = np.ascontiguousarray(np.concatenate([np.asarray(t, np.uint8) for t in tpls]), np.uint8)
+        self._check(self.lib.rf_set_templates_ids(self.ctx, len(tpls), ptr(ids), ptr(bases), ptr(off)))
+
     def rifraf_batch_native(self, bparams, read_off, read_seq, read_len, threshold, fixed_off, fixed,
                             slot_base, tpl_id, cons, cons_off, ref=None):
         """rf_rifraf_batch(_ref) + rf_batch_fetch(_ref): the native lockstep

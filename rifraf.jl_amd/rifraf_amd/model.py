@@ -400,10 +400,12 @@ def _align_ref_moves(state: RifrafState, run: _Run, skew: bool):
     """align_moves(consensus, reference; skew_matches) on the engine
     (align.jl:337-344): forward_moves! of the reference (rows) against the
     consensus with the reference's own bandwidth, then backtrace.  The
-    skewed fill may already be in the scratch slot (realign's B call)."""
+    skewed fill may already be in the scratch slot (realign's B call).  The
+    reference is on the device already (every change of state.reference
+    uploads it); uploading it again here would make the reference slot's A / B
+    bands stale for the scoring that follows (rf_score refuses them)."""
     ref = state.reference
     if not (skew and run.sip_ready):
-        run.set_ref(ref)
         run.e.realign([run.scratch()], [run.REF], 0, [ref.bandwidth], RF_FWD | (RF_SKEW if skew else 0))
     run.sip_ready = False
     moves, _ = run.e.backtrace([run.SCRATCH])

@@ -1134,6 +1134,80 @@ def test_plan_cache_follows_slot_contents(engine):
         np.testing.assert_array_equal(got[mask], ref[mask])
 
 
+@pytest.mark.parametrize("path", ["tables", "codes"])
+def test_replaced_sequence_refused_until_refill(engine, path):
+    """Bands remember the upload they were filled from: after rf_set_sequences
+    (or _codes) replaces a read -- same length, other bases and scores -- the
+    scorers, the backtrace and the proposal marking refuse the read's slot
+    with RF_ERR_STATE ("sequence changed since the bands were computed")
+    instead of combining the old cells with the new tables; a slot of which
+    only one band was filled again is still refused; after a full refill the
+    same calls give the oracle's values for the new read.  (Before the
+    version check these calls returned numbers without an error.)"""
+    from rifraf_amd.errormodel import phred_to_log_p
+    rng = np.random.default_rng(606)
+    t = random_seq(90, rng)
+    bases = [t.copy() for _ in range(5)]
+    for b in bases:
+        b[rng.integers(0, 90, 4)] = rng.integers(0, 4, 4)
+    phreds = [rng.integers(8, 40, 90).astype(np.int8) for _ in range(5)]
+    seqs = [RifrafSequence(b, p, 9, SEQ_SCORES) for b, p in zip(bases, phreds)]
+    nb = bases[1].copy()
+    nb[40:44] = (nb[40:44] + 1) % 4
+    nph = rng.integers(8, 40, 90).astype(np.int8)
+    new = RifrafSequence(nb, nph, 9, SEQ_SCORES)
+    sl = np.arange(5)
+    props = all_proposals_arrays(t)
+    engine.set_templates(0, [t])
+    engine.set_sequences(0, seqs)
+    engine.realign(sl, sl, 0, [9] * 5, RF_FWD | RF_BWD)
+    calls = {"score_dense": lambda: engine.score_dense([sl]),
+             "score": lambda: engine.score([(sl, -1, props)]),
+             "backtrace": lambda: engine.backtrace(sl),
+             "alignment_proposals": lambda: engine.alignment_proposals([sl], True),
+             "aln_error_sums": lambda: engine.aln_error_sums([sl], [90], [seqs])}
+    before = engine.score_dense([sl])[0].copy()
+    for _ in range(2):
+        for call in calls.values():                      # plans cached, validation skipped
+            call()
+    if path == "tables":
+        engine.set_sequences(1, [new])
+    else:
+        lp_t = phred_to_log_p(np.arange(256, dtype=np.uint8).view(np.int8))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            match_t = np.log10(1.0 - np.power(10.0, lp_t))
+        assert engine.set_sequences_codes(1, nb, np.array([0, 90], np.int64), nph.view(np.uint8), lp_t, match_t,
+                                          SEQ_SCORES)
+    for name, call in calls.items():
+        with pytest.raises(RifrafError, match="sequence changed since the bands were computed"):
+            call()
+    # the other slots are untouched and still scored
+    others = np.array([0, 2, 3, 4])
+    ref_o, _ = oracle.cpu_pass(t, [seqs[k] for k in others], nthreads=2)
+    mask = np.ones_like(ref_o, bool)
+    mask[0, :5] = False
+    mask[np.arange(1, 91), t.astype(np.int64)] = False
+    np.testing.assert_array_equal(engine.score_dense([others])[0][mask], ref_o[mask])
+    # one band filled again: A is new, B still belongs to the old read
+    engine.realign([1], [1], 0, [9], RF_FWD)
+    with pytest.raises(RifrafError):
+        engine.score_dense([sl])
+    engine.backtrace(sl)                                 # needs the A bands only
+    engine.realign([1], [1], 0, [9], RF_BWD)
+    now = seqs[:1] + [new] + seqs[2:]
+    ref, _ = oracle.cpu_pass(t, now, nthreads=2)
+    got = engine.score_dense([sl])[0]
+    np.testing.assert_array_equal(got[mask], ref[mask])
+    assert not np.array_equal(got[mask], before[mask])
+    kd, p, b = props
+    np.testing.assert_array_equal(engine.score([(sl, -1, props)])[0], ref[p, np.where(kd == 0, b, np.where(kd == 2, 4, 5 + b))])
+    moves, _ = engine.backtrace(sl)
+    _, mv = oracle.forward(t, new, moves=True)
+    np.testing.assert_array_equal(moves[1], oracle.backtrace(mv, 91, 91, 9))
+    engine.alignment_proposals([sl], True)
+    engine.aln_error_sums([sl], [90], [now])
+
+
 def test_row_code_dictionary_overflow():
     """Reads with all-distinct log error probabilities fill the 65 536-entry
     row-code dictionary part way through one upload: later reads stay
