@@ -11,6 +11,8 @@
  *   rf_realign        <- forward_moves!/forward!/backward! over a batch
  *                        src/align.jl:114-141,155-179,196-202;
  *                        realign! src/model.jl:679-714
+ *   rf_pair_scores    <- forward!(...)[end, end] over many pairs
+ *                        src/align.jl:155-179
  *   rf_backtrace      <- backtrace + count_errors   src/align.jl:229-245
  *   rf_alignment_proposals <- alignment_proposals / moves_to_proposals
  *                        src/model.jl:458-497
@@ -140,6 +142,9 @@ const char *rf_last_error(const rf_ctx *ctx);
 #define RF_OPT_BT_NW       31   /* 4 (default): a backtrace launch of at most 64
                                    walks runs each on 4 waves (k_bt_win<4096, 4>,
                                    a 252-cell box); 1: one wave per walk        */
+#define RF_OPT_PAIR_CHUNK  32   /* rf_pair_scores: pairs per launch set (default
+                                   65536); descriptors and scores of one chunk are
+                                   all the device memory the call needs         */
 /* Keys 3, 5-8, 14 and 20 selected scorer variants measured slower and removed
    in round 3 (k_score_lean, the 128-lane k_score_ws, k_score_seg /
    k_score_segc, 16-diagonal k_score_segl, the unspecialised k_score_w2);
@@ -241,6 +246,27 @@ int rf_realign(rf_ctx *ctx, int32_t njobs, const int32_t *slot,
 int rf_realign_jobs(rf_ctx *ctx, int32_t njobs, const int32_t *slot,
                     const int32_t *seq, const int32_t *tpl, const int32_t *bw,
                     const int32_t *flags, double *out_score);
+
+/* Score-only alignment: out[k] = A[end,end] of forward!(tpl[k], seq[k];
+ * bandwidth bw[k]) (align.jl:155-179, cell rule :50-112) for npairs
+ * independent pairs, without bands or slots -- exactly the value
+ * rf_realign(..., RF_FWD | flags) writes to out_score[k], bit for bit, from a
+ * fill that keeps only the last anti-diagonals on chip.  For R x T score
+ * grids (which reference / cluster does a read belong to) whose bands would
+ * not fit the device and that nobody reads.  flags: 0 or RF_SKEW / RF_TRIM;
+ * RF_FWD is implied and accepted, RF_BWD is RF_ERR_ARG.  Unknown ids, bw < 1
+ * and a band of more than 5,114 rows (2 bw + |n - m| + 1: what the widest
+ * pass holds in LDS) are RF_ERR_ARG.  Sequences come from any of the three
+ * upload calls, templates from rf_set_templates(_ids).  A pair the reference
+ * raises on ("new score is invalid", align.jl:105-110) gets NaN and the call
+ * still returns 0 (rf_score_dense's convention).  The call touches no slot,
+ * makes no band stale or fresh and does not move the band arena; pairs are
+ * sent RF_OPT_PAIR_CHUNK at a time, so device memory does not grow with
+ * npairs. */
+int rf_pair_scores(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl,
+                   const int32_t *bw, int32_t flags, double *out);
+/* Kernel time of the last rf_pair_scores call (all its chunks), milliseconds. */
+int rf_last_pair_ms(const rf_ctx *ctx, double *ms);
 
 /* Backtrace of the A band of each slot (align.jl:229-238), moves in
  * alignment order written at moves[moves_off[k] ...] (capacity n+m each);

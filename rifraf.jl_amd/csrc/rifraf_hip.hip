@@ -10,6 +10,10 @@
 //               latency-bound task per wave (the reference's codon DP)
 //   k_dpm / k_dp  very wide bands (edit_distance, align.jl:253-260): band
 //               slices across the CUs of an XCD / one block per band
+//   k_ps / k_ps_gen  score-only forward Viterbi of independent pairs
+//               (rf_pair_scores): A[end,end] without a band; register tier
+//               (k_dpr's systolic step, no stores) and LDS-ring tier (k_dp's)
+//               src/align.jl:155-179
 //   k_score_ws / k_score_segl / k_score
 //               dense per-position proposal scoring of every batch read,
 //               left-folded over the batch in batch order
@@ -1253,6 +1257,390 @@ k_dpr(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ 
       const double *__restrict__ lut)
 {
     dpr_body<NP, LEAN, PM, LPT, PFIX>(blockIdx.x, tasks, ntasks, bases, tabs, bands, out_score, err, sink, lut);
+}
+
+// ---------------------------------------------------------------------
+// k_ps / k_ps_gen: score-only forward Viterbi (rf_pair_scores).
+//
+// A[n+1, m+1] of forward! (align.jl:155-179, cell rule :50-112) for many
+// independent (sequence, template) pairs, one double out per pair and no
+// band: only the anti-diagonals kappa-1 and kappa-2 (kappa-3 with codon
+// moves) stay live.  Same candidates and FP64 sums as k_dpr / k_dp, so the
+// value is the one rf_realign(RF_FWD) writes to out_score, bit for bit.
+//
+// k_ps<NP, LPT> (fast tier): the lean condition of k_dpr -- no codon tables,
+// finite tables, no skew / trim -- and H <= 2*LPT*NP - 1 <= PS_FAST_H.  Four
+// 16-lane tasks per wave (NP = 1, 2, 4: H <= 31, 63, 127) or one 64-lane task
+// (NP = 2: H <= 255); the anti-diagonals, row records and template
+// bases move systolically by DPP exactly as in k_dpr (dpr_step / dpl_step
+// without their stores).  The lean interior takes its edge records (the row
+// entering lane 15, the column entering lane 0) from a PS_B-period LDS
+// block that the task's lanes load one block ahead, one record per lane, from
+// the row codes + dictionary or the tables; that block (768 B per task) is
+// the kernel's only LDS, and with no band stores nothing else waits on
+// memory.  Finite tables make every in-band cell finite (dpl_step's note),
+// so "new score is invalid" cannot fire in this tier.  The final cell is
+// kept in a register (fval / fset) and stored once after the loop.
+//
+// k_ps_gen<NT> (general tier): everything else up to H <= DPW_LDS_H --
+// codon tables, RF_SKEW, RF_TRIM, -Inf table entries, wide bands -- as
+// k_dp's LDS-ring recurrence with the band stores removed, one pair per
+// workgroup of NT threads.  A pair with an invalid cell (align.jl:105-110)
+// gets NaN; its neighbours are untouched and no error word is raised.
+// ---------------------------------------------------------------------
+constexpr int PS_B = 16;           // periods per edge-record block of k_ps (one record per lane)
+constexpr int PS_FAST_H = 255;     // widest band of the fast tier (k_ps<2, 64>)
+constexpr int PS_GEN64_H = 2040;   // widest band of the one-wave general tier (ring < 64 KB); above: DPW_NT threads
+constexpr int PS_CHUNK = 65536;    // pairs per launch set of rf_pair_scores (RF_OPT_PAIR_CHUNK's default)
+
+// dpr_step without codon moves, skew / trim and stores (borders of the matrix)
+template <int NP, int PAR, int LPT>
+__device__ __forceinline__ void ps_step(const DPTask &T, int q, int k, double (&v1)[NP], double (&v2)[NP],
+                                        const RowRec (&row)[NP], const int (&col)[NP], double &fval, int &fset)
+{
+    const double E1 = PAR == 0 ? dpp_f64<TaskLanes<LPT>::FROM_L1>(v1[NP - 1])
+                               : dpp_f64<TaskLanes<LPT>::FROM_R1>(v1[0]);
+    const bool live = k < T.klen;
+    double nv[NP];
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+        const int d = 2 * (q * NP + r) + PAR;
+        const int jj = (k - d) >> 1;
+        const int ii = d + jj - T.c;
+        const bool valid = live && d < T.H && d <= k && jj <= T.m && ii >= 0 && ii <= T.n;
+        const RowRec &R = row[r];
+        const double ms = (R.sb == col[r]) ? R.mt : R.mm;
+        const double x_ins = PAR ? v1[r] : (r > 0 ? v1[r > 0 ? r - 1 : 0] : E1);
+        const double x_del = PAR ? (r < NP - 1 ? v1[r < NP - 1 ? r + 1 : 0] : E1) : v1[r];
+        const double best = fmax(fmax(v2[r] + ms, x_ins + R.is), x_del + R.ds);
+        const double v = valid ? ((ii == 0 && jj == 0) ? 0.0 : best) : -RF_INF;
+        const bool fin = valid && ii == T.n && jj == T.m;
+        fval = fin ? v : fval;
+        fset |= fin ? 1 : 0;
+        nv[r] = v;
+    }
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+        v2[r] = v1[r];
+        v1[r] = nv[r];
+    }
+}
+
+// dpl_step without its LDS stores (the lean interior)
+template <int NP, int PAR, int LPT>
+__device__ __forceinline__ void ps_lean_step(double (&v1)[NP], double (&v2)[NP], const RowRec (&row)[NP],
+                                             const int (&col)[NP], const double (&lb)[NP])
+{
+    const double E1 = PAR == 0 ? dpp_rot_f64<TaskLanes<LPT>::ROT_L1>(v1[NP - 1])
+                               : dpp_rot_f64<TaskLanes<LPT>::ROT_R1>(v1[0]);
+    double nv[NP];
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+        const RowRec &R = row[r];
+        const double ms = (R.sb == col[r]) ? R.mt : R.mm;
+        const double x_ins = PAR ? v1[r] : (r > 0 ? v1[r > 0 ? r - 1 : 0] : E1);
+        const double x_del = PAR ? (r < NP - 1 ? v1[r < NP - 1 ? r + 1 : 0] : E1) : v1[r];
+        nv[r] = fmax(fmax(v2[r] + ms, x_ins + R.is), x_del + R.ds) + lb[r];
+    }
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+        v2[r] = v1[r];
+        v1[r] = nv[r];
+    }
+}
+
+template <int NP, int LPT = 16>
+__global__ void __launch_bounds__(64)
+k_ps(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+     const double *__restrict__ tabs, double *__restrict__ out, const double *__restrict__ lut)
+{
+    // 16 lanes per task, or the whole wave (wave_shr / wave_shl moves: no edge fix, TaskLanes)
+    static_assert(LPT == 16 || LPT == 64, "k_ps tasks are 16 or 64 lanes");
+    __shared__ EdgeRec s_edge[64 / LPT][PS_B];
+    const int q = threadIdx.x & (LPT - 1);
+    const int t = threadIdx.x / LPT;
+    const int tid = blockIdx.x * (64 / LPT) + t;
+    DPTask T = {};
+    if (tid < ntasks)
+        T = tasks[tid];
+    int kmax = T.klen;
+    for (int off = 32; off >= 1; off >>= 1)
+        kmax = max(kmax, __shfl_xor(kmax, off));
+    kmax = __builtin_amdgcn_readfirstlane(kmax);
+    const uint8_t *sbase = bases + T.sb;
+    const uint8_t *tbase = bases + T.tb;
+    const double *tb = tabs + T.tab;
+
+    double v1[NP], v2[NP];
+    RowRec row[NP];
+    int col[NP];
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+        v1[r] = -RF_INF;
+        v2[r] = -RF_INF;
+        const int pp = q * NP + r;
+        row[r] = load_row(T, false, sbase, tb, pp - T.c, false);   // kappa = 0
+        col[r] = load_col(T, false, tbase, -pp);
+    }
+    const int top = LPT * NP - 1;
+    RowRec nq = load_row(T, false, sbase, tb, top + 1 - T.c, false);   // enters at kappa = 1
+    int cq = load_col(T, false, tbase, 1);                             // enters at kappa = 2
+    double fval = 0.0;   // the final cell's score (the lane that computes it)
+    int fset = 0;
+
+    // lean interior [klo, khi] of the wave's four tasks (dpr_body)
+    int klo = INT_MAX, khi = -1;
+    double lb[2][NP];
+    {
+        int lo = 0, hi = INT_MAX;
+        bool ok = true;
+#pragma unroll
+        for (int par = 0; par < 2; ++par)
+#pragma unroll
+            for (int r = 0; r < NP; ++r) {
+                const int d = 2 * (q * NP + r) + par;
+                const int jlo = max(0, T.c - d), jhi = min(T.m, T.n + T.c - d);
+                const bool a = tid < ntasks && d < T.H && jlo <= jhi;
+                lb[par][r] = a ? 0.0 : -RF_INF;
+                if (a) {
+                    lo = max(lo, d + 2 * jlo);
+                    hi = min(hi, d + 2 * jhi);
+                }
+            }
+        if (tid < ntasks) {
+            lo = max(lo, T.c + 1);
+            hi = min(hi, T.klen - 2);
+            ok = T.c <= T.m;   // diagonal 0 holds cells: edge rows stay >= 1
+        }
+        for (int off = 32; off >= 1; off >>= 1) {
+            lo = max(lo, __shfl_xor(lo, off));
+            hi = min(hi, __shfl_xor(hi, off));
+        }
+        if (__all(ok)) {
+            klo = __builtin_amdgcn_readfirstlane((lo + 1) & ~1);
+            khi = __builtin_amdgcn_readfirstlane(hi);
+        }
+    }
+    const int nblk = khi >= klo ? (khi - klo + 1) / (2 * PS_B) : 0;
+
+    for (int k = 0; k < kmax; k += 2) {
+        if (k == klo && nblk > 0) {
+            EdgeRec *ein = s_edge[t];
+            const int top_c = LPT * NP - T.c;
+            const bool coded = T.flags & RF_TASK_CODED;
+            const uint64_t *codes = (const uint64_t *)(tb + row_code_off(T.n, T.ncins, T.ncdel));
+            const int ql = min(q, PS_B - 1);
+            auto edge_ks = [&](int kb) {   // lane q < PS_B: the edge row of period kb / 2 + q (clamped; masked by lb)
+                const int ii = max(1, min(top_c + (kb >> 1) + ql, T.n));
+                return ii - 1;
+            };
+            auto code_load = [&](int kb) -> uint64_t { return coded ? codes[edge_ks(kb)] : 0; };
+            auto edge_load = [&](int kb, uint64_t rec) {
+                EdgeRec e;
+                const int ks = edge_ks(kb);
+                if (coded) {
+                    const double *l3 = lut + 4 * (int)(rec & 0xffff);
+                    const dvec2 mt_mm = *(const dvec2 *)l3;
+                    e.mt = mt_mm.x;
+                    e.mm = mt_mm.y;
+                    e.is = l3[2];
+                    e.ds = lut[4 * RF_CODES + (int)((rec >> 32) & 0xffff)];
+                    e.sb = (int)(rec >> 48) & 0xff;
+                } else {
+                    e.sb = sbase[ks];
+                    e.mt = tb[ks];
+                    e.mm = tb[T.n + ks];
+                    e.is = tb[2 * (size_t)T.n + ks];
+                    e.ds = tb[3 * (size_t)T.n + ks + 1];
+                }
+                const int jj = max(1, min((kb >> 1) + ql, T.m));
+                e.col = tbase[jj - 1];
+                e.pad0 = e.pad1 = 0;
+                return e;
+            };
+            {
+                const EdgeRec first = edge_load(k, code_load(k));
+                if (q < PS_B)
+                    ein[q] = first;
+            }
+            EdgeRec pend = edge_load(k + 2 * PS_B, code_load(k + 2 * PS_B));
+            uint64_t pcode = code_load(k + 4 * PS_B);
+            wave_sync();
+            for (int b = 0; b < nblk; ++b) {
+                EdgeRec E = ein[0];
+#pragma unroll
+                for (int p = 0; p < PS_B; ++p) {
+                    EdgeRec En;
+                    if (p + 1 < PS_B)
+                        En = ein[p + 1];   // read one period ahead (LDS latency)
+                    {   // even step: column k/2 enters lane 0
+                        const int from = __builtin_amdgcn_update_dpp(E.col, col[NP - 1], TaskLanes<LPT>::FROM_L1,
+                                                                     0xF, 0xF, false);
+#pragma unroll
+                        for (int r = NP - 1; r > 0; --r)
+                            col[r] = col[r - 1];
+                        col[0] = from;
+                    }
+                    ps_lean_step<NP, 0, LPT>(v1, v2, row, col, lb[0]);
+                    {   // odd step: rows advance; lane 15 receives the edge row
+                        RowRec e;
+                        e.sb = E.sb;
+                        e.mt = E.mt;
+                        e.mm = E.mm;
+                        e.is = E.is;
+                        e.ds = E.ds;
+                        e.ci = e.cd = -RF_INF;
+                        const RowRec up = row_from_above<LPT>(row[0], e, false);
+#pragma unroll
+                        for (int r = 0; r < NP - 1; ++r)
+                            row[r] = row[r + 1];
+                        row[NP - 1] = up;
+                    }
+                    ps_lean_step<NP, 1, LPT>(v1, v2, row, col, lb[1]);
+                    if (p + 1 < PS_B)
+                        E = En;
+                }
+                wave_sync();
+                if (q < PS_B)
+                    ein[q] = pend;   // the next block's records, loaded one block ago
+                pend = edge_load(k + 4 * PS_B, pcode);
+                pcode = code_load(k + 6 * PS_B);
+                wave_sync();
+                k += 2 * PS_B;
+            }
+            // back to the general steps: the edge row and column they expect
+            nq = load_row(T, false, sbase, tb, top + k / 2 + 1 - T.c, false);
+            cq = load_col(T, false, tbase, k / 2);
+            if (k >= kmax)
+                break;
+        }
+        if (k > 0) {
+            // even step: columns advance; lane 0 receives column k/2
+            const int edge = cq;
+            cq = load_col(T, false, tbase, k / 2 + 1);
+            const int from = __builtin_amdgcn_update_dpp(edge, col[NP - 1], TaskLanes<LPT>::FROM_L1, 0xF, 0xF, false);
+#pragma unroll
+            for (int r = NP - 1; r > 0; --r)
+                col[r] = col[r - 1];
+            col[0] = from;
+        }
+        ps_step<NP, 0, LPT>(T, q, k, v1, v2, row, col, fval, fset);
+        if (k + 1 < kmax) {
+            // odd step: rows advance; lane 15 receives the prefetched row
+            const RowRec up = row_from_above<LPT>(row[0], nq, false);
+#pragma unroll
+            for (int r = 0; r < NP - 1; ++r)
+                row[r] = row[r + 1];
+            row[NP - 1] = up;
+            nq = load_row(T, false, sbase, tb, top + (k + 2) / 2 + 1 - T.c, false);
+            ps_step<NP, 1, LPT>(T, q, k + 1, v1, v2, row, col, fval, fset);
+        }
+    }
+    if (fset)
+        out[T.out_idx] = fval;
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT)
+k_ps_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
+         const double *__restrict__ tabs, double *__restrict__ out, int ring_ld)
+{
+    extern __shared__ __attribute__((aligned(16))) double ps_ring[];
+    const int q = threadIdx.x;
+    const DPTask T = tasks[blockIdx.x];
+    double *ring = ps_ring;
+    for (int e = q; e < 4 * ring_ld; e += NT)
+        ring[e] = -RF_INF;
+    auto sync = [] {
+        if (NT > 64)
+            lds_barrier();
+        else
+            wave_sync();
+    };
+    sync();
+    const bool skew = T.flags & 2;
+    const bool trim = T.flags & 4;
+    const uint8_t *sbase = bases + T.sb;
+    const uint8_t *tbase = bases + T.tb;
+    const double *tb = tabs + T.tab;
+    const double *t_match = tb;
+    const double *t_mism = tb + T.n;
+    const double *t_ins = tb + 2 * (size_t)T.n;
+    const double *t_del = tb + 3 * (size_t)T.n;
+    const double *t_cins = tb + 4 * (size_t)T.n + 1;
+    const double *t_cdel = t_cins + T.ncins;
+    bool bad = false;    // "new score is invalid" in a cell of this lane
+    double fval = 0.0;   // the final cell (the lane that computes it)
+    bool fset = false;
+
+    for (int k = 0; k < T.klen; ++k) {
+        const int par = k & 1;
+        double *r0 = ring + (k & 3) * ring_ld + 3;
+        const double *r1 = ring + ((k - 1) & 3) * ring_ld + 3;
+        const double *r2 = ring + ((k - 2) & 3) * ring_ld + 3;
+        const double *r3 = ring + ((k - 3) & 3) * ring_ld + 3;
+        for (int pp = q;; pp += NT) {
+            const int d = 2 * pp + par;
+            if (d >= T.H || d > k)
+                break;
+            const int jj = (k - d) >> 1;
+            double v = -RF_INF;
+            if (jj <= T.m) {
+                const int ii = d + jj - T.c;
+                if (ii >= 0 && ii <= T.n) {
+                    if (ii == 0 && jj == 0) {
+                        v = 0.0;
+                    } else {
+                        // align.jl:64-76 score lookups
+                        const int sb = ii >= 1 ? sbase[ii - 1] : 4;
+                        const int tbb = jj >= 1 ? tbase[jj - 1] : 4;
+                        const int ks = max(ii - 1, 0);
+                        double ms = (sb == tbb) ? t_match[ks] : t_mism[ks];
+                        double is = t_ins[ks];
+                        const double ds = t_del[ii];
+                        if (skew && sb != tbb)
+                            ms *= 0.99;
+                        if (trim && (jj == 0 || jj == T.m))
+                            is = 0.0;
+                        // align.jl:77-104, strict '>' in reference order
+                        double best = -RF_INF, s;
+                        s = r2[d] + ms;
+                        if (s > best) best = s;
+                        s = r1[d - 1] + is;
+                        if (s > best) best = s;
+                        s = r1[d + 1] + ds;
+                        if (s > best) best = s;
+                        if (T.ncins > 0 && ii >= 3) {
+                            s = r3[d - 3] + t_cins[ii - 3];
+                            if (s > best) best = s;
+                        }
+                        if (T.ncdel > 0 && jj >= 3) {
+                            s = r3[d + 3] + t_cdel[ii];
+                            if (s > best) best = s;
+                        }
+                        bad = bad || best == -RF_INF;   // "new score is invalid"
+                        v = best;
+                    }
+                    if (ii == T.n && jj == T.m) {
+                        fval = v;
+                        fset = true;
+                    }
+                }
+            }
+            r0[d] = v;
+        }
+        sync();
+    }
+    // the pair's flag through the ring (no longer read): NaN for a pair the
+    // reference raises on
+    if (q == 0)
+        ring[0] = 0.0;
+    sync();
+    if (bad)
+        ring[0] = 1.0;
+    sync();
+    if (fset)
+        out[T.out_idx] = ring[0] != 0.0 ? __builtin_nan("") : fval;
 }
 
 // ---------------------------------------------------------------------
@@ -4640,6 +5028,7 @@ struct Opts {
     int dp_pfit = 1;        // RF_OPT_DP_PFIT: lean NP >= 2 class launched at its tasks' stride class
     int dp_lat = 2048;      // RF_OPT_DP_LAT: a call with at most this many lean H <= 127 tasks runs them all as
                             // one k_dpx launch (latency mode: the launch cannot fill the GPU)
+    int pair_chunk = PS_CHUNK;   // RF_OPT_PAIR_CHUNK: pairs per launch set of rf_pair_scores
 };
 
 }  // namespace
@@ -4667,7 +5056,7 @@ struct rf_ctx {
     // a plan validated at the current epoch with the same job / slot list
     // needs no per-slot validation again
     uint64_t state_epoch = 1;
-    DevBuf scratch[28];
+    DevBuf scratch[30];   // 28, 29: rf_pair_scores' descriptors and scores
     // pinned host staging for sequence uploads (pageable H2D copies of a few
     // MB took ~14 ms per cluster upload on the box: page locking per call)
     void *pinned = nullptr;
@@ -4688,6 +5077,7 @@ struct rf_ctx {
     int *d_err = nullptr;
     double dp_ms = 0, score_ms = 0, gather_ms = 0, bt_ms = 0;
     double codon_ms = 0;        // k_codon of the last rf_score (inside score_ms)
+    double pair_ms = 0;         // kernels of the last rf_pair_scores
     hipEvent_t ev_codon = nullptr;
     hipEvent_t ev_block = nullptr;   // blocking-sync event (RF_OPT_SYNC_BLOCK)
     Opts opt;
@@ -5231,6 +5621,8 @@ int rf_create(int device, rf_ctx **out)
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)k_dp<DPW_NT, false, DPW_NT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void *)k_ps_gen<DPW_NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
     *out = ctx;
     return 0;
 }
@@ -5311,6 +5703,7 @@ static int *opt_slot(rf_ctx *ctx, int32_t key)
     case RF_OPT_DP_PFIT: return &o.dp_pfit;
     case RF_OPT_DP_MC: return &o.dp_mc;
     case RF_OPT_BT_NW: return &o.bt_nw;
+    case RF_OPT_PAIR_CHUNK: return &o.pair_chunk;
     default: return nullptr;
     }
 }
@@ -6482,6 +6875,136 @@ int rf_realign_jobs(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32
                     const int32_t *bw, const int32_t *flags, double *out_score)
 {
     return realign_impl(ctx, njobs, slot, seq, tpl, bw, flags, out_score);
+}
+
+// Score-only forward pass of independent pairs (k_ps / k_ps_gen).  Reads the
+// sequence and template arenas only: no slot, no band, no band bookkeeping.
+// Pairs go to the device RF_OPT_PAIR_CHUNK at a time (descriptors in
+// scratch[28], scores in scratch[29]), so device memory does not grow with
+// npairs; within a chunk they are sorted into width classes like rf_realign's
+// tasks, longest first.
+int rf_pair_scores(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
+                   int32_t flags, double *out)
+{
+    if (!ctx || npairs < 0 || (npairs > 0 && (!seq || !tpl || !bw || !out)))
+        return fail(ctx, RF_ERR_ARG, "rf_pair_scores: bad arguments");
+    if (flags & RF_BWD)
+        return fail(ctx, RF_ERR_ARG, "rf_pair_scores: RF_BWD is not supported (forward scores only)");
+    if (flags & ~(RF_FWD | RF_SKEW | RF_TRIM))
+        return fail(ctx, RF_ERR_ARG, "rf_pair_scores: unknown flags");
+    (void)hipSetDevice(ctx->device);
+    ctx->pair_ms = 0;
+    for (int64_t k = 0; k < npairs; ++k) {
+        if (seq[k] < 0 || seq[k] >= (int32_t)ctx->seqs.size() || !ctx->seqs[seq[k]].valid || tpl[k] < 0 ||
+            tpl[k] >= (int32_t)ctx->tpls.size() || !ctx->tpls[tpl[k]].valid)
+            return fail(ctx, RF_ERR_ARG, "rf_pair_scores: unknown sequence / template");
+        if (bw[k] < 1)
+            return fail(ctx, RF_ERR_ARG, "bandwidth must be positive");
+        const int64_t H = 2 * (int64_t)bw[k] + std::abs((int64_t)ctx->seqs[seq[k]].n - ctx->tpls[tpl[k]].m) + 1;
+        if (H > DPW_LDS_H)
+            return fail(ctx, RF_ERR_ARG,
+                        "rf_pair_scores: band of " + std::to_string(H) + " rows is wider than the " +
+                            std::to_string(DPW_LDS_H) + " a score-only pass holds in LDS");
+    }
+    const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
+    const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
+    const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
+    const double *d_tabs = (const double *)ctx->tab_arena.d;
+    const double *d_lut = (const double *)ctx->codes.lut.p;
+    std::vector<DPTask> cf[4], c64, cg, all;
+    for (int64_t p0 = 0; p0 < npairs; p0 += chunk) {
+        const int64_t cn = std::min(chunk, npairs - p0);
+        for (auto &c : cf)
+            c.clear();
+        c64.clear();
+        cg.clear();
+        int hmax64 = 0, hmaxg = 0;
+        for (int64_t k = p0; k < p0 + cn; ++k) {
+            const SeqObj &S = ctx->seqs[seq[k]];
+            const TplObj &T = ctx->tpls[tpl[k]];
+            DPTask t{};
+            t.sb = S.bases.off;
+            t.tab = S.tabs.off / 8;
+            t.tb = T.bases.off;
+            t.n = S.n;
+            t.m = T.m;
+            t.bw = bw[k];
+            t.H = band_rows(S.n + 1, T.m + 1, bw[k]);
+            t.c = std::max(T.m - S.n, 0) + bw[k];
+            t.ncins = S.ncins;
+            t.ncdel = S.ncdel;
+            t.flags = fl | (S.coded ? RF_TASK_CODED : 0);
+            t.out_idx = (int32_t)(k - p0);
+            t.klen = t.H + 2 * t.m;
+            // fast tier: k_dpr's lean condition, bands that live in registers
+            const bool lean = S.ncins == 0 && S.ncdel == 0 && S.finite && !fl;
+            if (lean && t.H <= PS_FAST_H)
+                cf[t.H <= 31 ? 0 : t.H <= 63 ? 1 : t.H <= 127 ? 2 : 3].push_back(t);
+            else if (t.H <= PS_GEN64_H) {
+                c64.push_back(t);
+                hmax64 = std::max(hmax64, t.H);
+            } else {
+                cg.push_back(t);
+                hmaxg = std::max(hmaxg, t.H);
+            }
+        }
+        auto by_len = [](const DPTask &x, const DPTask &y) { return x.klen > y.klen; };
+        all.clear();
+        size_t at[7] = {};
+        {
+            int i = 0;
+            for (std::vector<DPTask> *c : {&cf[0], &cf[1], &cf[2], &cf[3], &c64, &cg}) {
+                std::stable_sort(c->begin(), c->end(), by_len);
+                at[i++] = all.size();
+                all.insert(all.end(), c->begin(), c->end());
+            }
+            at[6] = all.size();
+        }
+        if (int e = upload(ctx, ctx->scratch[28], all))
+            return e;
+        if (int e = ensure_buf(ctx, ctx->scratch[29], sizeof(double) * (size_t)cn))
+            return e;
+        if (int e = ensure_hdn(ctx, sizeof(double) * (size_t)cn))
+            return e;
+        const DPTask *d_tasks = (const DPTask *)ctx->scratch[28].p;
+        double *d_out = (double *)ctx->scratch[29].p;
+        HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+        using KFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, const double *);
+        // H <= 31, 63, 127 as 16-lane tasks of 1, 2, 4 band-row pairs per lane, H <= PS_FAST_H as
+        // 64-lane tasks of 2 (k_dpr's wide class: 8 pairs per lane in 16 lanes leave one wave per SIMD)
+        const KFn kf[4] = {k_ps<1>, k_ps<2>, k_ps<4>, k_ps<2, 64>};
+        for (int a = 0; a < 4; ++a)
+            if (const int n = (int)cf[a].size()) {
+                const int tpw = a == 3 ? 1 : 4;
+                hipLaunchKernelGGL(kf[a], dim3((n + tpw - 1) / tpw), dim3(64), 0, ctx->stream, d_tasks + at[a], n,
+                                   d_bases, d_tabs, d_out, d_lut);
+            }
+        if (!c64.empty())
+            hipLaunchKernelGGL(k_ps_gen<64>, dim3((unsigned)c64.size()), dim3(64), 4 * (size_t)(hmax64 + 6) * 8,
+                               ctx->stream, d_tasks + at[4], d_bases, d_tabs, d_out, hmax64 + 6);
+        if (!cg.empty())
+            hipLaunchKernelGGL(k_ps_gen<DPW_NT>, dim3((unsigned)cg.size()), dim3(DPW_NT),
+                               4 * (size_t)(hmaxg + 6) * 8, ctx->stream, d_tasks + at[5], d_bases, d_tabs, d_out,
+                               hmaxg + 6);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync((char *)ctx->hdn + HDN_RES, d_out, sizeof(double) * (size_t)cn,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, stream_wait(ctx));
+        std::memcpy(out + p0, (const char *)ctx->hdn + HDN_RES, sizeof(double) * (size_t)cn);
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
+        ctx->pair_ms += ms;
+    }
+    return 0;
+}
+
+int rf_last_pair_ms(const rf_ctx *ctx, double *ms)
+{
+    if (!ctx || !ms)
+        return RF_ERR_ARG;
+    *ms = ctx->pair_ms;
+    return 0;
 }
 
 // Launch the backtraces of `tasks` (moves into scratch[3] at t.out, counts in

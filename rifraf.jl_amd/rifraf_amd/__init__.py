@@ -32,6 +32,9 @@ def __getattr__(name):
     if name in ("align", "align_moves", "forward", "backward", "forward_moves", "edit_distance"):
         from . import align
         return getattr(align, name)
+    if name in ("cross_scores", "choose_references"):
+        from . import assign
+        return getattr(assign, name)
     if name in ("sample_sequences", "sample_mixture", "sample_from_template", "sample_reference",
                 "random_seq"):
         from . import sample

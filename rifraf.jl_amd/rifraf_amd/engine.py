@@ -346,6 +346,28 @@ class Engine:
                                                  ptr(fl), ptr(out)))
         return out[:n]
 
+    def pair_scores(self, seqs, tpls, bws, flags=0) -> np.ndarray:
+        """rf_pair_scores: A[end,end] of forward! for independent (sequence,
+        template, bandwidth) pairs, without bands or slots -- the value
+        realign(..., RF_FWD | flags) returns, bit for bit.  seqs / tpls / bws
+        broadcast against each other; flags: 0 or RF_SKEW / RF_TRIM.  A pair
+        the reference raises on ("new score is invalid") is NaN."""
+        seqs, tpls, bws = np.broadcast_arrays(np.asarray(seqs), np.asarray(tpls), np.asarray(bws))
+        shape = seqs.shape
+        seqs = np.ascontiguousarray(seqs.reshape(-1), np.int32)
+        tpls = np.ascontiguousarray(tpls.reshape(-1), np.int32)
+        bws = np.ascontiguousarray(bws.reshape(-1), np.int32)
+        n = seqs.shape[0]
+        out = np.empty(max(n, 1))
+        self._check(self.lib.rf_pair_scores(self.ctx, n, ptr(seqs), ptr(tpls), ptr(bws), int(flags), ptr(out)))
+        return out[:n].reshape(shape)
+
+    def last_pair_ms(self) -> float:
+        """Kernel ms of the last pair_scores call (all its chunks)."""
+        v = c_double()
+        self._check(self.lib.rf_last_pair_ms(self.ctx, byref(v)))
+        return v.value
+
     def backtrace(self, slots, want_moves: bool = True):
         """backtrace + count_errors of each slot's A band.
         Returns (list of int8 move arrays in alignment order, nerrors)."""
