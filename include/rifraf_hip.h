@@ -13,6 +13,9 @@
  *                        realign! src/model.jl:679-714
  *   rf_pair_scores    <- forward!(...)[end, end] over many pairs
  *                        src/align.jl:155-179
+ *   rf_pair_align     <- backtrace(forward_moves(...)[2]) + count_errors over
+ *                        many pairs (align_moves, align, edit_distance,
+ *                        correct_shifts)  src/align.jl:114-153,229-260
  *   rf_backtrace      <- backtrace + count_errors   src/align.jl:229-245
  *   rf_alignment_proposals <- alignment_proposals / moves_to_proposals
  *                        src/model.jl:458-497
@@ -145,6 +148,9 @@ const char *rf_last_error(const rf_ctx *ctx);
 #define RF_OPT_PAIR_CHUNK  32   /* rf_pair_scores: pairs per launch set (default
                                    65536); descriptors and scores of one chunk are
                                    all the device memory the call needs         */
+#define RF_OPT_PAIR_TRACE_MB 33 /* rf_pair_align: device bytes of move trace per
+                                   launch set, MB (default 1024); a set also holds
+                                   at most RF_OPT_PAIR_CHUNK pairs                */
 /* Keys 3, 5-8, 14 and 20 selected scorer variants measured slower and removed
    in round 3 (k_score_lean, the 128-lane k_score_ws, k_score_seg /
    k_score_segc, 16-diagonal k_score_segl, the unspecialised k_score_w2);
@@ -267,6 +273,29 @@ int rf_pair_scores(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_
                    const int32_t *bw, int32_t flags, double *out);
 /* Kernel time of the last rf_pair_scores call (all its chunks), milliseconds. */
 int rf_last_pair_ms(const rf_ctx *ctx, double *ms);
+
+/* Alignments of npairs independent pairs without bands or slots: pair k is
+ * backtrace(forward_moves(tpl[k], seq[k]; bandwidth bw[k], trim,
+ * skew_matches)[2]) (align.jl:144-153, 229-238).  Its moves, in alignment
+ * order and in rf_backtrace's int8 codes, go to moves[moves_off[k] ...]
+ * (capacity n + m), their count to nmoves[k], count_errors (align.jl:240-245)
+ * to nerrors[k] and A[end, end] -- the bits rf_pair_scores returns -- to
+ * out_score[k].  Any output pointer may be NULL; moves and moves_off are NULL
+ * together.  The fill keeps the scores on chip and writes a 4-bit move per
+ * band cell (1/16 of an FP64 band); a walk follows the moves.
+ * flags, id checks, bw < 1 and the band limit are rf_pair_scores' (RF_FWD
+ * implied, RF_BWD is RF_ERR_ARG).  A pair the reference raises on ("new score
+ * is invalid") gets score NaN, nmoves = nerrors = -1 and no moves; the call
+ * still returns 0.  The call touches no slot, makes no band stale or fresh and
+ * does not move the band arena.  Pairs go out in launch sets of at most
+ * RF_OPT_PAIR_CHUNK pairs and RF_OPT_PAIR_TRACE_MB of trace (a single pair
+ * above the budget runs alone), so device memory does not grow with npairs. */
+int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl,
+                  const int32_t *bw, int32_t flags, double *out_score,
+                  int8_t *moves, const int64_t *moves_off, int32_t *nmoves, int32_t *nerrors);
+/* Kernel time of the last rf_pair_align call (all its sets), milliseconds:
+ * the fills and the walks.  Either pointer may be NULL. */
+int rf_last_pair_align_ms(const rf_ctx *ctx, double *fill_ms, double *walk_ms);
 
 /* Backtrace of the A band of each slot (align.jl:229-238), moves in
  * alignment order written at moves[moves_off[k] ...] (capacity n+m each);

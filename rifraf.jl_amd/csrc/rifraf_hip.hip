@@ -14,6 +14,9 @@
 //               (rf_pair_scores): A[end,end] without a band; register tier
 //               (k_dpr's systolic step, no stores) and LDS-ring tier (k_dp's)
 //               src/align.jl:155-179
+//   k_pa / k_pa_gen / k_pa_walk  alignments of independent pairs
+//               (rf_pair_align): k_ps / k_ps_gen writing a 4-bit move per
+//               cell, and a walk over the moves  src/align.jl:114-153,229-245
 //   k_score_ws / k_score_segl / k_score
 //               dense per-position proposal scoring of every batch read,
 //               left-folded over the batch in batch order
@@ -1641,6 +1644,521 @@ k_ps_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
     sync();
     if (fset)
         out[T.out_idx] = ring[0] != 0.0 ? __builtin_nan("") : fval;
+}
+
+// ---------------------------------------------------------------------
+// k_pa / k_pa_gen / k_pa_walk: alignments of independent pairs without FP64
+// bands (rf_pair_align): forward_moves! + backtrace + count_errors
+// (align.jl:114-153, 229-245).
+//
+// The fills are k_ps / k_ps_gen with one addition: each cell's move -- the
+// first candidate that is strictly greater, in the order match, insert,
+// delete, codon insert, codon delete (align.jl:77-104) -- goes into a 4-bit
+// trace.  The score stays the fmax value (k_ps) or the strict-> chain
+// (k_ps_gen), so out[] holds the bits rf_pair_scores returns.
+//
+// Trace of one pair: cell (d, jj) has kappa = d + 2 jj and period
+// p = kappa >> 1; its move is nibble p & 15 of the 64-bit word
+// tr[(p >> 4) * HP + d], HP = H rounded up to even (pa_hp), for
+// pa_blocks(klen) blocks of 16 periods.  A lane gathers the 16 periods of a
+// diagonal it owns in a register pair and the lanes of a task store the HP
+// words of a block as one contiguous run of 16-B vector stores; every word
+// of every block is stored, cells outside the DP as 0 (TRACE_NONE).
+//
+// k_pa<NP, LPT>: k_ps's tier.  The lean interior starts at a multiple of 32
+// anti-diagonals, so one PS_B-period block is one trace word per diagonal
+// and words are flushed at block ends only; the border steps flush after
+// every 16th period.
+// k_pa_gen<NT, NPP>: k_ps_gen's tier.  Thread q owns the diagonal pairs
+// q, q + NT, ... (NPP of them at most: one word pair each, in registers).
+//
+// k_pa_walk: one lane per pair, from (n, m) to (0, 0), reading trace nibbles
+// in place (a word serves up to 16 consecutive matches: they stay on one
+// diagonal) and the two base strings for the mismatch count.  At most n + m
+// steps; TRACE_NONE, an unknown code, a cell off the band or a step that
+// would leave the matrix ends the walk with nmoves = nerrors = -1.  Moves are
+// written end-aligned in the pair's n + m slot like k_bt_win's.  NaN pairs
+// are not walked.
+// ---------------------------------------------------------------------
+constexpr int PA_TRACE_MB = 1024;   // RF_OPT_PAIR_TRACE_MB's default
+__host__ __device__ inline int pa_hp(int H) { return (H + 1) & ~1; }
+__host__ __device__ inline int pa_blocks(int klen) { return (((klen + 1) >> 1) + 15) >> 4; }
+// diagonal pairs per thread of k_pa_gen: 2 NT NPP >= pa_hp(widest band of the tier)
+constexpr int PA_NPP64 = (PS_GEN64_H + 1 + 127) / 128;
+constexpr int PA_NPPW = (DPW_LDS_H + 1 + 2 * DPW_NT - 1) / (2 * DPW_NT);
+
+// ps_step + the cell's move (strict '>' in reference order) into nibble (k >> 1) & 15
+template <int NP, int PAR, int LPT>
+__device__ __forceinline__ void pa_step(const DPTask &T, int q, int k, double (&v1)[NP], double (&v2)[NP],
+                                        const RowRec (&row)[NP], const int (&col)[NP], double &fval, int &fset,
+                                        uint64_t (&w)[NP])
+{
+    const double E1 = PAR == 0 ? dpp_f64<TaskLanes<LPT>::FROM_L1>(v1[NP - 1])
+                               : dpp_f64<TaskLanes<LPT>::FROM_R1>(v1[0]);
+    const bool live = k < T.klen;
+    const int sh = 4 * ((k >> 1) & 15);
+    double nv[NP];
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+        const int d = 2 * (q * NP + r) + PAR;
+        const int jj = (k - d) >> 1;
+        const int ii = d + jj - T.c;
+        const bool valid = live && d < T.H && d <= k && jj <= T.m && ii >= 0 && ii <= T.n;
+        const RowRec &R = row[r];
+        const double ms = (R.sb == col[r]) ? R.mt : R.mm;
+        const double x_ins = PAR ? v1[r] : (r > 0 ? v1[r > 0 ? r - 1 : 0] : E1);
+        const double x_del = PAR ? (r < NP - 1 ? v1[r < NP - 1 ? r + 1 : 0] : E1) : v1[r];
+        const double cm = v2[r] + ms, ci = x_ins + R.is, cd = x_del + R.ds;
+        const double best = fmax(fmax(cm, ci), cd);
+        int mv = 0;
+        double b = -RF_INF;
+        if (cm > b) { b = cm; mv = 1; }
+        if (ci > b) { b = ci; mv = 2; }
+        if (cd > b) { mv = 3; }
+        const bool org = ii == 0 && jj == 0;
+        const double v = valid ? (org ? 0.0 : best) : -RF_INF;
+        mv = (valid && !org) ? mv : 0;
+        w[r] |= (uint64_t)mv << sh;
+        const bool fin = valid && ii == T.n && jj == T.m;
+        fval = fin ? v : fval;
+        fset |= fin ? 1 : 0;
+        nv[r] = v;
+    }
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+        v2[r] = v1[r];
+        v1[r] = nv[r];
+    }
+}
+
+// ps_lean_step + the move into nibble p (a constant once unrolled) of a
+// 4-period accumulator: two compares and selects on the candidates; a masked
+// diagonal (-Inf) carries 0
+template <int NP, int PAR, int LPT>
+__device__ __forceinline__ void pa_lean_step(double (&v1)[NP], double (&v2)[NP], const RowRec (&row)[NP],
+                                             const int (&col)[NP], const double (&lb)[NP], uint32_t (&w)[NP],
+                                             const int p)
+{
+    const double E1 = PAR == 0 ? dpp_rot_f64<TaskLanes<LPT>::ROT_L1>(v1[NP - 1])
+                               : dpp_rot_f64<TaskLanes<LPT>::ROT_R1>(v1[0]);
+    double nv[NP];
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+        const RowRec &R = row[r];
+        const double ms = (R.sb == col[r]) ? R.mt : R.mm;
+        const double x_ins = PAR ? v1[r] : (r > 0 ? v1[r > 0 ? r - 1 : 0] : E1);
+        const double x_del = PAR ? (r < NP - 1 ? v1[r < NP - 1 ? r + 1 : 0] : E1) : v1[r];
+        const double cm = v2[r] + ms, ci = x_ins + R.is, cd = x_del + R.ds;
+        const double t = fmax(cm, ci);
+        nv[r] = fmax(t, cd) + lb[r];
+        int mv = ci > cm ? 2 : 1;
+        mv = cd > t ? 3 : mv;
+        mv = nv[r] == -RF_INF ? 0 : mv;
+        w[r] |= (uint32_t)mv << (4 * p);
+    }
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+        v2[r] = v1[r];
+        v1[r] = nv[r];
+    }
+}
+
+template <int NP, int LPT = 16>
+__global__ void __launch_bounds__(64)
+k_pa(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+     const double *__restrict__ tabs, double *__restrict__ out, const double *__restrict__ lut,
+     uint64_t *__restrict__ trace)
+{
+    static_assert(LPT == 16 || LPT == 64, "k_pa tasks are 16 or 64 lanes");
+    __shared__ EdgeRec s_edge[64 / LPT][PS_B];
+    const int q = threadIdx.x & (LPT - 1);
+    const int t = threadIdx.x / LPT;
+    const int tid = blockIdx.x * (64 / LPT) + t;
+    DPTask T = {};   // a padding task: pad (its trace blocks) = 0, nothing stored
+    if (tid < ntasks)
+        T = tasks[tid];
+    int kmax = T.klen;
+    for (int off = 32; off >= 1; off >>= 1)
+        kmax = max(kmax, __shfl_xor(kmax, off));
+    kmax = __builtin_amdgcn_readfirstlane(kmax);
+    const uint8_t *sbase = bases + T.sb;
+    const uint8_t *tbase = bases + T.tb;
+    const double *tb = tabs + T.tab;
+
+    double v1[NP], v2[NP];
+    RowRec row[NP];
+    int col[NP];
+    uint64_t w[2][NP];   // the open trace words of diagonals 2 (q NP + r) + par
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+        v1[r] = -RF_INF;
+        v2[r] = -RF_INF;
+        w[0][r] = w[1][r] = 0;
+        const int pp = q * NP + r;
+        row[r] = load_row(T, false, sbase, tb, pp - T.c, false);   // kappa = 0
+        col[r] = load_col(T, false, tbase, -pp);
+    }
+    const int top = LPT * NP - 1;
+    RowRec nq = load_row(T, false, sbase, tb, top + 1 - T.c, false);   // enters at kappa = 1
+    int cq = load_col(T, false, tbase, 1);                             // enters at kappa = 2
+    double fval = 0.0;
+    int fset = 0;
+    // block b of the task's trace: diagonals 2 (q NP + r), + 1 as one 16-B store
+    uint64_t *trp = trace + T.band;
+    auto flush = [&](int b) {
+#pragma unroll
+        for (int r = 0; r < NP; ++r) {
+            const int d = 2 * (q * NP + r);
+            if (b < T.pad && d < T.P)
+                *(ulonglong2 *)(trp + (size_t)b * T.P + d) = make_ulonglong2(w[0][r], w[1][r]);
+            w[0][r] = w[1][r] = 0;
+        }
+    };
+
+    // lean interior [klo, khi] of the wave's tasks (k_ps), klo at a trace-word boundary
+    int klo = INT_MAX, khi = -1;
+    double lb[2][NP];
+    {
+        int lo = 0, hi = INT_MAX;
+        bool ok = true;
+#pragma unroll
+        for (int par = 0; par < 2; ++par)
+#pragma unroll
+            for (int r = 0; r < NP; ++r) {
+                const int d = 2 * (q * NP + r) + par;
+                const int jlo = max(0, T.c - d), jhi = min(T.m, T.n + T.c - d);
+                const bool a = tid < ntasks && d < T.H && jlo <= jhi;
+                lb[par][r] = a ? 0.0 : -RF_INF;
+                if (a) {
+                    lo = max(lo, d + 2 * jlo);
+                    hi = min(hi, d + 2 * jhi);
+                }
+            }
+        if (tid < ntasks) {
+            lo = max(lo, T.c + 1);
+            hi = min(hi, T.klen - 2);
+            ok = T.c <= T.m;
+        }
+        for (int off = 32; off >= 1; off >>= 1) {
+            lo = max(lo, __shfl_xor(lo, off));
+            hi = min(hi, __shfl_xor(hi, off));
+        }
+        if (__all(ok)) {
+            klo = __builtin_amdgcn_readfirstlane((lo + 2 * PS_B - 1) & ~(2 * PS_B - 1));
+            khi = __builtin_amdgcn_readfirstlane(hi);
+        }
+    }
+    const int nblk = khi >= klo ? (khi - klo + 1) / (2 * PS_B) : 0;
+    int open_blk = -1;   // the trace block the border steps have written into, not flushed yet
+
+    for (int k = 0; k < kmax; k += 2) {
+        if (k == klo && nblk > 0) {
+            // (k - 2) & 31 == 30: the border steps flushed their last block
+            EdgeRec *ein = s_edge[t];
+            const int top_c = LPT * NP - T.c;
+            const bool coded = T.flags & RF_TASK_CODED;
+            const uint64_t *codes = (const uint64_t *)(tb + row_code_off(T.n, T.ncins, T.ncdel));
+            const int ql = min(q, PS_B - 1);
+            auto edge_ks = [&](int kb) {
+                const int ii = max(1, min(top_c + (kb >> 1) + ql, T.n));
+                return ii - 1;
+            };
+            auto code_load = [&](int kb) -> uint64_t { return coded ? codes[edge_ks(kb)] : 0; };
+            auto edge_load = [&](int kb, uint64_t rec) {
+                EdgeRec e;
+                const int ks = edge_ks(kb);
+                if (coded) {
+                    const double *l3 = lut + 4 * (int)(rec & 0xffff);
+                    const dvec2 mt_mm = *(const dvec2 *)l3;
+                    e.mt = mt_mm.x;
+                    e.mm = mt_mm.y;
+                    e.is = l3[2];
+                    e.ds = lut[4 * RF_CODES + (int)((rec >> 32) & 0xffff)];
+                    e.sb = (int)(rec >> 48) & 0xff;
+                } else {
+                    e.sb = sbase[ks];
+                    e.mt = tb[ks];
+                    e.mm = tb[T.n + ks];
+                    e.is = tb[2 * (size_t)T.n + ks];
+                    e.ds = tb[3 * (size_t)T.n + ks + 1];
+                }
+                const int jj = max(1, min((kb >> 1) + ql, T.m));
+                e.col = tbase[jj - 1];
+                e.pad0 = e.pad1 = 0;
+                return e;
+            };
+            {
+                const EdgeRec first = edge_load(k, code_load(k));
+                if (q < PS_B)
+                    ein[q] = first;
+            }
+            EdgeRec pend = edge_load(k + 2 * PS_B, code_load(k + 2 * PS_B));
+            uint64_t pcode = code_load(k + 4 * PS_B);
+            wave_sync();
+            for (int b = 0; b < nblk; ++b) {
+                EdgeRec E = ein[0];
+                // 4 periods unrolled at a time (all 16 at once, the scheduler hoists every
+                // period's row / column moves and match selects and runs out of registers);
+                // their moves gather in 16 bits and join the trace word once
+#pragma unroll 1
+                for (int p4 = 0; p4 < PS_B; p4 += 4) {
+                    uint32_t acc[2][NP];
+#pragma unroll
+                    for (int r = 0; r < NP; ++r)
+                        acc[0][r] = acc[1][r] = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const EdgeRec En = ein[min(p4 + j + 1, PS_B - 1)];   // one period ahead (LDS latency)
+                        {
+                            const int from = __builtin_amdgcn_update_dpp(E.col, col[NP - 1], TaskLanes<LPT>::FROM_L1,
+                                                                         0xF, 0xF, false);
+#pragma unroll
+                            for (int r = NP - 1; r > 0; --r)
+                                col[r] = col[r - 1];
+                            col[0] = from;
+                        }
+                        pa_lean_step<NP, 0, LPT>(v1, v2, row, col, lb[0], acc[0], j);
+                        {
+                            RowRec e;
+                            e.sb = E.sb;
+                            e.mt = E.mt;
+                            e.mm = E.mm;
+                            e.is = E.is;
+                            e.ds = E.ds;
+                            e.ci = e.cd = -RF_INF;
+                            const RowRec up = row_from_above<LPT>(row[0], e, false);
+#pragma unroll
+                            for (int r = 0; r < NP - 1; ++r)
+                                row[r] = row[r + 1];
+                            row[NP - 1] = up;
+                        }
+                        pa_lean_step<NP, 1, LPT>(v1, v2, row, col, lb[1], acc[1], j);
+                        E = En;
+                    }
+#pragma unroll
+                    for (int r = 0; r < NP; ++r) {
+                        w[0][r] |= (uint64_t)acc[0][r] << (4 * p4);
+                        w[1][r] |= (uint64_t)acc[1][r] << (4 * p4);
+                    }
+                }
+                flush(k >> 5);   // the block's 16 periods are one trace word per diagonal
+                wave_sync();
+                if (q < PS_B)
+                    ein[q] = pend;
+                pend = edge_load(k + 4 * PS_B, pcode);
+                pcode = code_load(k + 6 * PS_B);
+                wave_sync();
+                k += 2 * PS_B;
+            }
+            nq = load_row(T, false, sbase, tb, top + k / 2 + 1 - T.c, false);
+            cq = load_col(T, false, tbase, k / 2);
+            if (k >= kmax)
+                break;
+        }
+        if (k > 0) {
+            const int edge = cq;
+            cq = load_col(T, false, tbase, k / 2 + 1);
+            const int from = __builtin_amdgcn_update_dpp(edge, col[NP - 1], TaskLanes<LPT>::FROM_L1, 0xF, 0xF, false);
+#pragma unroll
+            for (int r = NP - 1; r > 0; --r)
+                col[r] = col[r - 1];
+            col[0] = from;
+        }
+        open_blk = k >> 5;
+        pa_step<NP, 0, LPT>(T, q, k, v1, v2, row, col, fval, fset, w[0]);
+        if (k + 1 < kmax) {
+            const RowRec up = row_from_above<LPT>(row[0], nq, false);
+#pragma unroll
+            for (int r = 0; r < NP - 1; ++r)
+                row[r] = row[r + 1];
+            row[NP - 1] = up;
+            nq = load_row(T, false, sbase, tb, top + (k + 2) / 2 + 1 - T.c, false);
+            pa_step<NP, 1, LPT>(T, q, k + 1, v1, v2, row, col, fval, fset, w[1]);
+        }
+        if ((k & 31) == 30) {
+            flush(open_blk);
+            open_blk = -1;
+        }
+    }
+    if (open_blk >= 0)
+        flush(open_blk);
+    if (fset)
+        out[T.out_idx] = fval;
+}
+
+template <int NT, int NPP>
+__global__ void __launch_bounds__(NT)
+k_pa_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
+         const double *__restrict__ tabs, double *__restrict__ out, uint64_t *__restrict__ trace, int ring_ld)
+{
+    extern __shared__ __attribute__((aligned(16))) double ps_ring[];
+    const int q = threadIdx.x;
+    const DPTask T = tasks[blockIdx.x];
+    double *ring = ps_ring;
+    for (int e = q; e < 4 * ring_ld; e += NT)
+        ring[e] = -RF_INF;
+    auto sync = [] {
+        if (NT > 64)
+            lds_barrier();
+        else
+            wave_sync();
+    };
+    sync();
+    const bool skew = T.flags & 2;
+    const bool trim = T.flags & 4;
+    const uint8_t *sbase = bases + T.sb;
+    const uint8_t *tbase = bases + T.tb;
+    const double *tb = tabs + T.tab;
+    const double *t_match = tb;
+    const double *t_mism = tb + T.n;
+    const double *t_ins = tb + 2 * (size_t)T.n;
+    const double *t_del = tb + 3 * (size_t)T.n;
+    const double *t_cins = tb + 4 * (size_t)T.n + 1;
+    const double *t_cdel = t_cins + T.ncins;
+    uint64_t *trp = trace + T.band;
+    bool bad = false;
+    double fval = 0.0;
+    bool fset = false;
+    uint64_t w0[NPP], w1[NPP];   // open trace words of diagonals 2 (q + u NT), + 1
+    const int nu = min(NPP, (T.H + 2 * NT - 1) / (2 * NT));   // diagonal pairs per thread in use (uniform)
+#pragma unroll
+    for (int u = 0; u < NPP; ++u)
+        w0[u] = w1[u] = 0;
+
+    for (int k = 0; k < T.klen; ++k) {
+        const int par = k & 1;
+        const int sh = 4 * ((k >> 1) & 15);
+        double *r0 = ring + (k & 3) * ring_ld + 3;
+        const double *r1 = ring + ((k - 1) & 3) * ring_ld + 3;
+        const double *r2 = ring + ((k - 2) & 3) * ring_ld + 3;
+        const double *r3 = ring + ((k - 3) & 3) * ring_ld + 3;
+#pragma unroll
+        for (int u = 0; u < NPP; ++u) {   // no early exit: unrolled, so w0 / w1 stay in registers
+            const int pp = q + u * NT;
+            const int d = 2 * pp + par;
+            if (u >= nu || d >= T.H || d > k)
+                continue;
+            const int jj = (k - d) >> 1;
+            double v = -RF_INF;
+            int mv = 0;
+            if (jj <= T.m) {
+                const int ii = d + jj - T.c;
+                if (ii >= 0 && ii <= T.n) {
+                    if (ii == 0 && jj == 0) {
+                        v = 0.0;
+                    } else {
+                        const int sb = ii >= 1 ? sbase[ii - 1] : 4;
+                        const int tbb = jj >= 1 ? tbase[jj - 1] : 4;
+                        const int ks = max(ii - 1, 0);
+                        double ms = (sb == tbb) ? t_match[ks] : t_mism[ks];
+                        double is = t_ins[ks];
+                        const double ds = t_del[ii];
+                        if (skew && sb != tbb)
+                            ms *= 0.99;
+                        if (trim && (jj == 0 || jj == T.m))
+                            is = 0.0;
+                        // align.jl:77-104, strict '>' in reference order
+                        double best = -RF_INF, s;
+                        s = r2[d] + ms;
+                        if (s > best) { best = s; mv = 1; }
+                        s = r1[d - 1] + is;
+                        if (s > best) { best = s; mv = 2; }
+                        s = r1[d + 1] + ds;
+                        if (s > best) { best = s; mv = 3; }
+                        if (T.ncins > 0 && ii >= 3) {
+                            s = r3[d - 3] + t_cins[ii - 3];
+                            if (s > best) { best = s; mv = 4; }
+                        }
+                        if (T.ncdel > 0 && jj >= 3) {
+                            s = r3[d + 3] + t_cdel[ii];
+                            if (s > best) { best = s; mv = 5; }
+                        }
+                        bad = bad || best == -RF_INF;
+                        v = best;
+                    }
+                    if (ii == T.n && jj == T.m) {
+                        fval = v;
+                        fset = true;
+                    }
+                }
+            }
+            r0[d] = v;
+            const uint64_t nib = (uint64_t)mv << sh;
+            w0[u] |= par ? 0 : nib;
+            w1[u] |= par ? nib : 0;
+        }
+        if ((k & 31) == 31 || k == T.klen - 1) {
+            // 16 periods done (or the last): the block's HP words, 16 B per thread and diagonal pair
+            uint64_t *blk = trp + (size_t)(k >> 5) * T.P;
+#pragma unroll
+            for (int u = 0; u < NPP; ++u) {
+                const int d = 2 * (q + u * NT);
+                if (d < T.P)
+                    *(ulonglong2 *)(blk + d) = make_ulonglong2(w0[u], w1[u]);
+                w0[u] = w1[u] = 0;
+            }
+        }
+        sync();
+    }
+    if (q == 0)
+        ring[0] = 0.0;
+    sync();
+    if (bad)
+        ring[0] = 1.0;
+    sync();
+    if (fset)
+        out[T.out_idx] = ring[0] != 0.0 ? __builtin_nan("") : fval;
+}
+
+__global__ void __launch_bounds__(64)
+k_pa_walk(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+          const double *__restrict__ scores, const uint64_t *__restrict__ trace, int8_t *__restrict__ moves,
+          const int64_t *__restrict__ moves_off, int32_t *__restrict__ nmoves, int32_t *__restrict__ nerr)
+{
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= ntasks)
+        return;
+    const DPTask T = tasks[t];
+    const int n = T.n, m = T.m, H = T.H, HP = T.P, c = T.c, nb = T.pad;
+    const uint8_t *s = bases + T.sb;
+    const uint8_t *tt = bases + T.tb;
+    const uint64_t *tr = trace + T.band;
+    int8_t *o = moves ? moves + moves_off[T.out_idx] : nullptr;
+    int ii = n, jj = m, cnt = 0, errs = 0;
+    bool ok = !(scores[T.out_idx] != scores[T.out_idx]);   // NaN: the reference raised, no walk
+    int key = -1;
+    uint64_t word = 0;
+    for (int step = 0; ok && step < n + m && (ii > 0 || jj > 0); ++step) {
+        const int d = ii - jj + c, kap = ii + jj + c;
+        const int p = kap >> 1, b = p >> 4;
+        if ((unsigned)d >= (unsigned)H || b >= nb) {
+            ok = false;
+            break;
+        }
+        const int kk = b * HP + d;
+        if (kk != key) {
+            word = tr[kk];
+            key = kk;
+        }
+        const int mv = (int)(word >> (4 * (p & 15))) & 15;
+        const int di = (mv == 1 || mv == 2) ? 1 : (mv == 4 ? 3 : 0);
+        const int dj = (mv == 1 || mv == 3) ? 1 : (mv == 5 ? 3 : 0);
+        if (mv < 1 || mv > 5 || ii < di || jj < dj) {
+            ok = false;
+            break;
+        }
+        const bool mis = mv == 1 && s[ii - 1] != tt[jj - 1];
+        errs += (mv >= 2 || mis) ? 1 : 0;
+        errs += mv >= 4 ? 2 : 0;
+        if (o)
+            o[n + m - 1 - cnt] = (int8_t)mv;
+        ++cnt;
+        ii -= di;
+        jj -= dj;
+    }
+    ok = ok && ii == 0 && jj == 0;
+    nmoves[T.out_idx] = ok ? cnt : -1;
+    nerr[T.out_idx] = ok ? errs : -1;
 }
 
 // ---------------------------------------------------------------------
@@ -5028,7 +5546,8 @@ struct Opts {
     int dp_pfit = 1;        // RF_OPT_DP_PFIT: lean NP >= 2 class launched at its tasks' stride class
     int dp_lat = 2048;      // RF_OPT_DP_LAT: a call with at most this many lean H <= 127 tasks runs them all as
                             // one k_dpx launch (latency mode: the launch cannot fill the GPU)
-    int pair_chunk = PS_CHUNK;   // RF_OPT_PAIR_CHUNK: pairs per launch set of rf_pair_scores
+    int pair_chunk = PS_CHUNK;   // RF_OPT_PAIR_CHUNK: pairs per launch set of rf_pair_scores / rf_pair_align
+    int pair_trace_mb = PA_TRACE_MB;   // RF_OPT_PAIR_TRACE_MB: MB of move trace per launch set of rf_pair_align
 };
 
 }  // namespace
@@ -5056,7 +5575,8 @@ struct rf_ctx {
     // a plan validated at the current epoch with the same job / slot list
     // needs no per-slot validation again
     uint64_t state_epoch = 1;
-    DevBuf scratch[30];   // 28, 29: rf_pair_scores' descriptors and scores
+    DevBuf scratch[34];   // 28, 29: rf_pair_scores' / rf_pair_align's descriptors and scores;
+                          // 30-33: rf_pair_align's trace, moves, move offsets and counts
     // pinned host staging for sequence uploads (pageable H2D copies of a few
     // MB took ~14 ms per cluster upload on the box: page locking per call)
     void *pinned = nullptr;
@@ -5078,6 +5598,7 @@ struct rf_ctx {
     double dp_ms = 0, score_ms = 0, gather_ms = 0, bt_ms = 0;
     double codon_ms = 0;        // k_codon of the last rf_score (inside score_ms)
     double pair_ms = 0;         // kernels of the last rf_pair_scores
+    double pa_fill_ms = 0, pa_walk_ms = 0;   // fills / walks of the last rf_pair_align
     hipEvent_t ev_codon = nullptr;
     hipEvent_t ev_block = nullptr;   // blocking-sync event (RF_OPT_SYNC_BLOCK)
     Opts opt;
@@ -5486,6 +6007,7 @@ void load_env_opts(Opts &o)
     o.dp_pfit = env_int("RIFRAF_DP_PFIT", o.dp_pfit);
     o.dp_mc = env_int("RIFRAF_DP_MC", o.dp_mc);
     o.bt_nw = env_int("RIFRAF_BT_NW", o.bt_nw);
+    o.pair_trace_mb = env_int("RIFRAF_PAIR_TRACE_MB", o.pair_trace_mb);
 }
 
 ScorePick pick_scorer(const Opts &o, const std::vector<ScoreRead> &reads, bool all_finite)
@@ -5623,6 +6145,8 @@ int rf_create(int device, rf_ctx **out)
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)k_ps_gen<DPW_NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               160 * 1024);
+    (void)hipFuncSetAttribute((const void *)k_pa_gen<DPW_NT, PA_NPPW>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
     *out = ctx;
     return 0;
 }
@@ -5704,6 +6228,7 @@ static int *opt_slot(rf_ctx *ctx, int32_t key)
     case RF_OPT_DP_MC: return &o.dp_mc;
     case RF_OPT_BT_NW: return &o.bt_nw;
     case RF_OPT_PAIR_CHUNK: return &o.pair_chunk;
+    case RF_OPT_PAIR_TRACE_MB: return &o.pair_trace_mb;
     default: return nullptr;
     }
 }
@@ -7004,6 +7529,211 @@ int rf_last_pair_ms(const rf_ctx *ctx, double *ms)
     if (!ctx || !ms)
         return RF_ERR_ARG;
     *ms = ctx->pair_ms;
+    return 0;
+}
+
+// Alignments of independent pairs from a 4-bit move trace (k_pa / k_pa_gen,
+// then k_pa_walk).  Like rf_pair_scores it reads the sequence and template
+// arenas only.  Pairs go out in launch sets of at most RF_OPT_PAIR_CHUNK
+// pairs and RF_OPT_PAIR_TRACE_MB of trace (a pair above the budget alone), so
+// the trace (scratch[30]), the moves (31), their offsets (32) and the counts
+// (33) of one set are all the device memory the call needs.
+int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
+                  int32_t flags, double *out_score, int8_t *moves, const int64_t *moves_off, int32_t *nmoves,
+                  int32_t *nerrors)
+{
+    if (!ctx || npairs < 0 || (npairs > 0 && (!seq || !tpl || !bw)) || (!moves != !moves_off))
+        return fail(ctx, RF_ERR_ARG, "rf_pair_align: bad arguments");
+    if (flags & RF_BWD)
+        return fail(ctx, RF_ERR_ARG, "rf_pair_align: RF_BWD is not supported (forward alignments only)");
+    if (flags & ~(RF_FWD | RF_SKEW | RF_TRIM))
+        return fail(ctx, RF_ERR_ARG, "rf_pair_align: unknown flags");
+    (void)hipSetDevice(ctx->device);
+    ctx->pa_fill_ms = ctx->pa_walk_ms = 0;
+    for (int64_t k = 0; k < npairs; ++k) {
+        if (seq[k] < 0 || seq[k] >= (int32_t)ctx->seqs.size() || !ctx->seqs[seq[k]].valid || tpl[k] < 0 ||
+            tpl[k] >= (int32_t)ctx->tpls.size() || !ctx->tpls[tpl[k]].valid)
+            return fail(ctx, RF_ERR_ARG, "rf_pair_align: unknown sequence / template");
+        if (bw[k] < 1)
+            return fail(ctx, RF_ERR_ARG, "bandwidth must be positive");
+        const int64_t H = 2 * (int64_t)bw[k] + std::abs((int64_t)ctx->seqs[seq[k]].n - ctx->tpls[tpl[k]].m) + 1;
+        if (H > DPW_LDS_H)
+            return fail(ctx, RF_ERR_ARG,
+                        "rf_pair_align: band of " + std::to_string(H) + " rows (pair " + std::to_string(k) +
+                            ") is wider than the " + std::to_string(DPW_LDS_H) + " a bandless pass holds in LDS");
+    }
+    const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
+    const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
+    const int64_t budget = (int64_t)std::max(ctx->opt.pair_trace_mb, 1) << 20;   // bytes of trace per set
+    const bool walk = moves || nmoves || nerrors;
+    const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
+    const double *d_tabs = (const double *)ctx->tab_arena.d;
+    const double *d_lut = (const double *)ctx->codes.lut.p;
+    auto trace_words = [&](int64_t k) {
+        const SeqObj &S = ctx->seqs[seq[k]];
+        const TplObj &T = ctx->tpls[tpl[k]];
+        const int H = band_rows(S.n + 1, T.m + 1, bw[k]);
+        return (int64_t)pa_blocks(H + 2 * T.m) * pa_hp(H);
+    };
+    std::vector<DPTask> cf[4], c64, cg, all;
+    std::vector<int64_t> mvoff;
+    for (int64_t p0 = 0; p0 < npairs;) {
+        // the set [p0, p0 + cn): at least one pair, then while both bounds hold
+        int64_t cn = 0, words = 0;
+        while (p0 + cn < npairs && cn < chunk) {
+            const int64_t w = trace_words(p0 + cn);
+            if (cn > 0 && (words + w) * 8 > budget)
+                break;
+            words += w;
+            ++cn;
+        }
+        for (auto &c : cf)
+            c.clear();
+        c64.clear();
+        cg.clear();
+        mvoff.assign((size_t)cn, 0);
+        int hmax64 = 0, hmaxg = 0;
+        int64_t tr_at = 0, mv_total = 0;
+        for (int64_t k = p0; k < p0 + cn; ++k) {
+            const SeqObj &S = ctx->seqs[seq[k]];
+            const TplObj &T = ctx->tpls[tpl[k]];
+            DPTask t{};
+            t.sb = S.bases.off;
+            t.tab = S.tabs.off / 8;
+            t.tb = T.bases.off;
+            t.n = S.n;
+            t.m = T.m;
+            t.bw = bw[k];
+            t.H = band_rows(S.n + 1, T.m + 1, bw[k]);
+            t.c = std::max(T.m - S.n, 0) + bw[k];
+            t.ncins = S.ncins;
+            t.ncdel = S.ncdel;
+            t.flags = fl | (S.coded ? RF_TASK_CODED : 0);
+            t.out_idx = (int32_t)(k - p0);
+            t.klen = t.H + 2 * t.m;
+            t.band = tr_at;               // the pair's trace: 64-bit words from scratch[30]
+            t.P = pa_hp(t.H);             // words per 16-period block
+            t.pad = pa_blocks(t.klen);    // blocks
+            tr_at += (int64_t)t.pad * t.P;
+            mvoff[(size_t)(k - p0)] = mv_total;
+            mv_total += S.n + T.m;
+            // rf_pair_scores' routing
+            const bool lean = S.ncins == 0 && S.ncdel == 0 && S.finite && !fl;
+            if (lean && t.H <= PS_FAST_H)
+                cf[t.H <= 31 ? 0 : t.H <= 63 ? 1 : t.H <= 127 ? 2 : 3].push_back(t);
+            else if (t.H <= PS_GEN64_H) {
+                c64.push_back(t);
+                hmax64 = std::max(hmax64, t.H);
+            } else {
+                cg.push_back(t);
+                hmaxg = std::max(hmaxg, t.H);
+            }
+        }
+        auto by_len = [](const DPTask &x, const DPTask &y) { return x.klen > y.klen; };
+        all.clear();
+        size_t at[7] = {};
+        {
+            int i = 0;
+            for (std::vector<DPTask> *c : {&cf[0], &cf[1], &cf[2], &cf[3], &c64, &cg}) {
+                std::stable_sort(c->begin(), c->end(), by_len);
+                at[i++] = all.size();
+                all.insert(all.end(), c->begin(), c->end());
+            }
+            at[6] = all.size();
+        }
+        const bool want_mv = moves != nullptr;
+        // downloads: scores, then nmoves and nerrors, then the moves
+        const size_t cb = sizeof(double) * (size_t)cn, nbytes = sizeof(int32_t) * 2 * (size_t)cn;
+        const size_t mv_at = (cb + nbytes + 15) & ~(size_t)15;
+        if (int e = upload(ctx, ctx->scratch[28], all))
+            return e;
+        if (int e = ensure_buf(ctx, ctx->scratch[29], cb))
+            return e;
+        if (int e = ensure_buf(ctx, ctx->scratch[30], (size_t)std::max<int64_t>(tr_at, 2) * 8))
+            return e;
+        if (walk) {
+            if (want_mv) {
+                if (int e = ensure_buf(ctx, ctx->scratch[31], (size_t)std::max<int64_t>(mv_total, 16)))
+                    return e;
+                if (int e = upload(ctx, ctx->scratch[32], mvoff))
+                    return e;
+            }
+            if (int e = ensure_buf(ctx, ctx->scratch[33], nbytes))
+                return e;
+        }
+        if (int e = ensure_hdn(ctx, mv_at + (want_mv ? (size_t)mv_total : 0)))
+            return e;
+        const DPTask *d_tasks = (const DPTask *)ctx->scratch[28].p;
+        double *d_out = (double *)ctx->scratch[29].p;
+        uint64_t *d_tr = (uint64_t *)ctx->scratch[30].p;
+        int32_t *d_cnt = (int32_t *)ctx->scratch[33].p;
+        HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+        using KFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, const double *,
+                             uint64_t *);
+        const KFn kf[4] = {k_pa<1>, k_pa<2>, k_pa<4>, k_pa<2, 64>};
+        for (int a = 0; a < 4; ++a)
+            if (const int n = (int)cf[a].size()) {
+                const int tpw = a == 3 ? 1 : 4;
+                hipLaunchKernelGGL(kf[a], dim3((n + tpw - 1) / tpw), dim3(64), 0, ctx->stream, d_tasks + at[a], n,
+                                   d_bases, d_tabs, d_out, d_lut, d_tr);
+            }
+        if (!c64.empty())
+            hipLaunchKernelGGL((k_pa_gen<64, PA_NPP64>), dim3((unsigned)c64.size()), dim3(64),
+                               4 * (size_t)(hmax64 + 6) * 8, ctx->stream, d_tasks + at[4], d_bases, d_tabs, d_out,
+                               d_tr, hmax64 + 6);
+        if (!cg.empty())
+            hipLaunchKernelGGL((k_pa_gen<DPW_NT, PA_NPPW>), dim3((unsigned)cg.size()), dim3(DPW_NT),
+                               4 * (size_t)(hmaxg + 6) * 8, ctx->stream, d_tasks + at[5], d_bases, d_tabs, d_out,
+                               d_tr, hmaxg + 6);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        if (walk) {
+            hipLaunchKernelGGL(k_pa_walk, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, ctx->stream, d_tasks,
+                               (int)cn, d_bases, (const double *)d_out, (const uint64_t *)d_tr,
+                               want_mv ? (int8_t *)ctx->scratch[31].p : nullptr,
+                               (const int64_t *)ctx->scratch[32].p, d_cnt, d_cnt + cn);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+        char *h = (char *)ctx->hdn + HDN_RES;
+        HIPCHK(ctx, hipMemcpyAsync(h, d_out, cb, hipMemcpyDeviceToHost, ctx->stream));
+        if (walk)
+            HIPCHK(ctx, hipMemcpyAsync(h + cb, d_cnt, nbytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (want_mv && mv_total > 0)
+            HIPCHK(ctx, hipMemcpyAsync(h + mv_at, ctx->scratch[31].p, (size_t)mv_total, hipMemcpyDeviceToHost,
+                                       ctx->stream));
+        HIPCHK(ctx, stream_wait(ctx));
+        if (out_score)
+            std::memcpy(out_score + p0, h, cb);
+        const int32_t *cnt = (const int32_t *)(h + cb);
+        for (int64_t k = 0; k < cn && walk; ++k) {
+            if (nmoves)
+                nmoves[p0 + k] = cnt[k];
+            if (nerrors)
+                nerrors[p0 + k] = cnt[cn + k];
+            if (want_mv && cnt[k] > 0) {   // the walk leaves the moves at the end of the pair's n + m slot
+                const int64_t len = (k + 1 < cn ? mvoff[(size_t)k + 1] : mv_total) - mvoff[(size_t)k];
+                std::memcpy(moves + moves_off[p0 + k], h + mv_at + mvoff[(size_t)k] + len - cnt[k], (size_t)cnt[k]);
+            }
+        }
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
+        ctx->pa_fill_ms += ms;
+        (void)hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]);
+        ctx->pa_walk_ms += ms;
+        p0 += cn;
+    }
+    return 0;
+}
+
+int rf_last_pair_align_ms(const rf_ctx *ctx, double *fill_ms, double *walk_ms)
+{
+    if (!ctx)
+        return RF_ERR_ARG;
+    if (fill_ms)
+        *fill_ms = ctx->pa_fill_ms;
+    if (walk_ms)
+        *walk_ms = ctx->pa_walk_ms;
     return 0;
 }
 

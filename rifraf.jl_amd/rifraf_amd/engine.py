@@ -368,6 +368,50 @@ class Engine:
         self._check(self.lib.rf_last_pair_ms(self.ctx, byref(v)))
         return v.value
 
+    def pair_align(self, seqs, tpls, bws, flags=0, want_moves: bool = True, caps=None):
+        """rf_pair_align: backtrace(forward_moves(...)) + count_errors of
+        independent (sequence, template, bandwidth) pairs, without bands or
+        slots.  seqs / tpls / bws broadcast as in pair_scores.  caps: n + m
+        of each pair when the caller knows them (else a counts-only call
+        comes first).  Returns
+        (scores, moves, nerrors) over the flattened pairs: scores are
+        pair_scores' bits; moves is a list of int8 arrays in alignment order
+        (None with want_moves=False); a pair the reference raises on has score
+        NaN, moves None and nerrors -1."""
+        seqs, tpls, bws = np.broadcast_arrays(np.asarray(seqs), np.asarray(tpls), np.asarray(bws))
+        seqs = np.ascontiguousarray(seqs.reshape(-1), np.int32)
+        tpls = np.ascontiguousarray(tpls.reshape(-1), np.int32)
+        bws = np.ascontiguousarray(bws.reshape(-1), np.int32)
+        n = seqs.shape[0]
+        scores = np.empty(max(n, 1))
+        nmoves = np.empty(max(n, 1), np.int32)
+        nerr = np.empty(max(n, 1), np.int32)
+        moves = moves_off = None
+        if want_moves:
+            if caps is None:
+                # the engine knows the lengths, this object does not: a first
+                # call for the counts alone sizes the move buffer exactly
+                self._check(self.lib.rf_pair_align(self.ctx, n, ptr(seqs), ptr(tpls), ptr(bws), int(flags), None,
+                                                   None, None, ptr(nmoves), None))
+                caps = np.maximum(nmoves[:n], 0)
+            caps = np.broadcast_to(np.asarray(caps, np.int64).reshape(-1), (n,))
+            moves_off = np.zeros(n + 1, np.int64)
+            np.cumsum(caps, out=moves_off[1:])
+            moves = np.empty(max(int(moves_off[-1]), 1), np.int8)
+        self._check(self.lib.rf_pair_align(self.ctx, n, ptr(seqs), ptr(tpls), ptr(bws), int(flags), ptr(scores),
+                                           ptr(moves), ptr(moves_off), ptr(nmoves), ptr(nerr)))
+        out = None
+        if want_moves:
+            out = [moves[moves_off[k]:moves_off[k] + nmoves[k]].copy() if nmoves[k] >= 0 else None
+                   for k in range(n)]
+        return scores[:n], out, nerr[:n].copy()
+
+    def last_pair_align_ms(self):
+        """(fill ms, walk ms) of the last pair_align call (all its launch sets)."""
+        f, w = c_double(), c_double()
+        self._check(self.lib.rf_last_pair_align_ms(self.ctx, byref(f), byref(w)))
+        return f.value, w.value
+
     def backtrace(self, slots, want_moves: bool = True):
         """backtrace + count_errors of each slot's A band.
         Returns (list of int8 move arrays in alignment order, nerrors)."""

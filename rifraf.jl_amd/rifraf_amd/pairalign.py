@@ -1,0 +1,163 @@
+"""Alignments of many pairs in one engine call (rf_pair_align).
+
+The pairwise half of the reference's API over lists: align_moves / align
+(src/align.jl:337-353), edit_distance (:253-260) and the loop of
+scripts/correct_shifts.jl (:61-68, correct_shifts model.jl:1303-1316).  The
+engine fills each pair with the scores on chip, keeps a 4-bit move per band
+cell and walks it: no FP64 band, no slot.  align.py's one-pair functions and
+model.correct_shifts keep their slot path; the results are the same.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from .align import moves_to_aligned_seqs
+from .engine import RF_SKEW, RF_TRIM, RifrafError
+from .errormodel import ErrorModel, Scores
+from .proposals import Deletion, Insertion, apply_proposals
+from .rifrafsequences import RifrafSequence
+from .types import DNASeq
+
+MAX_BAND_ROWS = 160 * 1024 // 32 - 6   # DPW_LDS_H: the widest band a bandless pass holds in LDS
+
+
+def _engine(engine):
+    if engine is not None:
+        return engine
+    from .align import default_engine
+    return default_engine()
+
+
+def _pairs(pairs, nseq, ntpl):
+    if pairs is None:
+        if nseq != ntpl:
+            raise ValueError(f"{nseq} sequences and {ntpl} templates: give pairs=(sequence, template) indices")
+        k = np.arange(nseq, dtype=np.int64)
+        return k, k
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    if len(pairs) and (pairs.min() < 0 or pairs[:, 0].max() >= nseq or pairs[:, 1].max() >= ntpl):
+        raise ValueError("pairs: index out of range")
+    return pairs[:, 0], pairs[:, 1]
+
+
+def _run(e, seqs, templates, si, ti, bws, flags, want_moves):
+    """One rf_pair_align call over pairs (si[k], ti[k]); sequences and
+    templates are uploaded as ids 0.. of the engine."""
+    if len(si) == 0:
+        return np.empty(0), ([] if want_moves else None), np.empty(0, np.int32)
+    slen = np.array([len(s) for s in seqs], np.int64)
+    tlen = np.array([len(t) for t in templates], np.int64)
+    bws = np.broadcast_to(np.asarray(bws, np.int64), si.shape)
+    rows = 2 * bws + np.abs(slen[si] - tlen[ti]) + 1
+    wide = np.nonzero(rows > MAX_BAND_ROWS)[0]
+    if len(wide):
+        k = int(wide[0])
+        raise RifrafError(f"pair {k} (sequence {int(si[k])}, template {int(ti[k])}): band of {int(rows[k])} rows "
+                          f"is wider than the {MAX_BAND_ROWS} the engine aligns without bands")
+    e.set_sequences(0, seqs)
+    e.set_templates(0, templates)
+    return e.pair_align(si, ti, bws, flags, want_moves=want_moves, caps=slen[si] + tlen[ti])
+
+
+def align_moves_many(seqs, templates, pairs=None, bandwidth=None, skew_matches=False, trim=False, engine=None):
+    """align_moves(templates[j], seqs[i]) (align.jl:337-344) for every (i, j)
+    of `pairs` ((N, 2) indices; default k with k), in one engine call.
+    bandwidth=None uses each sequence's own.  -> list of int8 move arrays in
+    alignment order; None for a pair the reference raises on."""
+    seqs = list(seqs)
+    templates = [DNASeq(t) for t in templates]
+    si, ti = _pairs(pairs, len(seqs), len(templates))
+    if bandwidth is None:
+        bws = np.array([s.bandwidth for s in seqs], np.int64)[si]
+    else:
+        bws = np.full(si.shape, int(bandwidth), np.int64)
+    flags = (RF_SKEW if skew_matches else 0) | (RF_TRIM if trim else 0)
+    _, moves, _ = _run(_engine(engine), seqs, templates, si, ti, bws, flags, True)
+    return moves
+
+
+def align_many(seqs, templates, pairs=None, bandwidth=None, skew_matches=False, trim=False, engine=None):
+    """align (align.jl:346-353) per pair -> [(aligned t, aligned s)] with '-'
+    gaps; None for a pair the reference raises on."""
+    seqs = list(seqs)
+    templates = [DNASeq(t) for t in templates]
+    si, ti = _pairs(pairs, len(seqs), len(templates))
+    moves = align_moves_many(seqs, templates, pairs=pairs, bandwidth=bandwidth, skew_matches=skew_matches,
+                             trim=trim, engine=engine)
+    return [None if mv is None else moves_to_aligned_seqs(mv, templates[int(j)], seqs[int(i)].seq)
+            for mv, i, j in zip(moves, si, ti)]
+
+
+def edit_distances(templates, seqs, engine=None) -> np.ndarray:
+    """edit_distance(templates[k], seqs[k]) (align.jl:253-260) for bare base
+    sequences: log p = -1, ErrorModel(1, 1, 1), bandwidth ceil(min(m, n) / 2),
+    skewed alignment, count_errors.  One engine call."""
+    templates = [DNASeq(t) for t in templates]
+    seqs = [DNASeq(s) for s in seqs]
+    if len(templates) != len(seqs):
+        raise ValueError("edit_distances: one template per sequence")
+    scores = Scores.from_errors(ErrorModel(1.0, 1.0, 1.0))
+    rs, bws = [], []
+    for t, s in zip(templates, seqs):
+        bw = int(math.ceil(min(len(t), len(s)) * 0.5))
+        rs.append(RifrafSequence(s, np.full(len(s), -1.0), bw, scores))
+        bws.append(bw)
+    k = np.arange(len(seqs), dtype=np.int64)
+    _, _, nerr = _run(_engine(engine), rs, templates, k, k, np.array(bws, np.int64), RF_SKEW, False)
+    return nerr
+
+
+def _single_indels(moves, refseq):
+    """single_indel_proposals' walk (model.jl:538-562) over one move list."""
+    out = []
+    cons_idx = ref_idx = 0
+    for mv in moves.tolist():
+        if mv == 1:
+            cons_idx += 1
+            ref_idx += 1
+        elif mv == 2:
+            ref_idx += 1
+            out.append(Insertion(cons_idx, int(refseq[ref_idx - 1])))
+        elif mv == 3:
+            cons_idx += 1
+            out.append(Deletion(cons_idx))
+        elif mv == 4:
+            ref_idx += 3
+        elif mv == 5:
+            cons_idx += 3
+    return out
+
+
+def correct_shifts_many(consensuses, references, log_p=-1.0, bandwidth=-1, scores=None, engine=None):
+    """correct_shifts (model.jl:1303-1316) of every consensus against its
+    reference -- one reference for all, or one per consensus -- as the loop
+    of scripts/correct_shifts.jl:61-68 does, in one engine call: the skewed
+    codon alignment of single_indel_proposals (the reference is the
+    sequence, the consensus the template), then apply_proposals."""
+    scores = scores or Scores.from_errors(ErrorModel(10.0, 1e-5, 1e-5, 1.0, 1.0))
+    consensuses = [DNASeq(c) for c in consensuses]
+    if isinstance(references, str) or (isinstance(references, np.ndarray) and references.ndim == 1):
+        references = [references]
+    references = [DNASeq(r) for r in references]
+    if len(references) == 1:
+        references = references * len(consensuses)
+    if len(references) != len(consensuses):
+        raise ValueError("correct_shifts_many: one reference, or one per consensus")
+    rs = []
+    for c, r in zip(consensuses, references):
+        bw = bandwidth if bandwidth >= 0 else int(math.ceil(min(len(c), len(r)) * 0.1))
+        rs.append(RifrafSequence(r, np.full(len(r), log_p), bw, scores))
+    k = np.arange(len(consensuses), dtype=np.int64)
+    bws = np.array([s.bandwidth for s in rs], np.int64)
+    _, moves, _ = _run(_engine(engine), rs, consensuses, k, k, bws, RF_SKEW, True)
+    out = []
+    for i, (c, s, mv) in enumerate(zip(consensuses, rs, moves)):
+        if mv is None:
+            raise RifrafError(f"pair {i}: new score is invalid")
+        out.append(apply_proposals(c, _single_indels(mv, s.seq)))
+    return out
+
+
+__all__ = ["align_moves_many", "align_many", "edit_distances", "correct_shifts_many", "MAX_BAND_ROWS"]
