@@ -1263,43 +1263,83 @@ k_dpr(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------
-// k_ps / k_ps_gen: score-only forward Viterbi (rf_pair_scores).
+// k_ps / k_ps_gen (rf_pair_scores) and k_pa / k_pa_gen / k_pa_walk
+// (rf_pair_align): forward Viterbi of many independent (sequence, template)
+// pairs without FP64 bands.
 //
-// A[n+1, m+1] of forward! (align.jl:155-179, cell rule :50-112) for many
-// independent (sequence, template) pairs, one double out per pair and no
-// band: only the anti-diagonals kappa-1 and kappa-2 (kappa-3 with codon
-// moves) stay live.  Same candidates and FP64 sums as k_dpr / k_dp, so the
-// value is the one rf_realign(RF_FWD) writes to out_score, bit for bit.
+// The fill is A[n+1, m+1] of forward! (align.jl:155-179, cell rule :50-112),
+// one double out per pair: only the anti-diagonals kappa-1 and kappa-2
+// (kappa-3 with codon moves) stay live.  Same candidates and FP64 sums as
+// k_dpr / k_dp, so the value is the one rf_realign(RF_FWD) writes to
+// out_score, bit for bit.  Each tier is one body (ps_body, ps_gen_body) that
+// both entry points run: k_ps* with TRACE = false, k_pa* with TRACE = true.
 //
-// k_ps<NP, LPT> (fast tier): the lean condition of k_dpr -- no codon tables,
-// finite tables, no skew / trim -- and H <= 2*LPT*NP - 1 <= PS_FAST_H.  Four
-// 16-lane tasks per wave (NP = 1, 2, 4: H <= 31, 63, 127) or one 64-lane task
-// (NP = 2: H <= 255); the anti-diagonals, row records and template
-// bases move systolically by DPP exactly as in k_dpr (dpr_step / dpl_step
-// without their stores).  The lean interior takes its edge records (the row
-// entering lane 15, the column entering lane 0) from a PS_B-period LDS
-// block that the task's lanes load one block ahead, one record per lane, from
-// the row codes + dictionary or the tables; that block (768 B per task) is
-// the kernel's only LDS, and with no band stores nothing else waits on
+// ps_body<NP, LPT, TRACE> (fast tier): the lean condition of k_dpr -- no
+// codon tables, finite tables, no skew / trim -- and H <= 2*LPT*NP - 1 <=
+// PS_FAST_H.  Four 16-lane tasks per wave (NP = 1, 2, 4: H <= 31, 63, 127) or
+// one 64-lane task (NP = 2: H <= 255); the anti-diagonals, row records and
+// template bases move systolically by DPP exactly as in k_dpr (dpr_step /
+// dpl_step without their stores).  The lean interior takes its edge records
+// (the row entering lane 15, the column entering lane 0) from a PS_B-period
+// LDS block that the task's lanes load one block ahead, one record per lane,
+// from the row codes + dictionary or the tables; that block (768 B per task)
+// is the kernel's only LDS, and with no band stores nothing else waits on
 // memory.  Finite tables make every in-band cell finite (dpl_step's note),
 // so "new score is invalid" cannot fire in this tier.  The final cell is
 // kept in a register (fval / fset) and stored once after the loop.
 //
-// k_ps_gen<NT> (general tier): everything else up to H <= DPW_LDS_H --
-// codon tables, RF_SKEW, RF_TRIM, -Inf table entries, wide bands -- as
-// k_dp's LDS-ring recurrence with the band stores removed, one pair per
-// workgroup of NT threads.  A pair with an invalid cell (align.jl:105-110)
-// gets NaN; its neighbours are untouched and no error word is raised.
+// ps_gen_body<NT, NPP, TRACE> (general tier): everything else up to
+// H <= DPW_LDS_H -- codon tables, RF_SKEW, RF_TRIM, -Inf table entries, wide
+// bands -- as k_dp's LDS-ring recurrence with the band stores removed, one
+// pair per workgroup of NT threads; thread q owns the diagonal pairs q,
+// q + NT, ... (NPP of them at most).  A pair with an invalid cell
+// (align.jl:105-110) gets NaN; its neighbours are untouched and no error
+// word is raised.
+//
+// What TRACE adds (forward_moves!, align.jl:114-153): each cell's move --
+// the first candidate that is strictly greater, in the order match, insert,
+// delete, codon insert, codon delete (align.jl:77-104) -- goes into a 4-bit
+// trace.  The score stays the fmax value (fast tier) or the strict-> chain
+// (general tier) of the same expression, so out[] holds the same bits.
+// Trace of one pair: cell (d, jj) has kappa = d + 2 jj and period
+// p = kappa >> 1; its move is nibble p & 15 of the 64-bit word
+// tr[(p >> 4) * HP + d], HP = H rounded up to even (pa_hp), for
+// pa_blocks(klen) blocks of 16 periods.  A lane gathers the 16 periods of a
+// diagonal it owns in a register pair and the lanes of a task store the HP
+// words of a block as one contiguous run of 16-B vector stores; every word
+// of every block is stored, cells outside the DP as 0 (TRACE_NONE).  In the
+// fast tier the lean interior then starts at a multiple of 32 anti-diagonals
+// (2 without the trace), so one PS_B-period block is one trace word per
+// diagonal and words are flushed at block ends only; the border steps flush
+// after every 16th period.  In the general tier the loop over a thread's
+// diagonal pairs is unrolled, so their open words stay in registers.
+//
+// k_pa_walk (backtrace + count_errors, align.jl:229-245): one lane per pair,
+// from (n, m) to (0, 0), reading trace nibbles in place (a word serves up to
+// 16 consecutive matches: they stay on one diagonal) and the two base strings
+// for the mismatch count.  At most n + m steps; TRACE_NONE, an unknown code,
+// a cell off the band or a step that would leave the matrix ends the walk
+// with nmoves = nerrors = -1.  Moves are written end-aligned in the pair's
+// n + m slot like k_bt_win's.  NaN pairs are not walked.
 // ---------------------------------------------------------------------
-constexpr int PS_B = 16;           // periods per edge-record block of k_ps (one record per lane)
+constexpr int PS_B = 16;           // periods per edge-record block of the fast tier (one record per lane)
 constexpr int PS_FAST_H = 255;     // widest band of the fast tier (k_ps<2, 64>)
 constexpr int PS_GEN64_H = 2040;   // widest band of the one-wave general tier (ring < 64 KB); above: DPW_NT threads
 constexpr int PS_CHUNK = 65536;    // pairs per launch set of rf_pair_scores (RF_OPT_PAIR_CHUNK's default)
+constexpr int PA_TRACE_MB = 1024;  // RF_OPT_PAIR_TRACE_MB's default
+__host__ __device__ inline int pa_hp(int H) { return (H + 1) & ~1; }
+__host__ __device__ inline int pa_blocks(int klen) { return (((klen + 1) >> 1) + 15) >> 4; }
+// diagonal pairs per thread of the general tier: 2 NT NPP >= pa_hp(widest band of the tier)
+constexpr int PA_NPP64 = (PS_GEN64_H + 1 + 127) / 128;
+constexpr int PA_NPPW = (DPW_LDS_H + 1 + 2 * DPW_NT - 1) / (2 * DPW_NT);
 
-// dpr_step without codon moves, skew / trim and stores (borders of the matrix)
-template <int NP, int PAR, int LPT>
+// dpr_step without codon moves, skew / trim and stores (borders of the
+// matrix).  TRACE: the cell's move (strict '>' in reference order) goes into
+// nibble (k >> 1) & 15 of w
+template <int NP, int PAR, int LPT, bool TRACE>
 __device__ __forceinline__ void ps_step(const DPTask &T, int q, int k, double (&v1)[NP], double (&v2)[NP],
-                                        const RowRec (&row)[NP], const int (&col)[NP], double &fval, int &fset)
+                                        const RowRec (&row)[NP], const int (&col)[NP], double &fval, int &fset,
+                                        uint64_t (&w)[NP])
 {
     const double E1 = PAR == 0 ? dpp_f64<TaskLanes<LPT>::FROM_L1>(v1[NP - 1])
                                : dpp_f64<TaskLanes<LPT>::FROM_R1>(v1[0]);
@@ -1315,8 +1355,19 @@ __device__ __forceinline__ void ps_step(const DPTask &T, int q, int k, double (&
         const double ms = (R.sb == col[r]) ? R.mt : R.mm;
         const double x_ins = PAR ? v1[r] : (r > 0 ? v1[r > 0 ? r - 1 : 0] : E1);
         const double x_del = PAR ? (r < NP - 1 ? v1[r < NP - 1 ? r + 1 : 0] : E1) : v1[r];
-        const double best = fmax(fmax(v2[r] + ms, x_ins + R.is), x_del + R.ds);
-        const double v = valid ? ((ii == 0 && jj == 0) ? 0.0 : best) : -RF_INF;
+        const double cm = v2[r] + ms, ci = x_ins + R.is, cd = x_del + R.ds;
+        const double best = fmax(fmax(cm, ci), cd);
+        const bool org = ii == 0 && jj == 0;
+        const double v = valid ? (org ? 0.0 : best) : -RF_INF;
+        if constexpr (TRACE) {
+            int mv = 0;
+            double b = -RF_INF;
+            if (cm > b) { b = cm; mv = 1; }
+            if (ci > b) { b = ci; mv = 2; }
+            if (cd > b) { mv = 3; }
+            mv = (valid && !org) ? mv : 0;
+            w[r] |= (uint64_t)mv << (4 * ((k >> 1) & 15));
+        }
         const bool fin = valid && ii == T.n && jj == T.m;
         fval = fin ? v : fval;
         fset |= fin ? 1 : 0;
@@ -1329,10 +1380,13 @@ __device__ __forceinline__ void ps_step(const DPTask &T, int q, int k, double (&
     }
 }
 
-// dpl_step without its LDS stores (the lean interior)
-template <int NP, int PAR, int LPT>
+// dpl_step without its LDS stores (the lean interior).  TRACE: the move goes
+// into nibble p (a constant once unrolled) of a 4-period accumulator: two
+// compares and selects on the candidates; a masked diagonal (-Inf) carries 0
+template <int NP, int PAR, int LPT, bool TRACE>
 __device__ __forceinline__ void ps_lean_step(double (&v1)[NP], double (&v2)[NP], const RowRec (&row)[NP],
-                                             const int (&col)[NP], const double (&lb)[NP])
+                                             const int (&col)[NP], const double (&lb)[NP], uint32_t (&w)[NP],
+                                             const int p)
 {
     const double E1 = PAR == 0 ? dpp_rot_f64<TaskLanes<LPT>::ROT_L1>(v1[NP - 1])
                                : dpp_rot_f64<TaskLanes<LPT>::ROT_R1>(v1[0]);
@@ -1343,7 +1397,15 @@ __device__ __forceinline__ void ps_lean_step(double (&v1)[NP], double (&v2)[NP],
         const double ms = (R.sb == col[r]) ? R.mt : R.mm;
         const double x_ins = PAR ? v1[r] : (r > 0 ? v1[r > 0 ? r - 1 : 0] : E1);
         const double x_del = PAR ? (r < NP - 1 ? v1[r < NP - 1 ? r + 1 : 0] : E1) : v1[r];
-        nv[r] = fmax(fmax(v2[r] + ms, x_ins + R.is), x_del + R.ds) + lb[r];
+        const double cm = v2[r] + ms, ci = x_ins + R.is, cd = x_del + R.ds;
+        const double t = fmax(cm, ci);
+        nv[r] = fmax(t, cd) + lb[r];
+        if constexpr (TRACE) {
+            int mv = ci > cm ? 2 : 1;
+            mv = cd > t ? 3 : mv;
+            mv = nv[r] == -RF_INF ? 0 : mv;
+            w[r] |= (uint32_t)mv << (4 * p);
+        }
     }
 #pragma unroll
     for (int r = 0; r < NP; ++r) {
@@ -1352,18 +1414,19 @@ __device__ __forceinline__ void ps_lean_step(double (&v1)[NP], double (&v2)[NP],
     }
 }
 
-template <int NP, int LPT = 16>
-__global__ void __launch_bounds__(64)
-k_ps(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
-     const double *__restrict__ tabs, double *__restrict__ out, const double *__restrict__ lut)
+template <int NP, int LPT, bool TRACE>
+__device__ __forceinline__ void ps_body(const DPTask *__restrict__ tasks, int ntasks,
+                                        const uint8_t *__restrict__ bases, const double *__restrict__ tabs,
+                                        double *__restrict__ out, const double *__restrict__ lut,
+                                        uint64_t *__restrict__ trace)
 {
     // 16 lanes per task, or the whole wave (wave_shr / wave_shl moves: no edge fix, TaskLanes)
-    static_assert(LPT == 16 || LPT == 64, "k_ps tasks are 16 or 64 lanes");
+    static_assert(LPT == 16 || LPT == 64, "fast-tier tasks are 16 or 64 lanes");
     __shared__ EdgeRec s_edge[64 / LPT][PS_B];
     const int q = threadIdx.x & (LPT - 1);
     const int t = threadIdx.x / LPT;
     const int tid = blockIdx.x * (64 / LPT) + t;
-    DPTask T = {};
+    DPTask T = {};   // a padding task: pad (its trace blocks) = 0, nothing stored
     if (tid < ntasks)
         T = tasks[tid];
     int kmax = T.klen;
@@ -1377,10 +1440,13 @@ k_ps(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ b
     double v1[NP], v2[NP];
     RowRec row[NP];
     int col[NP];
+    uint64_t w[2][NP];   // TRACE: the open trace words of diagonals 2 (q NP + r) + par
 #pragma unroll
     for (int r = 0; r < NP; ++r) {
         v1[r] = -RF_INF;
         v2[r] = -RF_INF;
+        if constexpr (TRACE)
+            w[0][r] = w[1][r] = 0;
         const int pp = q * NP + r;
         row[r] = load_row(T, false, sbase, tb, pp - T.c, false);   // kappa = 0
         col[r] = load_col(T, false, tbase, -pp);
@@ -1390,8 +1456,20 @@ k_ps(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ b
     int cq = load_col(T, false, tbase, 1);                             // enters at kappa = 2
     double fval = 0.0;   // the final cell's score (the lane that computes it)
     int fset = 0;
+    // TRACE: block b of the task's trace, diagonals 2 (q NP + r), + 1 as one 16-B store
+    auto flush = [&](int b) {
+        uint64_t *trp = trace + T.band;
+#pragma unroll
+        for (int r = 0; r < NP; ++r) {
+            const int d = 2 * (q * NP + r);
+            if (b < T.pad && d < T.P)
+                *(ulonglong2 *)(trp + (size_t)b * T.P + d) = make_ulonglong2(w[0][r], w[1][r]);
+            w[0][r] = w[1][r] = 0;
+        }
+    };
 
-    // lean interior [klo, khi] of the wave's four tasks (dpr_body)
+    // lean interior [klo, khi] of the wave's tasks (dpr_body); with the trace klo is at a word boundary
+    constexpr int KLO_ALIGN = TRACE ? 2 * PS_B : 2;
     int klo = INT_MAX, khi = -1;
     double lb[2][NP];
     {
@@ -1420,14 +1498,16 @@ k_ps(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ b
             hi = min(hi, __shfl_xor(hi, off));
         }
         if (__all(ok)) {
-            klo = __builtin_amdgcn_readfirstlane((lo + 1) & ~1);
+            klo = __builtin_amdgcn_readfirstlane((lo + KLO_ALIGN - 1) & ~(KLO_ALIGN - 1));
             khi = __builtin_amdgcn_readfirstlane(hi);
         }
     }
     const int nblk = khi >= klo ? (khi - klo + 1) / (2 * PS_B) : 0;
+    int open_blk = -1;   // TRACE: the trace block the border steps have written into, not flushed yet
 
     for (int k = 0; k < kmax; k += 2) {
         if (k == klo && nblk > 0) {
+            // TRACE: (k - 2) & 31 == 30, the border steps flushed their last block
             EdgeRec *ein = s_edge[t];
             const int top_c = LPT * NP - T.c;
             const bool coded = T.flags & RF_TASK_CODED;
@@ -1469,40 +1549,59 @@ k_ps(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ b
             EdgeRec pend = edge_load(k + 2 * PS_B, code_load(k + 2 * PS_B));
             uint64_t pcode = code_load(k + 4 * PS_B);
             wave_sync();
+            // Periods unrolled per pass of the block: all 16 without the trace.  With it 4 (at
+            // 16 the scheduler hoists every period's row / column moves and match selects and
+            // runs out of registers); their moves gather in 16 bits and join the trace word once.
+            constexpr int GRP = TRACE ? 4 : PS_B;
             for (int b = 0; b < nblk; ++b) {
                 EdgeRec E = ein[0];
+#pragma unroll 1
+                for (int p0 = 0; p0 < PS_B; p0 += GRP) {
+                    uint32_t acc[2][NP];
+                    if constexpr (TRACE) {
 #pragma unroll
-                for (int p = 0; p < PS_B; ++p) {
-                    EdgeRec En;
-                    if (p + 1 < PS_B)
-                        En = ein[p + 1];   // read one period ahead (LDS latency)
-                    {   // even step: column k/2 enters lane 0
-                        const int from = __builtin_amdgcn_update_dpp(E.col, col[NP - 1], TaskLanes<LPT>::FROM_L1,
-                                                                     0xF, 0xF, false);
-#pragma unroll
-                        for (int r = NP - 1; r > 0; --r)
-                            col[r] = col[r - 1];
-                        col[0] = from;
+                        for (int r = 0; r < NP; ++r)
+                            acc[0][r] = acc[1][r] = 0;
                     }
-                    ps_lean_step<NP, 0, LPT>(v1, v2, row, col, lb[0]);
-                    {   // odd step: rows advance; lane 15 receives the edge row
-                        RowRec e;
-                        e.sb = E.sb;
-                        e.mt = E.mt;
-                        e.mm = E.mm;
-                        e.is = E.is;
-                        e.ds = E.ds;
-                        e.ci = e.cd = -RF_INF;
-                        const RowRec up = row_from_above<LPT>(row[0], e, false);
 #pragma unroll
-                        for (int r = 0; r < NP - 1; ++r)
-                            row[r] = row[r + 1];
-                        row[NP - 1] = up;
-                    }
-                    ps_lean_step<NP, 1, LPT>(v1, v2, row, col, lb[1]);
-                    if (p + 1 < PS_B)
+                    for (int j = 0; j < GRP; ++j) {
+                        const EdgeRec En = ein[min(p0 + j + 1, PS_B - 1)];   // one period ahead (LDS latency)
+                        {   // even step: column k/2 enters lane 0
+                            const int from = __builtin_amdgcn_update_dpp(E.col, col[NP - 1], TaskLanes<LPT>::FROM_L1,
+                                                                         0xF, 0xF, false);
+#pragma unroll
+                            for (int r = NP - 1; r > 0; --r)
+                                col[r] = col[r - 1];
+                            col[0] = from;
+                        }
+                        ps_lean_step<NP, 0, LPT, TRACE>(v1, v2, row, col, lb[0], acc[0], j);
+                        {   // odd step: rows advance; lane 15 receives the edge row
+                            RowRec e;
+                            e.sb = E.sb;
+                            e.mt = E.mt;
+                            e.mm = E.mm;
+                            e.is = E.is;
+                            e.ds = E.ds;
+                            e.ci = e.cd = -RF_INF;
+                            const RowRec up = row_from_above<LPT>(row[0], e, false);
+#pragma unroll
+                            for (int r = 0; r < NP - 1; ++r)
+                                row[r] = row[r + 1];
+                            row[NP - 1] = up;
+                        }
+                        ps_lean_step<NP, 1, LPT, TRACE>(v1, v2, row, col, lb[1], acc[1], j);
                         E = En;
+                    }
+                    if constexpr (TRACE) {
+#pragma unroll
+                        for (int r = 0; r < NP; ++r) {
+                            w[0][r] |= (uint64_t)acc[0][r] << (4 * p0);
+                            w[1][r] |= (uint64_t)acc[1][r] << (4 * p0);
+                        }
+                    }
                 }
+                if constexpr (TRACE)
+                    flush(k >> 5);   // the block's 16 periods are one trace word per diagonal
                 wave_sync();
                 if (q < PS_B)
                     ein[q] = pend;   // the next block's records, loaded one block ago
@@ -1527,7 +1626,9 @@ k_ps(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ b
                 col[r] = col[r - 1];
             col[0] = from;
         }
-        ps_step<NP, 0, LPT>(T, q, k, v1, v2, row, col, fval, fset);
+        if constexpr (TRACE)
+            open_blk = k >> 5;
+        ps_step<NP, 0, LPT, TRACE>(T, q, k, v1, v2, row, col, fval, fset, w[0]);
         if (k + 1 < kmax) {
             // odd step: rows advance; lane 15 receives the prefetched row
             const RowRec up = row_from_above<LPT>(row[0], nq, false);
@@ -1536,17 +1637,42 @@ k_ps(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ b
                 row[r] = row[r + 1];
             row[NP - 1] = up;
             nq = load_row(T, false, sbase, tb, top + (k + 2) / 2 + 1 - T.c, false);
-            ps_step<NP, 1, LPT>(T, q, k + 1, v1, v2, row, col, fval, fset);
+            ps_step<NP, 1, LPT, TRACE>(T, q, k + 1, v1, v2, row, col, fval, fset, w[1]);
         }
+        if constexpr (TRACE)
+            if ((k & 31) == 30) {
+                flush(open_blk);
+                open_blk = -1;
+            }
     }
+    if constexpr (TRACE)
+        if (open_blk >= 0)
+            flush(open_blk);
     if (fset)
         out[T.out_idx] = fval;
 }
 
-template <int NT>
-__global__ void __launch_bounds__(NT)
-k_ps_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
-         const double *__restrict__ tabs, double *__restrict__ out, int ring_ld)
+template <int NP, int LPT = 16>
+__global__ void __launch_bounds__(64)
+k_ps(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+     const double *__restrict__ tabs, double *__restrict__ out, const double *__restrict__ lut)
+{
+    ps_body<NP, LPT, false>(tasks, ntasks, bases, tabs, out, lut, nullptr);
+}
+
+template <int NP, int LPT = 16>
+__global__ void __launch_bounds__(64)
+k_pa(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+     const double *__restrict__ tabs, double *__restrict__ out, const double *__restrict__ lut,
+     uint64_t *__restrict__ trace)
+{
+    ps_body<NP, LPT, true>(tasks, ntasks, bases, tabs, out, lut, trace);
+}
+
+template <int NT, int NPP, bool TRACE>
+__device__ __forceinline__ void ps_gen_body(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
+                                            const double *__restrict__ tabs, double *__restrict__ out,
+                                            uint64_t *__restrict__ trace, int ring_ld)
 {
     extern __shared__ __attribute__((aligned(16))) double ps_ring[];
     const int q = threadIdx.x;
@@ -1575,6 +1701,15 @@ k_ps_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
     bool bad = false;    // "new score is invalid" in a cell of this lane
     double fval = 0.0;   // the final cell (the lane that computes it)
     bool fset = false;
+    uint64_t w0[NPP], w1[NPP];   // TRACE: open trace words of diagonals 2 (q + u NT), + 1
+    if constexpr (TRACE) {
+#pragma unroll
+        for (int u = 0; u < NPP; ++u)
+            w0[u] = w1[u] = 0;
+    }
+    const int nu = min(NPP, (T.H + 2 * NT - 1) / (2 * NT));   // diagonal pairs per thread in use (uniform)
+    // with the trace the loop over them is unrolled, so w0 / w1 stay in registers
+    constexpr int UNROLL = TRACE ? NPP : 1;
 
     for (int k = 0; k < T.klen; ++k) {
         const int par = k & 1;
@@ -1582,12 +1717,20 @@ k_ps_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
         const double *r1 = ring + ((k - 1) & 3) * ring_ld + 3;
         const double *r2 = ring + ((k - 2) & 3) * ring_ld + 3;
         const double *r3 = ring + ((k - 3) & 3) * ring_ld + 3;
-        for (int pp = q;; pp += NT) {
-            const int d = 2 * pp + par;
-            if (d >= T.H || d > k)
-                break;
+#pragma unroll UNROLL
+        for (int u = 0; u < NPP; ++u) {
+            const int d = 2 * (q + u * NT) + par;
+            if (u >= nu || d >= T.H || d > k) {
+                // d grows with u, so nothing follows: leave the rolled loop; the unrolled one
+                // stays straight-line (a jump out of it costs k_pa_gen<64> five times the SGPR spills)
+                if constexpr (TRACE)
+                    continue;
+                else
+                    break;
+            }
             const int jj = (k - d) >> 1;
             double v = -RF_INF;
+            int mv = 0;   // dead without TRACE
             if (jj <= T.m) {
                 const int ii = d + jj - T.c;
                 if (ii >= 0 && ii <= T.n) {
@@ -1595,458 +1738,6 @@ k_ps_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
                         v = 0.0;
                     } else {
                         // align.jl:64-76 score lookups
-                        const int sb = ii >= 1 ? sbase[ii - 1] : 4;
-                        const int tbb = jj >= 1 ? tbase[jj - 1] : 4;
-                        const int ks = max(ii - 1, 0);
-                        double ms = (sb == tbb) ? t_match[ks] : t_mism[ks];
-                        double is = t_ins[ks];
-                        const double ds = t_del[ii];
-                        if (skew && sb != tbb)
-                            ms *= 0.99;
-                        if (trim && (jj == 0 || jj == T.m))
-                            is = 0.0;
-                        // align.jl:77-104, strict '>' in reference order
-                        double best = -RF_INF, s;
-                        s = r2[d] + ms;
-                        if (s > best) best = s;
-                        s = r1[d - 1] + is;
-                        if (s > best) best = s;
-                        s = r1[d + 1] + ds;
-                        if (s > best) best = s;
-                        if (T.ncins > 0 && ii >= 3) {
-                            s = r3[d - 3] + t_cins[ii - 3];
-                            if (s > best) best = s;
-                        }
-                        if (T.ncdel > 0 && jj >= 3) {
-                            s = r3[d + 3] + t_cdel[ii];
-                            if (s > best) best = s;
-                        }
-                        bad = bad || best == -RF_INF;   // "new score is invalid"
-                        v = best;
-                    }
-                    if (ii == T.n && jj == T.m) {
-                        fval = v;
-                        fset = true;
-                    }
-                }
-            }
-            r0[d] = v;
-        }
-        sync();
-    }
-    // the pair's flag through the ring (no longer read): NaN for a pair the
-    // reference raises on
-    if (q == 0)
-        ring[0] = 0.0;
-    sync();
-    if (bad)
-        ring[0] = 1.0;
-    sync();
-    if (fset)
-        out[T.out_idx] = ring[0] != 0.0 ? __builtin_nan("") : fval;
-}
-
-// ---------------------------------------------------------------------
-// k_pa / k_pa_gen / k_pa_walk: alignments of independent pairs without FP64
-// bands (rf_pair_align): forward_moves! + backtrace + count_errors
-// (align.jl:114-153, 229-245).
-//
-// The fills are k_ps / k_ps_gen with one addition: each cell's move -- the
-// first candidate that is strictly greater, in the order match, insert,
-// delete, codon insert, codon delete (align.jl:77-104) -- goes into a 4-bit
-// trace.  The score stays the fmax value (k_ps) or the strict-> chain
-// (k_ps_gen), so out[] holds the bits rf_pair_scores returns.
-//
-// Trace of one pair: cell (d, jj) has kappa = d + 2 jj and period
-// p = kappa >> 1; its move is nibble p & 15 of the 64-bit word
-// tr[(p >> 4) * HP + d], HP = H rounded up to even (pa_hp), for
-// pa_blocks(klen) blocks of 16 periods.  A lane gathers the 16 periods of a
-// diagonal it owns in a register pair and the lanes of a task store the HP
-// words of a block as one contiguous run of 16-B vector stores; every word
-// of every block is stored, cells outside the DP as 0 (TRACE_NONE).
-//
-// k_pa<NP, LPT>: k_ps's tier.  The lean interior starts at a multiple of 32
-// anti-diagonals, so one PS_B-period block is one trace word per diagonal
-// and words are flushed at block ends only; the border steps flush after
-// every 16th period.
-// k_pa_gen<NT, NPP>: k_ps_gen's tier.  Thread q owns the diagonal pairs
-// q, q + NT, ... (NPP of them at most: one word pair each, in registers).
-//
-// k_pa_walk: one lane per pair, from (n, m) to (0, 0), reading trace nibbles
-// in place (a word serves up to 16 consecutive matches: they stay on one
-// diagonal) and the two base strings for the mismatch count.  At most n + m
-// steps; TRACE_NONE, an unknown code, a cell off the band or a step that
-// would leave the matrix ends the walk with nmoves = nerrors = -1.  Moves are
-// written end-aligned in the pair's n + m slot like k_bt_win's.  NaN pairs
-// are not walked.
-// ---------------------------------------------------------------------
-constexpr int PA_TRACE_MB = 1024;   // RF_OPT_PAIR_TRACE_MB's default
-__host__ __device__ inline int pa_hp(int H) { return (H + 1) & ~1; }
-__host__ __device__ inline int pa_blocks(int klen) { return (((klen + 1) >> 1) + 15) >> 4; }
-// diagonal pairs per thread of k_pa_gen: 2 NT NPP >= pa_hp(widest band of the tier)
-constexpr int PA_NPP64 = (PS_GEN64_H + 1 + 127) / 128;
-constexpr int PA_NPPW = (DPW_LDS_H + 1 + 2 * DPW_NT - 1) / (2 * DPW_NT);
-
-// ps_step + the cell's move (strict '>' in reference order) into nibble (k >> 1) & 15
-template <int NP, int PAR, int LPT>
-__device__ __forceinline__ void pa_step(const DPTask &T, int q, int k, double (&v1)[NP], double (&v2)[NP],
-                                        const RowRec (&row)[NP], const int (&col)[NP], double &fval, int &fset,
-                                        uint64_t (&w)[NP])
-{
-    const double E1 = PAR == 0 ? dpp_f64<TaskLanes<LPT>::FROM_L1>(v1[NP - 1])
-                               : dpp_f64<TaskLanes<LPT>::FROM_R1>(v1[0]);
-    const bool live = k < T.klen;
-    const int sh = 4 * ((k >> 1) & 15);
-    double nv[NP];
-#pragma unroll
-    for (int r = 0; r < NP; ++r) {
-        const int d = 2 * (q * NP + r) + PAR;
-        const int jj = (k - d) >> 1;
-        const int ii = d + jj - T.c;
-        const bool valid = live && d < T.H && d <= k && jj <= T.m && ii >= 0 && ii <= T.n;
-        const RowRec &R = row[r];
-        const double ms = (R.sb == col[r]) ? R.mt : R.mm;
-        const double x_ins = PAR ? v1[r] : (r > 0 ? v1[r > 0 ? r - 1 : 0] : E1);
-        const double x_del = PAR ? (r < NP - 1 ? v1[r < NP - 1 ? r + 1 : 0] : E1) : v1[r];
-        const double cm = v2[r] + ms, ci = x_ins + R.is, cd = x_del + R.ds;
-        const double best = fmax(fmax(cm, ci), cd);
-        int mv = 0;
-        double b = -RF_INF;
-        if (cm > b) { b = cm; mv = 1; }
-        if (ci > b) { b = ci; mv = 2; }
-        if (cd > b) { mv = 3; }
-        const bool org = ii == 0 && jj == 0;
-        const double v = valid ? (org ? 0.0 : best) : -RF_INF;
-        mv = (valid && !org) ? mv : 0;
-        w[r] |= (uint64_t)mv << sh;
-        const bool fin = valid && ii == T.n && jj == T.m;
-        fval = fin ? v : fval;
-        fset |= fin ? 1 : 0;
-        nv[r] = v;
-    }
-#pragma unroll
-    for (int r = 0; r < NP; ++r) {
-        v2[r] = v1[r];
-        v1[r] = nv[r];
-    }
-}
-
-// ps_lean_step + the move into nibble p (a constant once unrolled) of a
-// 4-period accumulator: two compares and selects on the candidates; a masked
-// diagonal (-Inf) carries 0
-template <int NP, int PAR, int LPT>
-__device__ __forceinline__ void pa_lean_step(double (&v1)[NP], double (&v2)[NP], const RowRec (&row)[NP],
-                                             const int (&col)[NP], const double (&lb)[NP], uint32_t (&w)[NP],
-                                             const int p)
-{
-    const double E1 = PAR == 0 ? dpp_rot_f64<TaskLanes<LPT>::ROT_L1>(v1[NP - 1])
-                               : dpp_rot_f64<TaskLanes<LPT>::ROT_R1>(v1[0]);
-    double nv[NP];
-#pragma unroll
-    for (int r = 0; r < NP; ++r) {
-        const RowRec &R = row[r];
-        const double ms = (R.sb == col[r]) ? R.mt : R.mm;
-        const double x_ins = PAR ? v1[r] : (r > 0 ? v1[r > 0 ? r - 1 : 0] : E1);
-        const double x_del = PAR ? (r < NP - 1 ? v1[r < NP - 1 ? r + 1 : 0] : E1) : v1[r];
-        const double cm = v2[r] + ms, ci = x_ins + R.is, cd = x_del + R.ds;
-        const double t = fmax(cm, ci);
-        nv[r] = fmax(t, cd) + lb[r];
-        int mv = ci > cm ? 2 : 1;
-        mv = cd > t ? 3 : mv;
-        mv = nv[r] == -RF_INF ? 0 : mv;
-        w[r] |= (uint32_t)mv << (4 * p);
-    }
-#pragma unroll
-    for (int r = 0; r < NP; ++r) {
-        v2[r] = v1[r];
-        v1[r] = nv[r];
-    }
-}
-
-template <int NP, int LPT = 16>
-__global__ void __launch_bounds__(64)
-k_pa(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
-     const double *__restrict__ tabs, double *__restrict__ out, const double *__restrict__ lut,
-     uint64_t *__restrict__ trace)
-{
-    static_assert(LPT == 16 || LPT == 64, "k_pa tasks are 16 or 64 lanes");
-    __shared__ EdgeRec s_edge[64 / LPT][PS_B];
-    const int q = threadIdx.x & (LPT - 1);
-    const int t = threadIdx.x / LPT;
-    const int tid = blockIdx.x * (64 / LPT) + t;
-    DPTask T = {};   // a padding task: pad (its trace blocks) = 0, nothing stored
-    if (tid < ntasks)
-        T = tasks[tid];
-    int kmax = T.klen;
-    for (int off = 32; off >= 1; off >>= 1)
-        kmax = max(kmax, __shfl_xor(kmax, off));
-    kmax = __builtin_amdgcn_readfirstlane(kmax);
-    const uint8_t *sbase = bases + T.sb;
-    const uint8_t *tbase = bases + T.tb;
-    const double *tb = tabs + T.tab;
-
-    double v1[NP], v2[NP];
-    RowRec row[NP];
-    int col[NP];
-    uint64_t w[2][NP];   // the open trace words of diagonals 2 (q NP + r) + par
-#pragma unroll
-    for (int r = 0; r < NP; ++r) {
-        v1[r] = -RF_INF;
-        v2[r] = -RF_INF;
-        w[0][r] = w[1][r] = 0;
-        const int pp = q * NP + r;
-        row[r] = load_row(T, false, sbase, tb, pp - T.c, false);   // kappa = 0
-        col[r] = load_col(T, false, tbase, -pp);
-    }
-    const int top = LPT * NP - 1;
-    RowRec nq = load_row(T, false, sbase, tb, top + 1 - T.c, false);   // enters at kappa = 1
-    int cq = load_col(T, false, tbase, 1);                             // enters at kappa = 2
-    double fval = 0.0;
-    int fset = 0;
-    // block b of the task's trace: diagonals 2 (q NP + r), + 1 as one 16-B store
-    uint64_t *trp = trace + T.band;
-    auto flush = [&](int b) {
-#pragma unroll
-        for (int r = 0; r < NP; ++r) {
-            const int d = 2 * (q * NP + r);
-            if (b < T.pad && d < T.P)
-                *(ulonglong2 *)(trp + (size_t)b * T.P + d) = make_ulonglong2(w[0][r], w[1][r]);
-            w[0][r] = w[1][r] = 0;
-        }
-    };
-
-    // lean interior [klo, khi] of the wave's tasks (k_ps), klo at a trace-word boundary
-    int klo = INT_MAX, khi = -1;
-    double lb[2][NP];
-    {
-        int lo = 0, hi = INT_MAX;
-        bool ok = true;
-#pragma unroll
-        for (int par = 0; par < 2; ++par)
-#pragma unroll
-            for (int r = 0; r < NP; ++r) {
-                const int d = 2 * (q * NP + r) + par;
-                const int jlo = max(0, T.c - d), jhi = min(T.m, T.n + T.c - d);
-                const bool a = tid < ntasks && d < T.H && jlo <= jhi;
-                lb[par][r] = a ? 0.0 : -RF_INF;
-                if (a) {
-                    lo = max(lo, d + 2 * jlo);
-                    hi = min(hi, d + 2 * jhi);
-                }
-            }
-        if (tid < ntasks) {
-            lo = max(lo, T.c + 1);
-            hi = min(hi, T.klen - 2);
-            ok = T.c <= T.m;
-        }
-        for (int off = 32; off >= 1; off >>= 1) {
-            lo = max(lo, __shfl_xor(lo, off));
-            hi = min(hi, __shfl_xor(hi, off));
-        }
-        if (__all(ok)) {
-            klo = __builtin_amdgcn_readfirstlane((lo + 2 * PS_B - 1) & ~(2 * PS_B - 1));
-            khi = __builtin_amdgcn_readfirstlane(hi);
-        }
-    }
-    const int nblk = khi >= klo ? (khi - klo + 1) / (2 * PS_B) : 0;
-    int open_blk = -1;   // the trace block the border steps have written into, not flushed yet
-
-    for (int k = 0; k < kmax; k += 2) {
-        if (k == klo && nblk > 0) {
-            // (k - 2) & 31 == 30: the border steps flushed their last block
-            EdgeRec *ein = s_edge[t];
-            const int top_c = LPT * NP - T.c;
-            const bool coded = T.flags & RF_TASK_CODED;
-            const uint64_t *codes = (const uint64_t *)(tb + row_code_off(T.n, T.ncins, T.ncdel));
-            const int ql = min(q, PS_B - 1);
-            auto edge_ks = [&](int kb) {
-                const int ii = max(1, min(top_c + (kb >> 1) + ql, T.n));
-                return ii - 1;
-            };
-            auto code_load = [&](int kb) -> uint64_t { return coded ? codes[edge_ks(kb)] : 0; };
-            auto edge_load = [&](int kb, uint64_t rec) {
-                EdgeRec e;
-                const int ks = edge_ks(kb);
-                if (coded) {
-                    const double *l3 = lut + 4 * (int)(rec & 0xffff);
-                    const dvec2 mt_mm = *(const dvec2 *)l3;
-                    e.mt = mt_mm.x;
-                    e.mm = mt_mm.y;
-                    e.is = l3[2];
-                    e.ds = lut[4 * RF_CODES + (int)((rec >> 32) & 0xffff)];
-                    e.sb = (int)(rec >> 48) & 0xff;
-                } else {
-                    e.sb = sbase[ks];
-                    e.mt = tb[ks];
-                    e.mm = tb[T.n + ks];
-                    e.is = tb[2 * (size_t)T.n + ks];
-                    e.ds = tb[3 * (size_t)T.n + ks + 1];
-                }
-                const int jj = max(1, min((kb >> 1) + ql, T.m));
-                e.col = tbase[jj - 1];
-                e.pad0 = e.pad1 = 0;
-                return e;
-            };
-            {
-                const EdgeRec first = edge_load(k, code_load(k));
-                if (q < PS_B)
-                    ein[q] = first;
-            }
-            EdgeRec pend = edge_load(k + 2 * PS_B, code_load(k + 2 * PS_B));
-            uint64_t pcode = code_load(k + 4 * PS_B);
-            wave_sync();
-            for (int b = 0; b < nblk; ++b) {
-                EdgeRec E = ein[0];
-                // 4 periods unrolled at a time (all 16 at once, the scheduler hoists every
-                // period's row / column moves and match selects and runs out of registers);
-                // their moves gather in 16 bits and join the trace word once
-#pragma unroll 1
-                for (int p4 = 0; p4 < PS_B; p4 += 4) {
-                    uint32_t acc[2][NP];
-#pragma unroll
-                    for (int r = 0; r < NP; ++r)
-                        acc[0][r] = acc[1][r] = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const EdgeRec En = ein[min(p4 + j + 1, PS_B - 1)];   // one period ahead (LDS latency)
-                        {
-                            const int from = __builtin_amdgcn_update_dpp(E.col, col[NP - 1], TaskLanes<LPT>::FROM_L1,
-                                                                         0xF, 0xF, false);
-#pragma unroll
-                            for (int r = NP - 1; r > 0; --r)
-                                col[r] = col[r - 1];
-                            col[0] = from;
-                        }
-                        pa_lean_step<NP, 0, LPT>(v1, v2, row, col, lb[0], acc[0], j);
-                        {
-                            RowRec e;
-                            e.sb = E.sb;
-                            e.mt = E.mt;
-                            e.mm = E.mm;
-                            e.is = E.is;
-                            e.ds = E.ds;
-                            e.ci = e.cd = -RF_INF;
-                            const RowRec up = row_from_above<LPT>(row[0], e, false);
-#pragma unroll
-                            for (int r = 0; r < NP - 1; ++r)
-                                row[r] = row[r + 1];
-                            row[NP - 1] = up;
-                        }
-                        pa_lean_step<NP, 1, LPT>(v1, v2, row, col, lb[1], acc[1], j);
-                        E = En;
-                    }
-#pragma unroll
-                    for (int r = 0; r < NP; ++r) {
-                        w[0][r] |= (uint64_t)acc[0][r] << (4 * p4);
-                        w[1][r] |= (uint64_t)acc[1][r] << (4 * p4);
-                    }
-                }
-                flush(k >> 5);   // the block's 16 periods are one trace word per diagonal
-                wave_sync();
-                if (q < PS_B)
-                    ein[q] = pend;
-                pend = edge_load(k + 4 * PS_B, pcode);
-                pcode = code_load(k + 6 * PS_B);
-                wave_sync();
-                k += 2 * PS_B;
-            }
-            nq = load_row(T, false, sbase, tb, top + k / 2 + 1 - T.c, false);
-            cq = load_col(T, false, tbase, k / 2);
-            if (k >= kmax)
-                break;
-        }
-        if (k > 0) {
-            const int edge = cq;
-            cq = load_col(T, false, tbase, k / 2 + 1);
-            const int from = __builtin_amdgcn_update_dpp(edge, col[NP - 1], TaskLanes<LPT>::FROM_L1, 0xF, 0xF, false);
-#pragma unroll
-            for (int r = NP - 1; r > 0; --r)
-                col[r] = col[r - 1];
-            col[0] = from;
-        }
-        open_blk = k >> 5;
-        pa_step<NP, 0, LPT>(T, q, k, v1, v2, row, col, fval, fset, w[0]);
-        if (k + 1 < kmax) {
-            const RowRec up = row_from_above<LPT>(row[0], nq, false);
-#pragma unroll
-            for (int r = 0; r < NP - 1; ++r)
-                row[r] = row[r + 1];
-            row[NP - 1] = up;
-            nq = load_row(T, false, sbase, tb, top + (k + 2) / 2 + 1 - T.c, false);
-            pa_step<NP, 1, LPT>(T, q, k + 1, v1, v2, row, col, fval, fset, w[1]);
-        }
-        if ((k & 31) == 30) {
-            flush(open_blk);
-            open_blk = -1;
-        }
-    }
-    if (open_blk >= 0)
-        flush(open_blk);
-    if (fset)
-        out[T.out_idx] = fval;
-}
-
-template <int NT, int NPP>
-__global__ void __launch_bounds__(NT)
-k_pa_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
-         const double *__restrict__ tabs, double *__restrict__ out, uint64_t *__restrict__ trace, int ring_ld)
-{
-    extern __shared__ __attribute__((aligned(16))) double ps_ring[];
-    const int q = threadIdx.x;
-    const DPTask T = tasks[blockIdx.x];
-    double *ring = ps_ring;
-    for (int e = q; e < 4 * ring_ld; e += NT)
-        ring[e] = -RF_INF;
-    auto sync = [] {
-        if (NT > 64)
-            lds_barrier();
-        else
-            wave_sync();
-    };
-    sync();
-    const bool skew = T.flags & 2;
-    const bool trim = T.flags & 4;
-    const uint8_t *sbase = bases + T.sb;
-    const uint8_t *tbase = bases + T.tb;
-    const double *tb = tabs + T.tab;
-    const double *t_match = tb;
-    const double *t_mism = tb + T.n;
-    const double *t_ins = tb + 2 * (size_t)T.n;
-    const double *t_del = tb + 3 * (size_t)T.n;
-    const double *t_cins = tb + 4 * (size_t)T.n + 1;
-    const double *t_cdel = t_cins + T.ncins;
-    uint64_t *trp = trace + T.band;
-    bool bad = false;
-    double fval = 0.0;
-    bool fset = false;
-    uint64_t w0[NPP], w1[NPP];   // open trace words of diagonals 2 (q + u NT), + 1
-    const int nu = min(NPP, (T.H + 2 * NT - 1) / (2 * NT));   // diagonal pairs per thread in use (uniform)
-#pragma unroll
-    for (int u = 0; u < NPP; ++u)
-        w0[u] = w1[u] = 0;
-
-    for (int k = 0; k < T.klen; ++k) {
-        const int par = k & 1;
-        const int sh = 4 * ((k >> 1) & 15);
-        double *r0 = ring + (k & 3) * ring_ld + 3;
-        const double *r1 = ring + ((k - 1) & 3) * ring_ld + 3;
-        const double *r2 = ring + ((k - 2) & 3) * ring_ld + 3;
-        const double *r3 = ring + ((k - 3) & 3) * ring_ld + 3;
-#pragma unroll
-        for (int u = 0; u < NPP; ++u) {   // no early exit: unrolled, so w0 / w1 stay in registers
-            const int pp = q + u * NT;
-            const int d = 2 * pp + par;
-            if (u >= nu || d >= T.H || d > k)
-                continue;
-            const int jj = (k - d) >> 1;
-            double v = -RF_INF;
-            int mv = 0;
-            if (jj <= T.m) {
-                const int ii = d + jj - T.c;
-                if (ii >= 0 && ii <= T.n) {
-                    if (ii == 0 && jj == 0) {
-                        v = 0.0;
-                    } else {
                         const int sb = ii >= 1 ? sbase[ii - 1] : 4;
                         const int tbb = jj >= 1 ? tbase[jj - 1] : 4;
                         const int ks = max(ii - 1, 0);
@@ -2073,7 +1764,7 @@ k_pa_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
                             s = r3[d + 3] + t_cdel[ii];
                             if (s > best) { best = s; mv = 5; }
                         }
-                        bad = bad || best == -RF_INF;
+                        bad = bad || best == -RF_INF;   // "new score is invalid"
                         v = best;
                     }
                     if (ii == T.n && jj == T.m) {
@@ -2083,23 +1774,28 @@ k_pa_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
                 }
             }
             r0[d] = v;
-            const uint64_t nib = (uint64_t)mv << sh;
-            w0[u] |= par ? 0 : nib;
-            w1[u] |= par ? nib : 0;
-        }
-        if ((k & 31) == 31 || k == T.klen - 1) {
-            // 16 periods done (or the last): the block's HP words, 16 B per thread and diagonal pair
-            uint64_t *blk = trp + (size_t)(k >> 5) * T.P;
-#pragma unroll
-            for (int u = 0; u < NPP; ++u) {
-                const int d = 2 * (q + u * NT);
-                if (d < T.P)
-                    *(ulonglong2 *)(blk + d) = make_ulonglong2(w0[u], w1[u]);
-                w0[u] = w1[u] = 0;
+            if constexpr (TRACE) {
+                const uint64_t nib = (uint64_t)mv << (4 * ((k >> 1) & 15));
+                w0[u] |= par ? 0 : nib;
+                w1[u] |= par ? nib : 0;
             }
         }
+        if constexpr (TRACE)
+            if ((k & 31) == 31 || k == T.klen - 1) {
+                // 16 periods done (or the last): the block's HP words, 16 B per thread and diagonal pair
+                uint64_t *blk = trace + T.band + (size_t)(k >> 5) * T.P;
+#pragma unroll
+                for (int u = 0; u < NPP; ++u) {
+                    const int d = 2 * (q + u * NT);
+                    if (d < T.P)
+                        *(ulonglong2 *)(blk + d) = make_ulonglong2(w0[u], w1[u]);
+                    w0[u] = w1[u] = 0;
+                }
+            }
         sync();
     }
+    // the pair's flag through the ring (no longer read): NaN for a pair the
+    // reference raises on
     if (q == 0)
         ring[0] = 0.0;
     sync();
@@ -2108,6 +1804,22 @@ k_pa_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
     sync();
     if (fset)
         out[T.out_idx] = ring[0] != 0.0 ? __builtin_nan("") : fval;
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT)
+k_ps_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
+         const double *__restrict__ tabs, double *__restrict__ out, int ring_ld)
+{
+    ps_gen_body<NT, NT == 64 ? PA_NPP64 : PA_NPPW, false>(tasks, bases, tabs, out, nullptr, ring_ld);
+}
+
+template <int NT, int NPP>
+__global__ void __launch_bounds__(NT)
+k_pa_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
+         const double *__restrict__ tabs, double *__restrict__ out, uint64_t *__restrict__ trace, int ring_ld)
+{
+    ps_gen_body<NT, NPP, true>(tasks, bases, tabs, out, trace, ring_ld);
 }
 
 __global__ void __launch_bounds__(64)
@@ -7402,116 +7114,178 @@ int rf_realign_jobs(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32
     return realign_impl(ctx, njobs, slot, seq, tpl, bw, flags, out_score);
 }
 
-// Score-only forward pass of independent pairs (k_ps / k_ps_gen).  Reads the
-// sequence and template arenas only: no slot, no band, no band bookkeeping.
-// Pairs go to the device RF_OPT_PAIR_CHUNK at a time (descriptors in
-// scratch[28], scores in scratch[29]), so device memory does not grow with
-// npairs; within a chunk they are sorted into width classes like rf_realign's
-// tasks, longest first.
-int rf_pair_scores(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
-                   int32_t flags, double *out)
+// ---- rf_pair_scores / rf_pair_align: the checks, the launch plan and the fill launches they share ----
+
+// Argument, flag and per-pair checks.  `fn` names the entry point in the
+// messages; `args_ok` is its own pointer check; `align` is rf_pair_align
+// (its wording, and its timers are the ones reset).
+static int pair_check(rf_ctx *ctx, const std::string &fn, bool align, bool args_ok, int64_t npairs,
+                      const int32_t *seq, const int32_t *tpl, const int32_t *bw, int32_t flags)
 {
-    if (!ctx || npairs < 0 || (npairs > 0 && (!seq || !tpl || !bw || !out)))
-        return fail(ctx, RF_ERR_ARG, "rf_pair_scores: bad arguments");
+    if (!args_ok)
+        return fail(ctx, RF_ERR_ARG, fn + ": bad arguments");
     if (flags & RF_BWD)
-        return fail(ctx, RF_ERR_ARG, "rf_pair_scores: RF_BWD is not supported (forward scores only)");
+        return fail(ctx, RF_ERR_ARG,
+                    fn + ": RF_BWD is not supported (forward " + (align ? "alignments" : "scores") + " only)");
     if (flags & ~(RF_FWD | RF_SKEW | RF_TRIM))
-        return fail(ctx, RF_ERR_ARG, "rf_pair_scores: unknown flags");
+        return fail(ctx, RF_ERR_ARG, fn + ": unknown flags");
     (void)hipSetDevice(ctx->device);
-    ctx->pair_ms = 0;
+    if (align)
+        ctx->pa_fill_ms = ctx->pa_walk_ms = 0;
+    else
+        ctx->pair_ms = 0;
     for (int64_t k = 0; k < npairs; ++k) {
         if (seq[k] < 0 || seq[k] >= (int32_t)ctx->seqs.size() || !ctx->seqs[seq[k]].valid || tpl[k] < 0 ||
             tpl[k] >= (int32_t)ctx->tpls.size() || !ctx->tpls[tpl[k]].valid)
-            return fail(ctx, RF_ERR_ARG, "rf_pair_scores: unknown sequence / template");
+            return fail(ctx, RF_ERR_ARG, fn + ": unknown sequence / template");
         if (bw[k] < 1)
             return fail(ctx, RF_ERR_ARG, "bandwidth must be positive");
         const int64_t H = 2 * (int64_t)bw[k] + std::abs((int64_t)ctx->seqs[seq[k]].n - ctx->tpls[tpl[k]].m) + 1;
         if (H > DPW_LDS_H)
             return fail(ctx, RF_ERR_ARG,
-                        "rf_pair_scores: band of " + std::to_string(H) + " rows is wider than the " +
-                            std::to_string(DPW_LDS_H) + " a score-only pass holds in LDS");
+                        fn + ": band of " + std::to_string(H) + " rows" +
+                            (align ? " (pair " + std::to_string(k) + ")" : std::string()) + " is wider than the " +
+                            std::to_string(DPW_LDS_H) + (align ? " a bandless" : " a score-only") +
+                            " pass holds in LDS");
     }
-    const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
-    const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
+    return 0;
+}
+
+// The DPTask of one pair (no slot, no band); fl: 2 = skew, 4 = trim
+static DPTask pair_task(const SeqObj &S, const TplObj &T, int bw, int fl, int32_t out_idx)
+{
+    DPTask t{};
+    t.sb = S.bases.off;
+    t.tab = S.tabs.off / 8;
+    t.tb = T.bases.off;
+    t.n = S.n;
+    t.m = T.m;
+    t.bw = bw;
+    t.H = band_rows(S.n + 1, T.m + 1, bw);
+    t.c = std::max(T.m - S.n, 0) + bw;
+    t.ncins = S.ncins;
+    t.ncdel = S.ncdel;
+    t.flags = fl | (S.coded ? RF_TASK_CODED : 0);
+    t.out_idx = out_idx;
+    t.klen = t.H + 2 * t.m;
+    return t;
+}
+
+// The tasks of one launch set in their six width classes, like rf_realign's:
+// 0-2: H <= 31, 63, 127 as 16-lane tasks of 1, 2, 4 band-row pairs per lane;
+// 3: H <= PS_FAST_H as 64-lane tasks of 2 (k_dpr's wide class: 8 pairs per
+// lane in 16 lanes leave one wave per SIMD); 4, 5: the general tier in one
+// wave (H <= PS_GEN64_H) or DPW_NT threads.
+struct PairPlan {
+    std::vector<DPTask> cls[6], all;   // all: the classes in order, each longest first
+    size_t at[7];                      // class a is all[at[a] .. at[a + 1])
+    int hmax[2];                       // widest band of classes 4 and 5
+
+    void clear()
+    {
+        for (auto &c : cls)
+            c.clear();
+        hmax[0] = hmax[1] = 0;
+    }
+    void add(const DPTask &t, const SeqObj &S)
+    {
+        // fast tier: k_dpr's lean condition, bands that live in registers
+        const bool lean = S.ncins == 0 && S.ncdel == 0 && S.finite && !(t.flags & (2 | 4));
+        const int a = lean && t.H <= PS_FAST_H ? (t.H <= 31 ? 0 : t.H <= 63 ? 1 : t.H <= 127 ? 2 : 3)
+                                               : (t.H <= PS_GEN64_H ? 4 : 5);
+        cls[a].push_back(t);
+        if (a >= 4)
+            hmax[a - 4] = std::max(hmax[a - 4], t.H);
+    }
+    void finish()
+    {
+        all.clear();
+        for (int a = 0; a < 6; ++a) {
+            std::stable_sort(cls[a].begin(), cls[a].end(),
+                             [](const DPTask &x, const DPTask &y) { return x.klen > y.klen; });
+            at[a] = all.size();
+            all.insert(all.end(), cls[a].begin(), cls[a].end());
+        }
+        at[6] = all.size();
+    }
+};
+
+// The fill launches of a plan whose tasks are in scratch[28]: k_pa* into the
+// trace d_tr, k_ps* without one.
+static int pair_fill(rf_ctx *ctx, const PairPlan &pl, double *d_out, uint64_t *d_tr)
+{
+    const DPTask *d_tasks = (const DPTask *)ctx->scratch[28].p;
     const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
     const double *d_tabs = (const double *)ctx->tab_arena.d;
     const double *d_lut = (const double *)ctx->codes.lut.p;
-    std::vector<DPTask> cf[4], c64, cg, all;
+    using KsFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, const double *);
+    using KaFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, const double *, uint64_t *);
+    const KsFn ks[4] = {k_ps<1>, k_ps<2>, k_ps<4>, k_ps<2, 64>};
+    const KaFn ka[4] = {k_pa<1>, k_pa<2>, k_pa<4>, k_pa<2, 64>};
+    for (int a = 0; a < 4; ++a)
+        if (const int n = (int)pl.cls[a].size()) {
+            const int tpw = a == 3 ? 1 : 4;
+            const dim3 grid((n + tpw - 1) / tpw);
+            if (d_tr)
+                hipLaunchKernelGGL(ka[a], grid, dim3(64), 0, ctx->stream, d_tasks + pl.at[a], n, d_bases, d_tabs,
+                                   d_out, d_lut, d_tr);
+            else
+                hipLaunchKernelGGL(ks[a], grid, dim3(64), 0, ctx->stream, d_tasks + pl.at[a], n, d_bases, d_tabs,
+                                   d_out, d_lut);
+        }
+    for (int g = 0; g < 2; ++g)
+        if (const unsigned n = (unsigned)pl.cls[4 + g].size()) {
+            const int ld = pl.hmax[g] + 6;   // the LDS ring: 4 anti-diagonals of ld doubles
+            const size_t lds = 4 * (size_t)ld * 8;
+            const DPTask *tk = d_tasks + pl.at[4 + g];
+            if (g == 0 && d_tr)
+                hipLaunchKernelGGL((k_pa_gen<64, PA_NPP64>), dim3(n), dim3(64), lds, ctx->stream, tk, d_bases,
+                                   d_tabs, d_out, d_tr, ld);
+            else if (g == 0)
+                hipLaunchKernelGGL(k_ps_gen<64>, dim3(n), dim3(64), lds, ctx->stream, tk, d_bases, d_tabs, d_out, ld);
+            else if (d_tr)
+                hipLaunchKernelGGL((k_pa_gen<DPW_NT, PA_NPPW>), dim3(n), dim3(DPW_NT), lds, ctx->stream, tk,
+                                   d_bases, d_tabs, d_out, d_tr, ld);
+            else
+                hipLaunchKernelGGL(k_ps_gen<DPW_NT>, dim3(n), dim3(DPW_NT), lds, ctx->stream, tk, d_bases, d_tabs,
+                                   d_out, ld);
+        }
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+// Score-only forward pass of independent pairs (k_ps / k_ps_gen).  Reads the
+// sequence and template arenas only: no slot, no band, no band bookkeeping.
+// Pairs go to the device RF_OPT_PAIR_CHUNK at a time (descriptors in
+// scratch[28], scores in scratch[29]), so device memory does not grow with
+// npairs; within a chunk they are sorted into width classes, longest first.
+int rf_pair_scores(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
+                   int32_t flags, double *out)
+{
+    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw && out));
+    if (int e = pair_check(ctx, "rf_pair_scores", false, args_ok, npairs, seq, tpl, bw, flags))
+        return e;
+    const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
+    const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
+    PairPlan pl;
     for (int64_t p0 = 0; p0 < npairs; p0 += chunk) {
         const int64_t cn = std::min(chunk, npairs - p0);
-        for (auto &c : cf)
-            c.clear();
-        c64.clear();
-        cg.clear();
-        int hmax64 = 0, hmaxg = 0;
+        pl.clear();
         for (int64_t k = p0; k < p0 + cn; ++k) {
             const SeqObj &S = ctx->seqs[seq[k]];
-            const TplObj &T = ctx->tpls[tpl[k]];
-            DPTask t{};
-            t.sb = S.bases.off;
-            t.tab = S.tabs.off / 8;
-            t.tb = T.bases.off;
-            t.n = S.n;
-            t.m = T.m;
-            t.bw = bw[k];
-            t.H = band_rows(S.n + 1, T.m + 1, bw[k]);
-            t.c = std::max(T.m - S.n, 0) + bw[k];
-            t.ncins = S.ncins;
-            t.ncdel = S.ncdel;
-            t.flags = fl | (S.coded ? RF_TASK_CODED : 0);
-            t.out_idx = (int32_t)(k - p0);
-            t.klen = t.H + 2 * t.m;
-            // fast tier: k_dpr's lean condition, bands that live in registers
-            const bool lean = S.ncins == 0 && S.ncdel == 0 && S.finite && !fl;
-            if (lean && t.H <= PS_FAST_H)
-                cf[t.H <= 31 ? 0 : t.H <= 63 ? 1 : t.H <= 127 ? 2 : 3].push_back(t);
-            else if (t.H <= PS_GEN64_H) {
-                c64.push_back(t);
-                hmax64 = std::max(hmax64, t.H);
-            } else {
-                cg.push_back(t);
-                hmaxg = std::max(hmaxg, t.H);
-            }
+            pl.add(pair_task(S, ctx->tpls[tpl[k]], bw[k], fl, (int32_t)(k - p0)), S);
         }
-        auto by_len = [](const DPTask &x, const DPTask &y) { return x.klen > y.klen; };
-        all.clear();
-        size_t at[7] = {};
-        {
-            int i = 0;
-            for (std::vector<DPTask> *c : {&cf[0], &cf[1], &cf[2], &cf[3], &c64, &cg}) {
-                std::stable_sort(c->begin(), c->end(), by_len);
-                at[i++] = all.size();
-                all.insert(all.end(), c->begin(), c->end());
-            }
-            at[6] = all.size();
-        }
-        if (int e = upload(ctx, ctx->scratch[28], all))
+        pl.finish();
+        if (int e = upload(ctx, ctx->scratch[28], pl.all))
             return e;
         if (int e = ensure_buf(ctx, ctx->scratch[29], sizeof(double) * (size_t)cn))
             return e;
         if (int e = ensure_hdn(ctx, sizeof(double) * (size_t)cn))
             return e;
-        const DPTask *d_tasks = (const DPTask *)ctx->scratch[28].p;
         double *d_out = (double *)ctx->scratch[29].p;
         HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-        using KFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, const double *);
-        // H <= 31, 63, 127 as 16-lane tasks of 1, 2, 4 band-row pairs per lane, H <= PS_FAST_H as
-        // 64-lane tasks of 2 (k_dpr's wide class: 8 pairs per lane in 16 lanes leave one wave per SIMD)
-        const KFn kf[4] = {k_ps<1>, k_ps<2>, k_ps<4>, k_ps<2, 64>};
-        for (int a = 0; a < 4; ++a)
-            if (const int n = (int)cf[a].size()) {
-                const int tpw = a == 3 ? 1 : 4;
-                hipLaunchKernelGGL(kf[a], dim3((n + tpw - 1) / tpw), dim3(64), 0, ctx->stream, d_tasks + at[a], n,
-                                   d_bases, d_tabs, d_out, d_lut);
-            }
-        if (!c64.empty())
-            hipLaunchKernelGGL(k_ps_gen<64>, dim3((unsigned)c64.size()), dim3(64), 4 * (size_t)(hmax64 + 6) * 8,
-                               ctx->stream, d_tasks + at[4], d_bases, d_tabs, d_out, hmax64 + 6);
-        if (!cg.empty())
-            hipLaunchKernelGGL(k_ps_gen<DPW_NT>, dim3((unsigned)cg.size()), dim3(DPW_NT),
-                               4 * (size_t)(hmaxg + 6) * 8, ctx->stream, d_tasks + at[5], d_bases, d_tabs, d_out,
-                               hmaxg + 6);
-        HIPCHK(ctx, hipGetLastError());
+        if (int e = pair_fill(ctx, pl, d_out, nullptr))
+            return e;
         HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync((char *)ctx->hdn + HDN_RES, d_out, sizeof(double) * (size_t)cn,
                                    hipMemcpyDeviceToHost, ctx->stream));
@@ -7542,40 +7316,21 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
                   int32_t flags, double *out_score, int8_t *moves, const int64_t *moves_off, int32_t *nmoves,
                   int32_t *nerrors)
 {
-    if (!ctx || npairs < 0 || (npairs > 0 && (!seq || !tpl || !bw)) || (!moves != !moves_off))
-        return fail(ctx, RF_ERR_ARG, "rf_pair_align: bad arguments");
-    if (flags & RF_BWD)
-        return fail(ctx, RF_ERR_ARG, "rf_pair_align: RF_BWD is not supported (forward alignments only)");
-    if (flags & ~(RF_FWD | RF_SKEW | RF_TRIM))
-        return fail(ctx, RF_ERR_ARG, "rf_pair_align: unknown flags");
-    (void)hipSetDevice(ctx->device);
-    ctx->pa_fill_ms = ctx->pa_walk_ms = 0;
-    for (int64_t k = 0; k < npairs; ++k) {
-        if (seq[k] < 0 || seq[k] >= (int32_t)ctx->seqs.size() || !ctx->seqs[seq[k]].valid || tpl[k] < 0 ||
-            tpl[k] >= (int32_t)ctx->tpls.size() || !ctx->tpls[tpl[k]].valid)
-            return fail(ctx, RF_ERR_ARG, "rf_pair_align: unknown sequence / template");
-        if (bw[k] < 1)
-            return fail(ctx, RF_ERR_ARG, "bandwidth must be positive");
-        const int64_t H = 2 * (int64_t)bw[k] + std::abs((int64_t)ctx->seqs[seq[k]].n - ctx->tpls[tpl[k]].m) + 1;
-        if (H > DPW_LDS_H)
-            return fail(ctx, RF_ERR_ARG,
-                        "rf_pair_align: band of " + std::to_string(H) + " rows (pair " + std::to_string(k) +
-                            ") is wider than the " + std::to_string(DPW_LDS_H) + " a bandless pass holds in LDS");
-    }
+    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && (!moves == !moves_off);
+    if (int e = pair_check(ctx, "rf_pair_align", true, args_ok, npairs, seq, tpl, bw, flags))
+        return e;
     const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
     const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
     const int64_t budget = (int64_t)std::max(ctx->opt.pair_trace_mb, 1) << 20;   // bytes of trace per set
     const bool walk = moves || nmoves || nerrors;
     const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
-    const double *d_tabs = (const double *)ctx->tab_arena.d;
-    const double *d_lut = (const double *)ctx->codes.lut.p;
     auto trace_words = [&](int64_t k) {
         const SeqObj &S = ctx->seqs[seq[k]];
         const TplObj &T = ctx->tpls[tpl[k]];
         const int H = band_rows(S.n + 1, T.m + 1, bw[k]);
         return (int64_t)pa_blocks(H + 2 * T.m) * pa_hp(H);
     };
-    std::vector<DPTask> cf[4], c64, cg, all;
+    PairPlan pl;
     std::vector<int64_t> mvoff;
     for (int64_t p0 = 0; p0 < npairs;) {
         // the set [p0, p0 + cn): at least one pair, then while both bounds hold
@@ -7587,65 +7342,27 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
             words += w;
             ++cn;
         }
-        for (auto &c : cf)
-            c.clear();
-        c64.clear();
-        cg.clear();
+        pl.clear();
         mvoff.assign((size_t)cn, 0);
-        int hmax64 = 0, hmaxg = 0;
         int64_t tr_at = 0, mv_total = 0;
         for (int64_t k = p0; k < p0 + cn; ++k) {
             const SeqObj &S = ctx->seqs[seq[k]];
             const TplObj &T = ctx->tpls[tpl[k]];
-            DPTask t{};
-            t.sb = S.bases.off;
-            t.tab = S.tabs.off / 8;
-            t.tb = T.bases.off;
-            t.n = S.n;
-            t.m = T.m;
-            t.bw = bw[k];
-            t.H = band_rows(S.n + 1, T.m + 1, bw[k]);
-            t.c = std::max(T.m - S.n, 0) + bw[k];
-            t.ncins = S.ncins;
-            t.ncdel = S.ncdel;
-            t.flags = fl | (S.coded ? RF_TASK_CODED : 0);
-            t.out_idx = (int32_t)(k - p0);
-            t.klen = t.H + 2 * t.m;
+            DPTask t = pair_task(S, T, bw[k], fl, (int32_t)(k - p0));
             t.band = tr_at;               // the pair's trace: 64-bit words from scratch[30]
             t.P = pa_hp(t.H);             // words per 16-period block
             t.pad = pa_blocks(t.klen);    // blocks
             tr_at += (int64_t)t.pad * t.P;
             mvoff[(size_t)(k - p0)] = mv_total;
             mv_total += S.n + T.m;
-            // rf_pair_scores' routing
-            const bool lean = S.ncins == 0 && S.ncdel == 0 && S.finite && !fl;
-            if (lean && t.H <= PS_FAST_H)
-                cf[t.H <= 31 ? 0 : t.H <= 63 ? 1 : t.H <= 127 ? 2 : 3].push_back(t);
-            else if (t.H <= PS_GEN64_H) {
-                c64.push_back(t);
-                hmax64 = std::max(hmax64, t.H);
-            } else {
-                cg.push_back(t);
-                hmaxg = std::max(hmaxg, t.H);
-            }
+            pl.add(t, S);
         }
-        auto by_len = [](const DPTask &x, const DPTask &y) { return x.klen > y.klen; };
-        all.clear();
-        size_t at[7] = {};
-        {
-            int i = 0;
-            for (std::vector<DPTask> *c : {&cf[0], &cf[1], &cf[2], &cf[3], &c64, &cg}) {
-                std::stable_sort(c->begin(), c->end(), by_len);
-                at[i++] = all.size();
-                all.insert(all.end(), c->begin(), c->end());
-            }
-            at[6] = all.size();
-        }
+        pl.finish();
         const bool want_mv = moves != nullptr;
         // downloads: scores, then nmoves and nerrors, then the moves
         const size_t cb = sizeof(double) * (size_t)cn, nbytes = sizeof(int32_t) * 2 * (size_t)cn;
         const size_t mv_at = (cb + nbytes + 15) & ~(size_t)15;
-        if (int e = upload(ctx, ctx->scratch[28], all))
+        if (int e = upload(ctx, ctx->scratch[28], pl.all))
             return e;
         if (int e = ensure_buf(ctx, ctx->scratch[29], cb))
             return e;
@@ -7668,24 +7385,8 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
         uint64_t *d_tr = (uint64_t *)ctx->scratch[30].p;
         int32_t *d_cnt = (int32_t *)ctx->scratch[33].p;
         HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-        using KFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, const double *,
-                             uint64_t *);
-        const KFn kf[4] = {k_pa<1>, k_pa<2>, k_pa<4>, k_pa<2, 64>};
-        for (int a = 0; a < 4; ++a)
-            if (const int n = (int)cf[a].size()) {
-                const int tpw = a == 3 ? 1 : 4;
-                hipLaunchKernelGGL(kf[a], dim3((n + tpw - 1) / tpw), dim3(64), 0, ctx->stream, d_tasks + at[a], n,
-                                   d_bases, d_tabs, d_out, d_lut, d_tr);
-            }
-        if (!c64.empty())
-            hipLaunchKernelGGL((k_pa_gen<64, PA_NPP64>), dim3((unsigned)c64.size()), dim3(64),
-                               4 * (size_t)(hmax64 + 6) * 8, ctx->stream, d_tasks + at[4], d_bases, d_tabs, d_out,
-                               d_tr, hmax64 + 6);
-        if (!cg.empty())
-            hipLaunchKernelGGL((k_pa_gen<DPW_NT, PA_NPPW>), dim3((unsigned)cg.size()), dim3(DPW_NT),
-                               4 * (size_t)(hmaxg + 6) * 8, ctx->stream, d_tasks + at[5], d_bases, d_tabs, d_out,
-                               d_tr, hmaxg + 6);
-        HIPCHK(ctx, hipGetLastError());
+        if (int e = pair_fill(ctx, pl, d_out, d_tr))
+            return e;
         HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
         if (walk) {
             hipLaunchKernelGGL(k_pa_walk, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, ctx->stream, d_tasks,

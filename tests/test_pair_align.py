@@ -91,6 +91,40 @@ def test_width_ladder(engine):
     check(got, [oracle_align(t, s) for t, s in zip(tpls, seqs)], what)
 
 
+def test_scores_and_align_share_the_fill(engine):
+    """pair_scores and pair_align run one recurrence in every class: n == m
+    pairs on each side of every fast-tier threshold (H = 2 bw + 1 = 31 / 33,
+    63 / 65, 127 / 129, 255 / 257; the last takes the general tier), reads a
+    few edits from templates of 3 H bases (two or more lean-interior blocks),
+    and one read with codon tables (general tier).  One call each: the score
+    bits are equal, and moves, scores and error counts are the oracle's."""
+    rng = np.random.default_rng(2210)
+    seqs, tpls, bws, what = [], [], [], []
+
+    def add(m, bw, scores):
+        t = random_seq(m, rng)
+        s = t.copy()
+        for i in rng.integers(0, m, 3):   # substitutions, then one deletion and one insertion: n == m
+            s[i] = (s[i] + rng.integers(1, 4)) % 4
+        s = np.delete(s, rng.integers(0, m))
+        s = np.insert(s, rng.integers(0, m), rng.integers(0, 4)).astype(np.uint8)
+        seqs.append(RifrafSequence(s, np.log10(rng.uniform(0.01, 0.3, m)), bw, scores))
+        tpls.append(t)
+        bws.append(bw)
+        what.append((m, bw, scores is REF_SCORES))
+
+    for bw in (15, 16, 31, 32, 63, 64, 127, 128):
+        add(3 * (2 * bw + 1), bw, SEQ_SCORES)
+    add(99, 16, REF_SCORES)
+    engine.set_sequences(0, seqs)
+    engine.set_templates(0, tpls)
+    ids = np.arange(len(seqs))
+    scores = engine.pair_scores(ids, ids, bws)
+    got = engine.pair_align(ids, ids, bws)
+    assert np.array_equal(np.asarray(scores).view(np.int64), np.asarray(got[0]).view(np.int64)), (scores, got[0])
+    check(got, [oracle_align(t, s, bw) for t, s, bw in zip(tpls, seqs, bws)], what)
+
+
 # ---------------------------------------------------------------------
 # 3. trace-word edges
 # ---------------------------------------------------------------------
