@@ -16,6 +16,8 @@
  *   rf_pair_align     <- backtrace(forward_moves(...)[2]) + count_errors over
  *                        many pairs (align_moves, align, edit_distance,
  *                        correct_shifts)  src/align.jl:114-153,229-260
+ *   rf_pair_align_smart <- smart_forward_moves! (band doubling) over many
+ *                        pairs  src/model.jl:643-672
  *   rf_backtrace      <- backtrace + count_errors   src/align.jl:229-245
  *   rf_alignment_proposals <- alignment_proposals / moves_to_proposals
  *                        src/model.jl:458-497
@@ -151,6 +153,16 @@ const char *rf_last_error(const rf_ctx *ctx);
 #define RF_OPT_PAIR_TRACE_MB 33 /* rf_pair_align: device bytes of move trace per
                                    launch set, MB (default 1024); a set also holds
                                    at most RF_OPT_PAIR_CHUNK pairs                */
+#define RF_OPT_PAIR_WALK   34   /* the walk of rf_pair_align and of every round of
+                                   rf_pair_align_smart (model.jl:643-672 walks the
+                                   pending pairs once per round): 1: one lane per
+                                   pair (k_pa_walk); 2: one wave per pair over a
+                                   64-diagonal window of trace words held in the
+                                   lanes (k_pa_walk_w); 0 (default): per launch
+                                   set, the wave walk where the mean n + m of its
+                                   pairs is at least 512, as measured for 16 to
+                                   62,500 pairs.  Same moves and
+                                   counts under every value                      */
 /* Keys 3, 5-8, 14 and 20 selected scorer variants measured slower and removed
    in round 3 (k_score_lean, the 128-lane k_score_ws, k_score_seg /
    k_score_segc, 16-diagonal k_score_segl, the unspecialised k_score_w2);
@@ -296,6 +308,37 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
 /* Kernel time of the last rf_pair_align call (all its sets), milliseconds:
  * the fills and the walks.  Either pointer may be NULL. */
 int rf_last_pair_align_ms(const rf_ctx *ctx, double *fill_ms, double *walk_ms);
+
+/* rf_pair_align with the band doubling of smart_forward_moves!
+ * (model.jl:643-672), pair by pair: bw[k] is the starting bandwidth,
+ * fixed[k] != 0 the sequence's bandwidth_fixed (fixed may be NULL: none),
+ * threshold[k] the caller's cquantile(Poisson(est_n_errors), pvalue) as in
+ * rf_rifraf_batch, and
+ *   max_bw = fixed ? bw : min(bw << max_doublings, m, n)
+ * with max_doublings in 0..5 (the reference's 2^5 is 5).  A round fills the
+ * pair at its current bandwidth and stops if it is fixed or bw >= max_bw;
+ * otherwise old = n_err, n_err = count_errors (both start at INT_MAX), and if
+ * n_err > threshold && n_err < old the pair goes into another round at
+ * bw = min(2 bw, max_bw).  A round submits only the pairs still pending.
+ * out_score, moves, nmoves and nerrors are those of the pair's last fill
+ * (nerrors is count_errors of the final moves, also when the loop stopped at
+ * max_bw), out_bw[k] the final bandwidth and out_rounds[k] the number of
+ * fills.  Any output pointer may be NULL; moves and moves_off are NULL
+ * together.  A pair whose fill is invalid in some round stops there with
+ * score NaN, nmoves = nerrors = -1 and out_bw the bandwidth that raised; the
+ * call still returns 0.  Checked before anything runs, each RF_ERR_ARG with a
+ * message naming the first such pair: rf_pair_align's checks, threshold
+ * non-NULL, max_doublings in 0..5, and the band at max_bw within the 5,114
+ * rows (2 max_bw + |n - m| + 1).  Like rf_pair_align the call touches no
+ * slot, no band and not the band arena, and its device memory is bounded by
+ * RF_OPT_PAIR_CHUNK / RF_OPT_PAIR_TRACE_MB, not by npairs or the number of
+ * rounds.  max_doublings = 0 is rf_pair_align at bw, bit for bit.
+ * rf_last_pair_align_ms then sums the fills and walks of all rounds. */
+int rf_pair_align_smart(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl,
+                        const int32_t *bw, const double *threshold, const uint8_t *fixed,
+                        int32_t max_doublings, int32_t flags, double *out_score, int8_t *moves,
+                        const int64_t *moves_off, int32_t *nmoves, int32_t *nerrors,
+                        int32_t *out_bw, int32_t *out_rounds);
 
 /* Backtrace of the A band of each slot (align.jl:229-238), moves in
  * alignment order written at moves[moves_off[k] ...] (capacity n+m each);

@@ -14,7 +14,7 @@
 //               (rf_pair_scores): A[end,end] without a band; register tier
 //               (k_dpr's systolic step, no stores) and LDS-ring tier (k_dp's)
 //               src/align.jl:155-179
-//   k_pa / k_pa_gen / k_pa_walk  alignments of independent pairs
+//   k_pa / k_pa_gen / k_pa_walk / k_pa_walk_w  alignments of independent pairs
 //               (rf_pair_align): k_ps / k_ps_gen writing a 4-bit move per
 //               cell, and a walk over the moves  src/align.jl:114-153,229-245
 //   k_score_ws / k_score_segl / k_score
@@ -46,6 +46,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -1871,6 +1872,111 @@ k_pa_walk(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restric
     ok = ok && ii == 0 && jj == 0;
     nmoves[T.out_idx] = ok ? cnt : -1;
     nerr[T.out_idx] = ok ? errs : -1;
+}
+
+// k_pa_walk with one wave per pair (RF_OPT_PAIR_WALK), for launches of few
+// long walks: same inputs, trace format, outputs and termination rules.  The
+// walk state (ii, jj, counts) is wave-uniform.  The lanes hold a window of the
+// trace: the words of up to 64 diagonals d0 .. d0 + 63 of the current
+// 16-period block (one coalesced load, masked at HP: only words the fill
+// wrote) and the same diagonals of the block before it, which is loaded while
+// the current one is walked and moves up when the walk crosses the block
+// edge inside the window.  A step takes the current diagonal's word from its
+// lane (readlane).  A run of matches stays on one diagonal and inside one
+// word: its length comes from the word's nibbles with one count of leading
+// zeros, the run is one step, and its lanes store the move bytes and load
+// the two bases each; the comparison is taken one run later, per lane, so no
+// step waits for those loads, and the lanes' mismatch counts are summed once
+// after the walk.  Every other move is one uniform step.  Each iteration
+// takes at least one move, so n + m iterations bound the loop as they bound
+// k_pa_walk's.
+constexpr int PAW_NW = 4;   // waves (pairs) per workgroup
+__global__ void __launch_bounds__(64 * PAW_NW)
+k_pa_walk_w(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+            const double *__restrict__ scores, const uint64_t *__restrict__ trace, int8_t *__restrict__ moves,
+            const int64_t *__restrict__ moves_off, int32_t *__restrict__ nmoves, int32_t *__restrict__ nerr)
+{
+    const int lane = threadIdx.x & 63;
+    const int t = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * PAW_NW + (threadIdx.x >> 6)));
+    if (t >= ntasks)
+        return;
+    const DPTask &T = tasks[t];
+    const int n = T.n, m = T.m, H = T.H, HP = T.P, c = T.c, nb = T.pad, oi = T.out_idx;
+    const uint8_t *s = bases + T.sb;
+    const uint8_t *tt = bases + T.tb;
+    const uint64_t *tr = trace + T.band;
+    int8_t *o = moves ? moves + moves_off[oi] : nullptr;
+    int ii = n, jj = m, cnt = 0, errs = 0;
+    bool ok = !(scores[oi] != scores[oi]);   // NaN: the reference raised, no walk
+    int wb = -2, d0 = 0;            // the window: block wb (and wb - 1), diagonals d0 + lane
+    uint64_t wcur = 0, wprev = 0;
+    int ps = 0, pt = 0, lerr = 0;   // this lane's bases of the last run, its mismatches so far
+    for (int it = 0; ok && it < n + m && (ii > 0 || jj > 0); ++it) {
+        const int d = ii - jj + c, kap = ii + jj + c;
+        const int p = kap >> 1, b = p >> 4;
+        if ((unsigned)d >= (unsigned)H || b >= nb) {
+            ok = false;
+            break;
+        }
+        if (b != wb || (unsigned)(d - d0) >= 64u) {
+            const bool up = b == wb - 1 && (unsigned)(d - d0) < 64u;
+            if (!up)
+                d0 = max(d - 32, 0);
+            const bool in = d0 + lane < HP;
+            wcur = up ? wprev : (in ? tr[(size_t)b * HP + d0 + lane] : 0);
+            wprev = (b > 0 && in) ? tr[(size_t)(b - 1) * HP + d0 + lane] : 0;
+            wb = b;
+        }
+        const int sl = __builtin_amdgcn_readfirstlane(d - d0);
+        const uint32_t wlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)wcur, sl);
+        const uint32_t whi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(wcur >> 32), sl);
+        const uint64_t word = ((uint64_t)whi << 32) | wlo;
+        const int q = p & 15;
+        const int mv = (int)(word >> (4 * q)) & 15;
+        if (mv == 1) {
+            // nibbles q, q - 1, ... that are 1: the shifted-in low nibbles are 0 and end the run at nibble 0
+            const uint64_t y = (word << (4 * (15 - q))) ^ 0x1111111111111111ull;
+            const int run = y ? __builtin_clzll(y) >> 2 : 16;
+            const int r = min(run, min(ii, jj));
+            if (r == 0) {   // a match that would leave the matrix
+                ok = false;
+                break;
+            }
+            lerr += ps != pt ? 1 : 0;
+            ps = pt = 0;
+            if (lane < r) {
+                ps = s[ii - 1 - lane];
+                pt = tt[jj - 1 - lane];
+                if (o)
+                    o[n + m - 1 - cnt - lane] = 1;
+            }
+            cnt += r;
+            ii -= r;
+            jj -= r;
+        } else {
+            const int di = mv == 2 ? 1 : (mv == 4 ? 3 : 0);
+            const int dj = mv == 3 ? 1 : (mv == 5 ? 3 : 0);
+            if (mv < 2 || mv > 5 || ii < di || jj < dj) {
+                ok = false;
+                break;
+            }
+            errs += mv >= 4 ? 3 : 1;
+            if (o && lane == 0)
+                o[n + m - 1 - cnt] = (int8_t)mv;
+            ++cnt;
+            ii -= di;
+            jj -= dj;
+        }
+    }
+    lerr += ps != pt ? 1 : 0;
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1)
+        lerr += __shfl_xor(lerr, w, 64);
+    ok = ok && ii == 0 && jj == 0;
+    if (lane == 0) {
+        nmoves[oi] = ok ? cnt : -1;
+        nerr[oi] = ok ? errs + lerr : -1;
+    }
 }
 
 // ---------------------------------------------------------------------
@@ -5260,6 +5366,7 @@ struct Opts {
                             // one k_dpx launch (latency mode: the launch cannot fill the GPU)
     int pair_chunk = PS_CHUNK;   // RF_OPT_PAIR_CHUNK: pairs per launch set of rf_pair_scores / rf_pair_align
     int pair_trace_mb = PA_TRACE_MB;   // RF_OPT_PAIR_TRACE_MB: MB of move trace per launch set of rf_pair_align
+    int pair_walk = 0;                 // RF_OPT_PAIR_WALK: 0 auto, 1 k_pa_walk (lane per pair), 2 k_pa_walk_w (wave per pair)
 };
 
 }  // namespace
@@ -5720,6 +5827,7 @@ void load_env_opts(Opts &o)
     o.dp_mc = env_int("RIFRAF_DP_MC", o.dp_mc);
     o.bt_nw = env_int("RIFRAF_BT_NW", o.bt_nw);
     o.pair_trace_mb = env_int("RIFRAF_PAIR_TRACE_MB", o.pair_trace_mb);
+    o.pair_walk = env_int("RIFRAF_PAIR_WALK", o.pair_walk);
 }
 
 ScorePick pick_scorer(const Opts &o, const std::vector<ScoreRead> &reads, bool all_finite)
@@ -5941,6 +6049,7 @@ static int *opt_slot(rf_ctx *ctx, int32_t key)
     case RF_OPT_BT_NW: return &o.bt_nw;
     case RF_OPT_PAIR_CHUNK: return &o.pair_chunk;
     case RF_OPT_PAIR_TRACE_MB: return &o.pair_trace_mb;
+    case RF_OPT_PAIR_WALK: return &o.pair_walk;
     default: return nullptr;
     }
 }
@@ -7306,24 +7415,40 @@ int rf_last_pair_ms(const rf_ctx *ctx, double *ms)
     return 0;
 }
 
-// Alignments of independent pairs from a 4-bit move trace (k_pa / k_pa_gen,
-// then k_pa_walk).  Like rf_pair_scores it reads the sequence and template
-// arenas only.  Pairs go out in launch sets of at most RF_OPT_PAIR_CHUNK
-// pairs and RF_OPT_PAIR_TRACE_MB of trace (a pair above the budget alone), so
-// the trace (scratch[30]), the moves (31), their offsets (32) and the counts
-// (33) of one set are all the device memory the call needs.
-int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
-                  int32_t flags, double *out_score, int8_t *moves, const int64_t *moves_off, int32_t *nmoves,
-                  int32_t *nerrors)
+// Which walk a launch set takes: RF_OPT_PAIR_WALK, or with 0 (auto) the rule
+// measured by scripts/pair_align_timing.py --walk-ab (DESIGN.md §4,
+// profiles/pair_align_smart_timing.json): the wave walk from a mean n + m of
+// PAW_MIN_NM.  62,500 pairs at bw 9: n + m = 60, 120, 301 -> the lane walk is
+// faster (wave / lane time 1.80, 1.50, 1.14); 802, 3,006 -> the wave walk
+// (0.86, 0.57).  At n + m = 20,037 the wave walk took 0.10-0.14 of the lane
+// walk's time for 16, 128, 1,024 and 4,096 pairs alike, so the number of
+// pairs does not enter the rule.
+constexpr int PAW_MIN_NM = 512;
+static bool pair_walk_wave(const rf_ctx *ctx, int64_t cn, int64_t mv_total)
 {
-    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && (!moves == !moves_off);
-    if (int e = pair_check(ctx, "rf_pair_align", true, args_ok, npairs, seq, tpl, bw, flags))
-        return e;
-    const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
+    if (ctx->opt.pair_walk != 0)
+        return ctx->opt.pair_walk == 2;
+    return mv_total >= (int64_t)PAW_MIN_NM * cn;
+}
+
+// The body of rf_pair_align and of one round of rf_pair_align_smart: the
+// pairs idx[0 .. nidx) (idx NULL: 0 .. nidx - 1) at the bandwidths bw[k], in
+// launch sets of at most RF_OPT_PAIR_CHUNK pairs and RF_OPT_PAIR_TRACE_MB of
+// trace (a pair above the budget alone), so the trace (scratch[30]), the
+// moves (31), their offsets (32) and the counts (33) of one set are all the
+// device memory a call needs.  seq, tpl, bw and every output are indexed by
+// the pair's own k.  `walk`: run the walk (counts, and moves with `moves`).
+// `ended` (may be empty) sees a pair's score and counts and says whether its
+// moves go to the caller; without it every pair's do.
+static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const int32_t *seq, const int32_t *tpl,
+                          const int32_t *bw, int fl, bool walk, double *out_score, int8_t *moves,
+                          const int64_t *moves_off, int32_t *nmoves, int32_t *nerrors,
+                          const std::function<bool(int64_t, double, int32_t, int32_t)> &ended)
+{
     const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
     const int64_t budget = (int64_t)std::max(ctx->opt.pair_trace_mb, 1) << 20;   // bytes of trace per set
-    const bool walk = moves || nmoves || nerrors;
     const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
+    auto at = [&](int64_t i) { return idx ? idx[i] : i; };
     auto trace_words = [&](int64_t k) {
         const SeqObj &S = ctx->seqs[seq[k]];
         const TplObj &T = ctx->tpls[tpl[k]];
@@ -7332,11 +7457,11 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
     };
     PairPlan pl;
     std::vector<int64_t> mvoff;
-    for (int64_t p0 = 0; p0 < npairs;) {
+    for (int64_t p0 = 0; p0 < nidx;) {
         // the set [p0, p0 + cn): at least one pair, then while both bounds hold
         int64_t cn = 0, words = 0;
-        while (p0 + cn < npairs && cn < chunk) {
-            const int64_t w = trace_words(p0 + cn);
+        while (p0 + cn < nidx && cn < chunk) {
+            const int64_t w = trace_words(at(p0 + cn));
             if (cn > 0 && (words + w) * 8 > budget)
                 break;
             words += w;
@@ -7345,15 +7470,16 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
         pl.clear();
         mvoff.assign((size_t)cn, 0);
         int64_t tr_at = 0, mv_total = 0;
-        for (int64_t k = p0; k < p0 + cn; ++k) {
+        for (int64_t i = p0; i < p0 + cn; ++i) {
+            const int64_t k = at(i);
             const SeqObj &S = ctx->seqs[seq[k]];
             const TplObj &T = ctx->tpls[tpl[k]];
-            DPTask t = pair_task(S, T, bw[k], fl, (int32_t)(k - p0));
+            DPTask t = pair_task(S, T, bw[k], fl, (int32_t)(i - p0));
             t.band = tr_at;               // the pair's trace: 64-bit words from scratch[30]
             t.P = pa_hp(t.H);             // words per 16-period block
             t.pad = pa_blocks(t.klen);    // blocks
             tr_at += (int64_t)t.pad * t.P;
-            mvoff[(size_t)(k - p0)] = mv_total;
+            mvoff[(size_t)(i - p0)] = mv_total;
             mv_total += S.n + T.m;
             pl.add(t, S);
         }
@@ -7389,10 +7515,16 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
             return e;
         HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
         if (walk) {
-            hipLaunchKernelGGL(k_pa_walk, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, ctx->stream, d_tasks,
-                               (int)cn, d_bases, (const double *)d_out, (const uint64_t *)d_tr,
-                               want_mv ? (int8_t *)ctx->scratch[31].p : nullptr,
-                               (const int64_t *)ctx->scratch[32].p, d_cnt, d_cnt + cn);
+            if (pair_walk_wave(ctx, cn, mv_total))
+                hipLaunchKernelGGL(k_pa_walk_w, dim3((unsigned)((cn + PAW_NW - 1) / PAW_NW)), dim3(64 * PAW_NW), 0,
+                                   ctx->stream, d_tasks, (int)cn, d_bases, (const double *)d_out,
+                                   (const uint64_t *)d_tr, want_mv ? (int8_t *)ctx->scratch[31].p : nullptr,
+                                   (const int64_t *)ctx->scratch[32].p, d_cnt, d_cnt + cn);
+            else
+                hipLaunchKernelGGL(k_pa_walk, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, ctx->stream, d_tasks,
+                                   (int)cn, d_bases, (const double *)d_out, (const uint64_t *)d_tr,
+                                   want_mv ? (int8_t *)ctx->scratch[31].p : nullptr,
+                                   (const int64_t *)ctx->scratch[32].p, d_cnt, d_cnt + cn);
             HIPCHK(ctx, hipGetLastError());
         }
         HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
@@ -7400,21 +7532,27 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
         HIPCHK(ctx, hipMemcpyAsync(h, d_out, cb, hipMemcpyDeviceToHost, ctx->stream));
         if (walk)
             HIPCHK(ctx, hipMemcpyAsync(h + cb, d_cnt, nbytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (want_mv && mv_total > 0)
+        if (walk && want_mv && mv_total > 0)
             HIPCHK(ctx, hipMemcpyAsync(h + mv_at, ctx->scratch[31].p, (size_t)mv_total, hipMemcpyDeviceToHost,
                                        ctx->stream));
         HIPCHK(ctx, stream_wait(ctx));
-        if (out_score)
-            std::memcpy(out_score + p0, h, cb);
+        const double *sc = (const double *)h;
         const int32_t *cnt = (const int32_t *)(h + cb);
-        for (int64_t k = 0; k < cn && walk; ++k) {
+        for (int64_t i = 0; i < cn; ++i) {
+            const int64_t k = at(p0 + i);
+            if (out_score)
+                out_score[k] = sc[i];
+            if (!walk)
+                continue;
             if (nmoves)
-                nmoves[p0 + k] = cnt[k];
+                nmoves[k] = cnt[i];
             if (nerrors)
-                nerrors[p0 + k] = cnt[cn + k];
-            if (want_mv && cnt[k] > 0) {   // the walk leaves the moves at the end of the pair's n + m slot
-                const int64_t len = (k + 1 < cn ? mvoff[(size_t)k + 1] : mv_total) - mvoff[(size_t)k];
-                std::memcpy(moves + moves_off[p0 + k], h + mv_at + mvoff[(size_t)k] + len - cnt[k], (size_t)cnt[k]);
+                nerrors[k] = cnt[cn + i];
+            if (ended && !ended(k, sc[i], cnt[i], cnt[cn + i]))
+                continue;
+            if (want_mv && cnt[i] > 0) {   // the walk leaves the moves at the end of the pair's n + m slot
+                const int64_t len = (i + 1 < cn ? mvoff[(size_t)i + 1] : mv_total) - mvoff[(size_t)i];
+                std::memcpy(moves + moves_off[k], h + mv_at + mvoff[(size_t)i] + len - cnt[i], (size_t)cnt[i]);
             }
         }
         float ms = 0;
@@ -7424,6 +7562,107 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
         ctx->pa_walk_ms += ms;
         p0 += cn;
     }
+    return 0;
+}
+
+// Alignments of independent pairs from a 4-bit move trace (k_pa / k_pa_gen,
+// then k_pa_walk or k_pa_walk_w).  Like rf_pair_scores it reads the sequence
+// and template arenas only.
+int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
+                  int32_t flags, double *out_score, int8_t *moves, const int64_t *moves_off, int32_t *nmoves,
+                  int32_t *nerrors)
+{
+    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && (!moves == !moves_off);
+    if (int e = pair_check(ctx, "rf_pair_align", true, args_ok, npairs, seq, tpl, bw, flags))
+        return e;
+    const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
+    return pair_align_run(ctx, npairs, nullptr, seq, tpl, bw, fl, moves || nmoves || nerrors, out_score, moves,
+                          moves_off, nmoves, nerrors, nullptr);
+}
+
+// smart_forward_moves! (model.jl:643-672) of independent pairs: rounds of
+// pair_align_run over the pairs still pending, each at its current bandwidth;
+// the loop's decisions are taken here from the downloaded counts.
+int rf_pair_align_smart(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
+                        const double *threshold, const uint8_t *fixed, int32_t max_doublings, int32_t flags,
+                        double *out_score, int8_t *moves, const int64_t *moves_off, int32_t *nmoves,
+                        int32_t *nerrors, int32_t *out_bw, int32_t *out_rounds)
+{
+    const std::string fn = "rf_pair_align_smart";
+    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && (!moves == !moves_off);
+    if (int e = pair_check(ctx, fn, true, args_ok, npairs, seq, tpl, bw, flags))
+        return e;
+    if (npairs > 0 && !threshold)
+        return fail(ctx, RF_ERR_ARG, fn + ": threshold is NULL");
+    if (max_doublings < 0 || max_doublings > 5)
+        return fail(ctx, RF_ERR_ARG, fn + ": max_doublings must be 0..5");
+    std::vector<int32_t> cur((size_t)npairs), maxbw((size_t)npairs);
+    for (int64_t k = 0; k < npairs; ++k) {
+        const int64_t n = ctx->seqs[seq[k]].n, m = ctx->tpls[tpl[k]].m;
+        // model.jl:648-651
+        const int64_t mb = (fixed && fixed[k]) ? bw[k] : std::min({(int64_t)bw[k] << max_doublings, m, n});
+        const int64_t H = 2 * mb + std::abs(n - m) + 1;
+        if (H > DPW_LDS_H)
+            return fail(ctx, RF_ERR_ARG,
+                        fn + ": band of " + std::to_string(H) + " rows at the largest bandwidth " +
+                            std::to_string(mb) + " (pair " + std::to_string(k) + ") is wider than the " +
+                            std::to_string(DPW_LDS_H) + " a bandless pass holds in LDS");
+        cur[(size_t)k] = bw[k];
+        maxbw[(size_t)k] = (int32_t)mb;
+    }
+    const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
+    const bool want = moves || nmoves || nerrors;
+    // the loop reads every pair's score and error count, whatever the caller asked for
+    std::vector<double> sc_own;
+    std::vector<int32_t> ne_own;
+    if (!out_score) {
+        sc_own.resize((size_t)npairs);
+        out_score = sc_own.data();
+    }
+    if (!nerrors) {
+        ne_own.resize((size_t)npairs);
+        nerrors = ne_own.data();
+    }
+    std::vector<int32_t> n_err((size_t)npairs, INT32_MAX), old_err((size_t)npairs, INT32_MAX);
+    std::vector<int64_t> pending((size_t)npairs), next;
+    std::vector<uint8_t> more((size_t)npairs, 0);
+    for (int64_t k = 0; k < npairs; ++k)
+        pending[(size_t)k] = k;
+    if (out_rounds)
+        std::fill(out_rounds, out_rounds + npairs, 0);
+    auto stops_at_fill = [&](int64_t k) { return (fixed && fixed[k]) || cur[(size_t)k] >= maxbw[(size_t)k]; };
+    auto ended = [&](int64_t k, double score, int32_t, int32_t ne) {
+        more[(size_t)k] = 0;
+        if (score != score || stops_at_fill(k))   // the reference raised / model.jl:656-658
+            return true;
+        old_err[(size_t)k] = n_err[(size_t)k];
+        n_err[(size_t)k] = ne;
+        // a walk that failed (-1) ends the pair like the error it would be
+        more[(size_t)k] = ne >= 0 && (double)ne > threshold[k] && ne < old_err[(size_t)k];
+        return !more[(size_t)k];
+    };
+    while (!pending.empty()) {
+        bool walk = want;
+        for (int64_t k : pending)
+            walk = walk || !stops_at_fill(k);
+        if (int e = pair_align_run(ctx, (int64_t)pending.size(), pending.data(), seq, tpl, cur.data(), fl, walk,
+                                   out_score, moves, moves_off, nmoves, nerrors, ended))
+            return e;
+        next.clear();
+        for (int64_t k : pending) {
+            if (out_rounds)
+                ++out_rounds[k];
+            if (!walk)
+                continue;   // every pair of the round stopped at its fill
+            if (more[(size_t)k]) {
+                cur[(size_t)k] = (int32_t)std::min<int64_t>(2 * (int64_t)cur[(size_t)k], maxbw[(size_t)k]);
+                next.push_back(k);
+            }
+        }
+        pending.swap(next);
+    }
+    if (out_bw)
+        std::copy(cur.begin(), cur.end(), out_bw);
     return 0;
 }
 

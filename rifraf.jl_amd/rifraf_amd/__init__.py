@@ -35,7 +35,8 @@ def __getattr__(name):
     if name in ("cross_scores", "choose_references"):
         from . import assign
         return getattr(assign, name)
-    if name in ("align_moves_many", "align_many", "edit_distances", "correct_shifts_many"):
+    if name in ("align_moves_many", "align_many", "smart_align_moves_many", "smart_align_many", "edit_distances",
+                "correct_shifts_many"):
         from . import pairalign
         return getattr(pairalign, name)
     if name in ("sample_sequences", "sample_mixture", "sample_from_template", "sample_reference",

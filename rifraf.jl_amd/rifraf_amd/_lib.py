@@ -60,6 +60,8 @@ _SIGNATURES = {
     "rf_pair_align": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p]),
     "rf_last_pair_align_ms": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
+    "rf_pair_align_smart": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                    c_int32] + [c_void_p] * 7),
     "rf_backtrace": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rf_score": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_void_p]),
@@ -82,10 +84,11 @@ OPTIONS = {"score_mode": 1, "score_kernel": 2, "lean_lds_kb": 4, "dp_psplit": 10
            "band_pad": 17, "dp_wide": 18, "aln_sums_host": 19,
            "aln_marks_min": 22, "sync_block": 23, "dp_nl64": 24, "dp_lat": 26,
            "score_wgs": 27, "seg_wgs": 28, "dp_pfit": 29, "dp_mc": 30, "bt_nw": 31, "pair_chunk": 32,
-           "pair_trace_mb": 33}
+           "pair_trace_mb": 33, "pair_walk": 34}
 # symbolic values of the enum-like options
 OPTION_VALUES = {"score_mode": {"auto": 0, "fused": 1, "split": 2},
-                 "score_kernel": {"auto": 0, "general": 1, "seg": 2, "ws": 3}}
+                 "score_kernel": {"auto": 0, "general": 1, "seg": 2, "ws": 3},
+                 "pair_walk": {"auto": 0, "lane": 1, "wave": 2}}
 
 
 

@@ -17,11 +17,17 @@ from .types import DNASeq
 
 
 def cross_scores(seqs, templates, bandwidth=None, engine=None, first_seq=0, first_tpl=0,
-                 skew_matches=False, trim=False) -> np.ndarray:
+                 skew_matches=False, trim=False, bandwidth_pvalue=None, return_bandwidths=False,
+                 max_doublings=5):
     """(R, T) matrix of A[end, end] of every RifrafSequence against every
     template, in one engine call.  The sequences are uploaded as ids
     [first_seq, first_seq + R) and the templates as [first_tpl, first_tpl +
-    T).  bandwidth=None uses each sequence's own."""
+    T).  bandwidth=None uses each sequence's own.  bandwidth_pvalue=None
+    scores every cell at that bandwidth (rf_pair_scores); a value starts
+    there and doubles the band of each cell as smart_forward_moves!
+    (model.jl:643-672) does (rf_pair_align_smart, no moves kept), without
+    changing the sequences.  return_bandwidths: -> (scores, (R, T) int32
+    bandwidths the cells were scored at)."""
     from .align import default_engine
     from .engine import RF_SKEW, RF_TRIM
     e = engine or default_engine()
@@ -29,7 +35,7 @@ def cross_scores(seqs, templates, bandwidth=None, engine=None, first_seq=0, firs
     templates = [DNASeq(t) for t in templates]
     R, T = len(seqs), len(templates)
     if R == 0 or T == 0:
-        return np.empty((R, T))
+        return (np.empty((R, T)), np.empty((R, T), np.int32)) if return_bandwidths else np.empty((R, T))
     e.set_sequences(first_seq, seqs)
     e.set_templates(first_tpl, templates)
     if bandwidth is None:
@@ -37,7 +43,24 @@ def cross_scores(seqs, templates, bandwidth=None, engine=None, first_seq=0, firs
     else:
         bws = np.full((R, 1), int(bandwidth), np.int32)
     flags = (RF_SKEW if skew_matches else 0) | (RF_TRIM if trim else 0)
-    return e.pair_scores(first_seq + np.arange(R)[:, None], first_tpl + np.arange(T)[None, :], bws, flags)
+    si, ti = first_seq + np.arange(R)[:, None], first_tpl + np.arange(T)[None, :]
+    if bandwidth_pvalue is None:
+        out = e.pair_scores(si, ti, bws, flags)
+        return (out, np.broadcast_to(bws, (R, T)).astype(np.int32)) if return_bandwidths else out
+    from .pairalign import MAX_BAND_ROWS, max_bandwidths, smart_inputs
+    from .engine import RifrafError
+    thr, fixed = smart_inputs(seqs, np.arange(R), bandwidth_pvalue)
+    slen = np.array([len(s) for s in seqs], np.int64)[:, None]
+    tlen = np.array([len(t) for t in templates], np.int64)[None, :]
+    rows = 2 * max_bandwidths(bws, fixed[:, None], slen, tlen, max_doublings) + np.abs(slen - tlen) + 1
+    if (rows > MAX_BAND_ROWS).any():
+        r, j = (int(x[0]) for x in np.nonzero(rows > MAX_BAND_ROWS))
+        raise RifrafError(f"sequence {r}, template {j}: band of {int(rows[r, j])} rows at its largest bandwidth is "
+                          f"wider than the {MAX_BAND_ROWS} the engine aligns without bands")
+    sc, _, _, out_bw, _ = e.pair_align_smart(si, ti, bws, thr[:, None], fixed=fixed[:, None],
+                                             max_doublings=max_doublings, flags=flags, want_moves=False)
+    sc, out_bw = sc.reshape(R, T), out_bw.reshape(R, T)
+    return (sc, out_bw) if return_bandwidths else sc
 
 
 def fold_totals(scores) -> np.ndarray:
@@ -55,12 +78,16 @@ def first_maximum(totals) -> int:
     return int(np.argmax(np.asarray(totals)))
 
 
-def choose_references(clusters, references, scores=None, bandwidth=9, phred_cap=None, engine=None):
+def choose_references(clusters, references, scores=None, bandwidth=9, phred_cap=None, engine=None,
+                      bandwidth_pvalue=None):
     """The reference of each cluster.  clusters: (dnaseqs, phreds) per
     cluster; references: bare base sequences.  Every read (with its Phred
     tables, capped at phred_cap if given) is aligned to every reference as
     the *template*; totals[j] is the left fold of the cluster's scores against
-    reference j and the first maximum wins.  -> [(index, totals)]."""
+    reference j and the first maximum wins.  bandwidth_pvalue: as in
+    cross_scores (None: every cell at `bandwidth`; a value: band doubling
+    from there, so a read against a reference it fits badly is not
+    under-scored).  -> [(index, totals)]."""
     if scores is None:
         scores = Scores.from_errors(ErrorModel(1.0, 2.0, 2.0))
     out = []
@@ -68,7 +95,8 @@ def choose_references(clusters, references, scores=None, bandwidth=9, phred_cap=
         if phred_cap is not None:
             phreds = [cap_phreds(p, phred_cap) for p in phreds]
         seqs = [RifrafSequence(s, np.asarray(p, np.int8), bandwidth, scores) for s, p in zip(dnaseqs, phreds)]
-        totals = fold_totals(cross_scores(seqs, references, bandwidth=bandwidth, engine=engine))
+        totals = fold_totals(cross_scores(seqs, references, bandwidth=bandwidth, engine=engine,
+                                           bandwidth_pvalue=bandwidth_pvalue))
         out.append((first_maximum(totals), totals))
     return out
 

@@ -406,8 +406,56 @@ class Engine:
                    for k in range(n)]
         return scores[:n], out, nerr[:n].copy()
 
+    def pair_align_smart(self, seqs, tpls, bws, thresholds, fixed=None, max_doublings: int = 5, flags=0,
+                         want_moves: bool = True, caps=None):
+        """rf_pair_align_smart: pair_align with smart_forward_moves!' band
+        doubling (model.jl:643-672) per pair.  bws: starting bandwidths;
+        thresholds: cquantile(Poisson(est_n_errors), pvalue) per pair; fixed:
+        bandwidth_fixed per pair (None: none).  All five broadcast against
+        each other.  caps: n + m of each pair when the caller knows them (else
+        a counts-only call comes first).  Returns (scores, moves, nerrors,
+        bandwidths, rounds) over the flattened pairs, the first three as
+        pair_align's for the last fill of each pair."""
+        arrs = [np.asarray(seqs), np.asarray(tpls), np.asarray(bws), np.asarray(thresholds, np.float64)]
+        if fixed is not None:
+            arrs.append(np.asarray(fixed))
+        arrs = np.broadcast_arrays(*arrs)
+        seqs = np.ascontiguousarray(arrs[0].reshape(-1), np.int32)
+        tpls = np.ascontiguousarray(arrs[1].reshape(-1), np.int32)
+        bws = np.ascontiguousarray(arrs[2].reshape(-1), np.int32)
+        thr = np.ascontiguousarray(arrs[3].reshape(-1), np.float64)
+        fx = np.ascontiguousarray(arrs[4].reshape(-1) != 0, np.uint8) if fixed is not None else None
+        n = seqs.shape[0]
+        scores = np.empty(max(n, 1))
+        nmoves = np.empty(max(n, 1), np.int32)
+        nerr = np.empty(max(n, 1), np.int32)
+        out_bw = np.empty(max(n, 1), np.int32)
+        rounds = np.empty(max(n, 1), np.int32)
+        moves = moves_off = None
+
+        def call(sc, mv, off, nm, ne, ob, rd):
+            self._check(self.lib.rf_pair_align_smart(self.ctx, n, ptr(seqs), ptr(tpls), ptr(bws), ptr(thr), ptr(fx),
+                                                     int(max_doublings), int(flags), ptr(sc), ptr(mv), ptr(off),
+                                                     ptr(nm), ptr(ne), ptr(ob), ptr(rd)))
+
+        if want_moves:
+            if caps is None:
+                call(None, None, None, nmoves, None, None, None)
+                caps = np.maximum(nmoves[:n], 0)
+            caps = np.broadcast_to(np.asarray(caps, np.int64).reshape(-1), (n,))
+            moves_off = np.zeros(n + 1, np.int64)
+            np.cumsum(caps, out=moves_off[1:])
+            moves = np.empty(max(int(moves_off[-1]), 1), np.int8)
+        call(scores, moves, moves_off, nmoves, nerr, out_bw, rounds)
+        out = None
+        if want_moves:
+            out = [moves[moves_off[k]:moves_off[k] + nmoves[k]].copy() if nmoves[k] >= 0 else None
+                   for k in range(n)]
+        return scores[:n], out, nerr[:n].copy(), out_bw[:n].copy(), rounds[:n].copy()
+
     def last_pair_align_ms(self):
-        """(fill ms, walk ms) of the last pair_align call (all its launch sets)."""
+        """(fill ms, walk ms) of the last pair_align / pair_align_smart call
+        (all its launch sets and rounds)."""
         f, w = c_double(), c_double()
         self._check(self.lib.rf_last_pair_align_ms(self.ctx, byref(f), byref(w)))
         return f.value, w.value

@@ -16,11 +16,13 @@ import numpy as np
 from .align import moves_to_aligned_seqs
 from .engine import RF_SKEW, RF_TRIM, RifrafError
 from .errormodel import ErrorModel, Scores
+from .poisson import cquantile_poisson_many
 from .proposals import Deletion, Insertion, apply_proposals
 from .rifrafsequences import RifrafSequence
 from .types import DNASeq
 
 MAX_BAND_ROWS = 160 * 1024 // 32 - 6   # DPW_LDS_H: the widest band a bandless pass holds in LDS
+BANDWIDTH_PVALUE = 0.1                 # RifrafParams' default bandwidth_pvalue (model.py)
 
 
 def _engine(engine):
@@ -42,23 +44,38 @@ def _pairs(pairs, nseq, ntpl):
     return pairs[:, 0], pairs[:, 1]
 
 
-def _run(e, seqs, templates, si, ti, bws, flags, want_moves):
+def max_bandwidths(bws, fixed, slen, tlen, max_doublings):
+    """smart_forward_moves!' max_bandwidth (model.jl:648-651) per pair."""
+    bws = np.asarray(bws, np.int64)
+    grown = np.minimum(np.minimum(bws << int(max_doublings), tlen), slen)
+    return np.where(np.asarray(fixed, bool), bws, grown)
+
+
+def _run(e, seqs, templates, si, ti, bws, flags, want_moves, smart=None):
     """One rf_pair_align call over pairs (si[k], ti[k]); sequences and
-    templates are uploaded as ids 0.. of the engine."""
+    templates are uploaded as ids 0.. of the engine.  smart = (thresholds,
+    fixed, max_doublings): one rf_pair_align_smart call, and the band that
+    must fit is the one at the largest bandwidth a pair can reach."""
     if len(si) == 0:
-        return np.empty(0), ([] if want_moves else None), np.empty(0, np.int32)
+        empty = (np.empty(0), ([] if want_moves else None), np.empty(0, np.int32))
+        return empty if smart is None else empty + (np.empty(0, np.int32), np.empty(0, np.int32))
     slen = np.array([len(s) for s in seqs], np.int64)
     tlen = np.array([len(t) for t in templates], np.int64)
     bws = np.broadcast_to(np.asarray(bws, np.int64), si.shape)
-    rows = 2 * bws + np.abs(slen[si] - tlen[ti]) + 1
+    top = bws if smart is None else max_bandwidths(bws, smart[1], slen[si], tlen[ti], smart[2])
+    rows = 2 * top + np.abs(slen[si] - tlen[ti]) + 1
     wide = np.nonzero(rows > MAX_BAND_ROWS)[0]
     if len(wide):
         k = int(wide[0])
-        raise RifrafError(f"pair {k} (sequence {int(si[k])}, template {int(ti[k])}): band of {int(rows[k])} rows "
-                          f"is wider than the {MAX_BAND_ROWS} the engine aligns without bands")
+        at = "" if smart is None else f" at its largest bandwidth {int(top[k])}"
+        raise RifrafError(f"pair {k} (sequence {int(si[k])}, template {int(ti[k])}): band of {int(rows[k])} rows"
+                          f"{at} is wider than the {MAX_BAND_ROWS} the engine aligns without bands")
     e.set_sequences(0, seqs)
     e.set_templates(0, templates)
-    return e.pair_align(si, ti, bws, flags, want_moves=want_moves, caps=slen[si] + tlen[ti])
+    if smart is None:
+        return e.pair_align(si, ti, bws, flags, want_moves=want_moves, caps=slen[si] + tlen[ti])
+    return e.pair_align_smart(si, ti, bws, smart[0], fixed=smart[1], max_doublings=smart[2], flags=flags,
+                              want_moves=want_moves, caps=slen[si] + tlen[ti])
 
 
 def align_moves_many(seqs, templates, pairs=None, bandwidth=None, skew_matches=False, trim=False, engine=None):
@@ -88,6 +105,51 @@ def align_many(seqs, templates, pairs=None, bandwidth=None, skew_matches=False, 
                              trim=trim, engine=engine)
     return [None if mv is None else moves_to_aligned_seqs(mv, templates[int(j)], seqs[int(i)].seq)
             for mv, i, j in zip(moves, si, ti)]
+
+
+def smart_inputs(seqs, si, pvalue):
+    """(thresholds, fixed) of pairs whose sequences are seqs[si]: the
+    cquantile(Poisson(est_n_errors), pvalue) of model.jl:661 and each
+    sequence's bandwidth_fixed."""
+    thr = np.asarray(cquantile_poisson_many([s.est_n_errors for s in seqs], pvalue), np.float64)
+    fixed = np.array([bool(s.bandwidth_fixed) for s in seqs], bool)
+    return thr[si], fixed[si]
+
+
+def smart_align_moves_many(seqs, templates, pairs=None, pvalue=BANDWIDTH_PVALUE, max_doublings=5, bandwidth=None,
+                           skew_matches=False, trim=False, engine=None):
+    """align_moves_many with smart_forward_moves!' band doubling
+    (model.jl:643-672) per pair, in one engine call: the bandwidth (each
+    sequence's own, or `bandwidth`) is where a pair starts.  The
+    RifrafSequences are not changed -- one sequence may be in many pairs --
+    so the bandwidths the pairs ended at are returned.
+    -> (moves as align_moves_many's, int32 bandwidths)."""
+    seqs = list(seqs)
+    templates = [DNASeq(t) for t in templates]
+    si, ti = _pairs(pairs, len(seqs), len(templates))
+    if bandwidth is None:
+        bws = np.array([s.bandwidth for s in seqs], np.int64)[si]
+    else:
+        bws = np.full(si.shape, int(bandwidth), np.int64)
+    thr, fixed = smart_inputs(seqs, si, pvalue)
+    flags = (RF_SKEW if skew_matches else 0) | (RF_TRIM if trim else 0)
+    _, moves, _, out_bw, _ = _run(_engine(engine), seqs, templates, si, ti, bws, flags, True,
+                                  smart=(thr, fixed, max_doublings))
+    return moves, out_bw
+
+
+def smart_align_many(seqs, templates, pairs=None, pvalue=BANDWIDTH_PVALUE, max_doublings=5, bandwidth=None,
+                     skew_matches=False, trim=False, engine=None):
+    """align_many over smart_align_moves_many
+    -> ([(aligned t, aligned s)] with None for a pair the reference raises
+    on, int32 bandwidths)."""
+    seqs = list(seqs)
+    templates = [DNASeq(t) for t in templates]
+    si, ti = _pairs(pairs, len(seqs), len(templates))
+    moves, out_bw = smart_align_moves_many(seqs, templates, pairs=pairs, pvalue=pvalue, max_doublings=max_doublings,
+                                           bandwidth=bandwidth, skew_matches=skew_matches, trim=trim, engine=engine)
+    return [None if mv is None else moves_to_aligned_seqs(mv, templates[int(j)], seqs[int(i)].seq)
+            for mv, i, j in zip(moves, si, ti)], out_bw
 
 
 def edit_distances(templates, seqs, engine=None) -> np.ndarray:
@@ -160,4 +222,5 @@ def correct_shifts_many(consensuses, references, log_p=-1.0, bandwidth=-1, score
     return out
 
 
-__all__ = ["align_moves_many", "align_many", "edit_distances", "correct_shifts_many", "MAX_BAND_ROWS"]
+__all__ = ["align_moves_many", "align_many", "smart_align_moves_many", "smart_align_many", "edit_distances",
+           "correct_shifts_many", "MAX_BAND_ROWS"]
