@@ -393,6 +393,20 @@ int rf_score_dense(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off,
 int rf_score_dense_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off,
                        const int32_t *slots, double *dev_out);
 
+/* rf_score_dense with the reference term of score_proposal(m, state, newcols,
+ * use_ref = true) (model.jl:385-399 over :302-383): ref_slot[g] >= 0 adds
+ * s_ref last, out = (0.0 + s_1 + ... + s_R) + s_ref; ref_slot[g] = -1 gives
+ * rf_score_dense's bits for that group.  s_ref is rf_score's reference score
+ * of the slot's proposal (codon moves when the reference's sequence has codon
+ * tables), computed for the whole table by k_codon_dense without a
+ * per-proposal descriptor or scratch column; a slot the reference would raise
+ * on is NaN.  ref_slot must not be NULL; a reference slot must be known
+ * (RF_ERR_ARG), hold current A and B bands (RF_ERR_STATE, as rf_score) of the
+ * group's template (RF_ERR_ARG).  Everything else is rf_score_dense's,
+ * out == NULL included. */
+int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off,
+                       const int32_t *slots, const int32_t *ref_slot, double *out);
+
 /* Native batched rifraf() (src/model.jl:1116-1275) for reference-free
  * clusters: the INIT stage of every cluster runs in lockstep on this context
  * with one batched engine call per step kind (rifraf_batch.cpp); each
@@ -567,6 +581,8 @@ int rf_last_backtrace_ms(const rf_ctx *ctx, double *ms);
  * model.jl:287-383) in the last rf_score call, milliseconds (0 when the call
  * scored no reference); it is part of that call's score_ms. */
 int rf_last_codon_ms(const rf_ctx *ctx, double *ms);
+/* k_codon_dense ms of the last rf_score_dense_ref (inside its score_ms). */
+int rf_last_codon_dense_ms(const rf_ctx *ctx, double *ms);
 
 #ifdef __cplusplus
 }

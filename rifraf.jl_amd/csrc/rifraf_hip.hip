@@ -24,6 +24,8 @@
 //               :385-399 (fold)
 //   k_codon     codon-move scoring (reference sequence), one lane per
 //               proposal  src/model.jl:287-383
+//   k_codon_dense  the same score for every dense slot of a group, one lane
+//               per slot, new columns in registers (rf_score_dense_ref)
 //   k_reduce    ordered fold of per-read partials (split mode)
 //   k_gather    proposal list -> totals (+ reference score, last)
 //   k_bt_win    moves recomputed from the stored A band, backtrace +
@@ -4314,6 +4316,263 @@ __global__ void k_codon(const CodonTask *__restrict__ tasks, int ntasks,
     out[T.out_idx] = (best == -RF_INF) ? qnan : best;
 }
 
+// ---------------------------------------------------------------------
+// k_codon_dense: k_codon's score for every dense slot of a group, one lane
+// per slot, no per-proposal scratch and no per-proposal descriptor
+// (rf_score_dense_ref).
+//
+// In update_nc, new column j at row i reads column j at rows i-1 and i-3,
+// column j-1 at rows i and i-1 and column j-3 at row i (a column of A for
+// j <= 3, new column 1 for j = 4).  So the up-to-four new columns advance row
+// by row together, each with its last four rows in registers (h[j][0..3] =
+// rows i .. i-3), column 1 first; the closing summax against B accumulates
+// as the rows pass (ascending, first value then fmax, as summax_nc).  Every
+// candidate, gate and addition is k_codon's, in k_codon's order, so the
+// result has k_codon's bits; k_codon stops at the first failed update where
+// this kernel goes on and reports NaN at the end.
+//
+// Lane order is the dense table's: slot = p * 9 + k, so the nine lanes of a
+// position read the same A / B cells and table rows.  The lane adds its
+// score to the reads' total in place (total + s_ref).  Sub / Del of p = 0 get
+// NaN; the consensus base's own Sub slot is left as the scorer wrote it.
+// ---------------------------------------------------------------------
+
+// one per group that has a reference slot, ordered by blk0
+struct alignas(16) CodonDenseGroup {
+    int64_t A, B, sb, tab, tb;   // the reference's bands, bases and tables; template bases
+    int64_t dense_off;           // the group's totals [m+1][9]
+    int32_t n, m, bw, H;
+    int32_t ncins, ncdel, P;
+    int32_t blk0;                // first workgroup of the group
+};
+
+__device__ __forceinline__ double codon_dense_sref(const Geo &g, const double *__restrict__ A,
+                                                   const double *__restrict__ B,
+                                                   const uint8_t *__restrict__ s,
+                                                   const uint8_t *__restrict__ cons,
+                                                   const double *__restrict__ tb, int ncins, int ncdel,
+                                                   int kind, int pos, int base)
+{
+    const double qnan = __builtin_nan("");
+    const int n = g.n, m = g.m;
+    const int nrows = n + 1, ncols = m + 1;
+    int acol, n_new, n_new_bases = 1, nsum, bj0;
+    if (ncins == 0 && ncdel == 0) {
+        // score_nocodon on a single sequence (model.jl:242-285)
+        if (kind == 2) {
+            // seq_score_deletion: summax(A col pos, B col pos+1) (model.jl:227-236)
+            int as, ae, bs, be;
+            g.rows(pos - 1, as, ae);
+            g.rows(pos, bs, be);
+            const int lo = max(as, bs), hi = min(ae, be);
+            double r = -RF_INF;
+            for (int i = lo; i <= hi; ++i) {
+                const double x = g.get(A, i, pos - 1) + g.get(B, i, pos);
+                r = (i == lo) ? x : fmax(r, x);
+            }
+            return r;
+        }
+        acol = pos + (kind == 0 ? 0 : 1);
+        n_new = 1;
+        nsum = 1;
+        bj0 = pos + 1;
+    } else {
+        // codon path (model.jl:310-383)
+        acol = pos + (kind == 1 ? 0 : -1) + 1;
+        const int first_bcol = acol + (kind == 1 ? 1 : 2);
+        const int last_bcol = first_bcol + 2;
+        if (kind == 2 && acol == ncols - 1)
+            return g.get(A, nrows - 1, ncols - 2);
+        const bool just_a = last_bcol >= ncols;
+        const int n_after = !just_a ? 3 : m - pos;
+        n_new_bases = kind == 2 ? 0 : 1;
+        if (n_new_bases == 0 && n_after == 0)
+            return qnan;
+        n_new = n_new_bases + n_after;
+        // sub_consensus: the proposal's base, then the consensus after pos
+        if (n_new_bases + min(n_after, m - pos) < n_new || n_new > 4)
+            return qnan;
+        nsum = just_a ? 0 : 3;
+        bj0 = first_bcol;
+    }
+
+    // per new column (0-based j here; update_nc's column is acol + j + 1)
+    double h[4][4], r[4];
+    int amin[4], amax[4], slo[4], shi[4], bjc[4], subb[4];
+    int imin = INT_MAX, imax = 0;
+    bool nob = false;   // a B column past the band's last (k_codon: NaN)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            h[j][q] = -RF_INF;
+        r[j] = -RF_INF;
+        amin[j] = 1;
+        amax[j] = 0;
+        slo[j] = 1;
+        shi[j] = 0;
+        bjc[j] = 0;
+        subb[j] = 4;
+        if (j < n_new) {
+            int a, b;
+            g.rows(min(acol + j + 1, ncols) - 1, a, b);
+            amin[j] = a + 1;
+            amax[j] = b + 1;
+            imin = min(imin, amin[j]);
+            imax = max(imax, amax[j]);
+            subb[j] = j < n_new_bases ? base : cons[pos + j - n_new_bases];
+            const int sidx = j - (n_new - nsum);   // >= 0: summed with B column bj0 + sidx
+            if (sidx >= 0) {
+                const int bj = bj0 + sidx;
+                if (bj > ncols) {
+                    nob = true;
+                } else {
+                    int bs, be;
+                    g.rows(bj - 1, bs, be);
+                    slo[j] = max(amin[j], bs + 1);
+                    shi[j] = min(amax[j], be + 1);
+                    bjc[j] = bj;
+                }
+            }
+        }
+    }
+
+    const double *t_cins = tb + 4 * (size_t)n + 1;
+    const double *t_cdel = t_cins + ncins;
+    bool bad = false;
+    double last = -RF_INF;   // the last new column at the band's last row (just_a)
+    for (int i = imin; i <= imax; ++i) {
+        // align.jl:50-112, 1-based row i as update_nc
+        const int seq_i = max(i - 1, 1);
+        const int sb = i > 1 ? s[i - 2] : 4;
+        const double t_m = tb[seq_i - 1];
+        const double t_x = tb[n + seq_i - 1];
+        const double is = tb[2 * n + seq_i - 1];
+        const double ds = tb[3 * n + i - 1];
+        const double cis = (ncins > 0 && i > 3) ? t_cins[i - 3 - 1] : 0.0;
+        const double cds = ncdel > 0 ? t_cdel[i - 1] : 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < n_new) {
+                h[j][3] = h[j][2];
+                h[j][2] = h[j][1];
+                h[j][1] = h[j][0];
+                h[j][0] = -RF_INF;
+                if (i >= amin[j] && i <= amax[j]) {
+                    const int jabs = acol + j + 1;
+                    const int cself = min(jabs, ncols) - 1;       // 0-based range columns
+                    const int cprev = min(jabs - 1, ncols) - 1;
+                    const double ms = (sb == subb[j]) ? t_m : t_x;
+                    double best = -RF_INF;
+                    if (g.inband(i - 2, cprev)) {                 // match
+                        double v;
+                        if (j == 0)
+                            v = g.get(A, i - 2, jabs - 2);
+                        else
+                            v = h[j > 0 ? j - 1 : 0][1];
+                        const double sc = v + ms;
+                        if (sc > best)
+                            best = sc;
+                    }
+                    if (g.inband(i - 2, cself)) {                 // insert
+                        const double sc = h[j][1] + is;
+                        if (sc > best)
+                            best = sc;
+                    }
+                    if (g.inband(i - 1, cprev)) {                 // delete
+                        double v;
+                        if (j == 0)
+                            v = g.get(A, i - 1, jabs - 2);
+                        else
+                            v = h[j > 0 ? j - 1 : 0][0];
+                        const double sc = v + ds;
+                        if (sc > best)
+                            best = sc;
+                    }
+                    if (ncins > 0 && i > 3 && g.inband(i - 4, cself)) {   // codon insert
+                        const double sc = h[j][3] + cis;
+                        if (sc > best)
+                            best = sc;
+                    }
+                    if (ncdel > 0 && jabs > 3 && g.inband(i - 1, min(jabs - 3, ncols) - 1)) {   // codon delete
+                        double v;
+                        if (j < 3)
+                            v = g.get(A, i - 1, jabs - 4);
+                        else
+                            v = h[0][0];
+                        const double sc = v + cds;
+                        if (sc > best)
+                            best = sc;
+                    }
+                    h[j][0] = best;
+                    bad = bad || best == -RF_INF;
+                    if (bjc[j] > 0 && i >= slo[j] && i <= shi[j]) {
+                        const double x = best + g.get(B, i - 1, bjc[j] - 1);
+                        r[j] = (i == slo[j]) ? x : fmax(r[j], x);
+                    }
+                    if (j == n_new - 1 && i == nrows)
+                        last = best;
+                }
+            }
+        }
+    }
+    if (bad)
+        return qnan;
+    if (ncins == 0 && ncdel == 0)
+        return r[0] == -RF_INF ? qnan : r[0];
+    if (nsum == 0)
+        return last;
+    if (nob)
+        return qnan;
+    double best = -RF_INF;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (bjc[j] > 0 && r[j] > best)
+            best = r[j];
+    return best == -RF_INF ? qnan : best;
+}
+
+__global__ void __launch_bounds__(64)
+k_codon_dense(const CodonDenseGroup *__restrict__ groups, int ngroups,
+              const uint8_t *__restrict__ bases, const double *__restrict__ tabs,
+              const double *__restrict__ bands, double *__restrict__ dense)
+{
+    // the group of this workgroup: the last descriptor with blk0 <= blockIdx.x
+    int glo = 0, ghi = ngroups - 1;
+    while (glo < ghi) {
+        const int mid = (glo + ghi + 1) >> 1;
+        if (groups[mid].blk0 <= (int)blockIdx.x)
+            glo = mid;
+        else
+            ghi = mid - 1;
+    }
+    const CodonDenseGroup G = groups[glo];
+    const int idx = ((int)blockIdx.x - G.blk0) * 64 + (int)threadIdx.x;
+    if (idx >= 9 * (G.m + 1))
+        return;
+    const int p = idx / 9, k = idx - 9 * p;
+    const int kind = k < 4 ? 0 : (k == 4 ? 2 : 1);
+    const int base = k < 4 ? k : (k == 4 ? 0 : k - 5);
+    double *dst = dense + G.dense_off + idx;
+    const uint8_t *cons = bases + G.tb;
+    if (kind != 1 && p == 0) {
+        *dst = __builtin_nan("");
+        return;
+    }
+    if (kind == 0 && cons[p - 1] == base)
+        return;   // the consensus base's own slot: not a proposal
+    Geo g;
+    g.n = G.n;
+    g.m = G.m;
+    g.bw = G.bw;
+    g.H = G.H;
+    g.P = G.P;
+    g.c = max(G.m - G.n, 0) + G.bw;
+    const double sref = codon_dense_sref(g, bands + G.A, bands + G.B, bases + G.sb, cons, tabs + G.tab,
+                                         G.ncins, G.ncdel, kind, p, base);
+    *dst = *dst + sref;
+}
+
 // totals for the proposal list: reads fold (dense) + reference score last
 __global__ void k_gather(int64_t nprops, const int32_t *__restrict__ pgroup,
                          const uint8_t *__restrict__ kind, const int32_t *__restrict__ pos,
@@ -5394,8 +5653,9 @@ struct rf_ctx {
     // a plan validated at the current epoch with the same job / slot list
     // needs no per-slot validation again
     uint64_t state_epoch = 1;
-    DevBuf scratch[34];   // 28, 29: rf_pair_scores' / rf_pair_align's descriptors and scores;
-                          // 30-33: rf_pair_align's trace, moves, move offsets and counts
+    DevBuf scratch[35];   // 28, 29: rf_pair_scores' / rf_pair_align's descriptors and scores;
+                          // 30-33: rf_pair_align's trace, moves, move offsets and counts;
+                          // 34: rf_score_dense_ref's group descriptors
     // pinned host staging for sequence uploads (pageable H2D copies of a few
     // MB took ~14 ms per cluster upload on the box: page locking per call)
     void *pinned = nullptr;
@@ -5416,6 +5676,7 @@ struct rf_ctx {
     int *d_err = nullptr;
     double dp_ms = 0, score_ms = 0, gather_ms = 0, bt_ms = 0;
     double codon_ms = 0;        // k_codon of the last rf_score (inside score_ms)
+    double codon_dense_ms = 0;  // k_codon_dense of the last rf_score_dense_ref (inside score_ms)
     double pair_ms = 0;         // kernels of the last rf_pair_scores
     double pa_fill_ms = 0, pa_walk_ms = 0;   // fills / walks of the last rf_pair_align
     hipEvent_t ev_codon = nullptr;
@@ -7849,6 +8110,39 @@ int rf_alignment_proposals(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off
     return 0;
 }
 
+// rf_score's check of a slot it scores: both bands filled, for one alignment,
+// and neither the template nor the sequence replaced since
+static bool score_band_ok(const rf_ctx *ctx, int32_t s, std::string &why)
+{
+    if (s < 0 || s >= (int32_t)ctx->slots.size()) {
+        why = "unknown slot";
+        return false;
+    }
+    const Slot &S = ctx->slots[s];
+    if (!S.a.valid || !S.b.valid) {
+        why = "slot has no A/B bands";
+        return false;
+    }
+    if (S.a.seq != S.b.seq || S.a.tpl != S.b.tpl || S.a.bw != S.b.bw || S.a.tplver != S.b.tplver ||
+        S.a.m != S.b.m || S.a.seqver != S.b.seqver || S.a.n != S.b.n) {
+        why = "A and B bands were computed for different alignments";
+        return false;
+    }
+    if (S.a.P != S.b.P) {
+        why = "A and B bands have different row strides";
+        return false;
+    }
+    if (ctx->tpls[S.a.tpl].version != S.a.tplver) {
+        why = "template changed since the bands were computed";
+        return false;
+    }
+    if (seq_stale(ctx, S.a)) {
+        why = "sequence changed since the bands were computed";
+        return false;
+    }
+    return true;
+}
+
 int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
              const int32_t *ref_slot, const int64_t *prop_off, const uint8_t *kind,
              const int32_t *pos, const uint8_t *base, double *out_total, double *out_per_seq)
@@ -7860,35 +8154,7 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
     if (nprops > 0 && (!kind || !pos || !base || !out_total))
         return fail(ctx, RF_ERR_ARG, "rf_score: bad proposal arrays");
 
-    auto band_ok = [&](int32_t s, std::string &why) -> bool {
-        if (s < 0 || s >= (int32_t)ctx->slots.size()) {
-            why = "unknown slot";
-            return false;
-        }
-        const Slot &S = ctx->slots[s];
-        if (!S.a.valid || !S.b.valid) {
-            why = "slot has no A/B bands";
-            return false;
-        }
-        if (S.a.seq != S.b.seq || S.a.tpl != S.b.tpl || S.a.bw != S.b.bw || S.a.tplver != S.b.tplver ||
-            S.a.m != S.b.m || S.a.seqver != S.b.seqver || S.a.n != S.b.n) {
-            why = "A and B bands were computed for different alignments";
-            return false;
-        }
-        if (S.a.P != S.b.P) {
-            why = "A and B bands have different row strides";
-            return false;
-        }
-        if (ctx->tpls[S.a.tpl].version != S.a.tplver) {
-            why = "template changed since the bands were computed";
-            return false;
-        }
-        if (seq_stale(ctx, S.a)) {
-            why = "sequence changed since the bands were computed";
-            return false;
-        }
-        return true;
-    };
+    auto band_ok = [&](int32_t s, std::string &why) -> bool { return score_band_ok(ctx, s, why); };
 
     std::vector<ScoreGroup> groups(ngroups);
     std::vector<ScoreRead> reads;
@@ -8316,6 +8582,92 @@ int rf_score_dense_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
     return score_dense_impl(ctx, ngroups, slot_off, slots, dev_out, hipMemcpyDeviceToDevice);
 }
 
+int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
+                       const int32_t *ref_slot, double *out)
+{
+    if (!ctx || ngroups < 0 || (ngroups > 0 && (!slot_off || !slots)))
+        return fail(ctx, RF_ERR_ARG, "rf_score_dense: bad arguments");
+    if (!ref_slot)
+        return fail(ctx, RF_ERR_ARG, "rf_score_dense_ref: null ref_slot");
+    // the reference slots, before anything runs
+    bool any_ref = false;
+    for (int32_t g = 0; g < ngroups; ++g) {
+        const int32_t rs = ref_slot[g];
+        if (rs < 0)
+            continue;
+        any_ref = true;
+        std::string why;
+        if (rs >= (int32_t)ctx->slots.size())
+            return fail(ctx, RF_ERR_ARG, "rf_score_dense_ref: unknown reference slot");
+        if (!score_band_ok(ctx, rs, why))
+            return fail(ctx, RF_ERR_STATE, "rf_score_dense_ref (reference): " + why);
+        // the group's template is its first batch slot's (a bad batch slot is
+        // refused by the reads' fold below)
+        if (slot_off[g + 1] > slot_off[g]) {
+            const int32_t s0 = slots[slot_off[g]];
+            if (s0 >= 0 && s0 < (int32_t)ctx->slots.size() && ctx->slots[s0].a.valid &&
+                ctx->slots[s0].a.tpl != ctx->slots[rs].a.tpl)
+                return fail(ctx, RF_ERR_ARG, "rf_score_dense_ref: reference uses a different template");
+        }
+    }
+    // the reads' fold: totals in scratch[15]
+    if (int e = score_dense_impl(ctx, ngroups, slot_off, slots, nullptr, hipMemcpyDeviceToHost))
+        return e;
+    const auto &P = ctx->dplan;
+    ctx->codon_dense_ms = 0;
+    double *d_dense = (double *)ctx->scratch[15].p;
+    if (any_ref) {
+        std::vector<CodonDenseGroup> cg;
+        int64_t nblk = 0;
+        for (int32_t g = 0; g < ngroups; ++g) {
+            if (ref_slot[g] < 0)
+                continue;
+            const Band &A = ctx->slots[ref_slot[g]].a;
+            const Band &B = ctx->slots[ref_slot[g]].b;
+            const SeqObj &S = ctx->seqs[A.seq];
+            CodonDenseGroup G{};
+            G.A = A.r.off / 8;
+            G.B = B.r.off / 8;
+            G.sb = S.bases.off;
+            G.tab = S.tabs.off / 8;
+            G.tb = ctx->tpls[A.tpl].bases.off;
+            G.dense_off = P.groups[g].dense_off;
+            G.n = A.n;
+            G.m = A.m;
+            G.bw = A.bw;
+            G.H = A.H;
+            G.ncins = S.ncins;
+            G.ncdel = S.ncdel;
+            G.P = A.P;
+            G.blk0 = (int32_t)nblk;
+            nblk += (9 * ((int64_t)A.m + 1) + 63) / 64;
+            cg.push_back(G);
+        }
+        if (nblk > INT32_MAX)
+            return fail(ctx, RF_ERR_ARG, "rf_score_dense_ref: too many slots for one launch");
+        if (int e = upload(ctx, ctx->scratch[34], cg)) return e;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_codon, ctx->stream));
+        hipLaunchKernelGGL(k_codon_dense, dim3((unsigned)nblk), dim3(64), 0, ctx->stream,
+                           (const CodonDenseGroup *)ctx->scratch[34].p, (int)cg.size(),
+                           (const uint8_t *)ctx->bytes_arena.d, (const double *)ctx->tab_arena.d,
+                           (const double *)ctx->band_arena.d, d_dense);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+        // cg sources the upload when it does not fit the pinned ring
+        HIPCHK(ctx, stream_wait(ctx));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev_codon, ctx->ev[4]);
+        ctx->codon_dense_ms = ms;
+        ctx->score_ms += ms;
+    }
+    if (out && P.dense_total > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(out, d_dense, sizeof(double) * P.dense_total, hipMemcpyDeviceToHost,
+                                   ctx->stream));
+        HIPCHK(ctx, stream_wait(ctx));
+    }
+    return 0;
+}
+
 int rf_slot_geometry(rf_ctx *ctx, int32_t slot, int32_t which, int32_t *nrows, int32_t *ncols,
                      int32_t *bw, int32_t *H)
 {
@@ -8365,6 +8717,14 @@ int rf_last_codon_ms(const rf_ctx *ctx, double *ms)
     if (!ctx || !ms)
         return RF_ERR_ARG;
     *ms = ctx->codon_ms;
+    return 0;
+}
+
+int rf_last_codon_dense_ms(const rf_ctx *ctx, double *ms)
+{
+    if (!ctx || !ms)
+        return RF_ERR_ARG;
+    *ms = ctx->codon_dense_ms;
     return 0;
 }
 

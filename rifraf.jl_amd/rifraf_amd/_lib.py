@@ -68,12 +68,14 @@ _SIGNATURES = {
     "rf_alignment_proposals": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "rf_score_dense": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "rf_score_dense_dev": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rf_score_dense_ref": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rf_slot_geometry": (c_int, [c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32),
                                  POINTER(c_int32), POINTER(c_int32)]),
     "rf_download_band": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     "rf_last_timing": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "rf_last_backtrace_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rf_last_codon_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rf_last_codon_dense_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rf_set_option": (c_int, [c_void_p, c_int32, c_int32]),
     "rf_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int32)]),
 }

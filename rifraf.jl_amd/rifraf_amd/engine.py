@@ -568,6 +568,32 @@ class Engine:
             at += r
         return res
 
+    def score_dense_ref(self, groups, ref_slots, to_host: bool = True, rows=None):
+        """rf_score_dense_ref: score_dense with the reference's score added
+        last in every slot.  ref_slots: one slot per group, -1 for a group
+        without a reference (that group's result is score_dense's).  Returns
+        a list of (m_g+1, 9) arrays (or None when to_host is False)."""
+        pg = groups if isinstance(groups, PackedGroups) else pack_groups(groups)
+        G, slot_off, slots = pg.n, pg.slot_off, pg.slots
+        refs = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
+        if len(refs) != G:
+            raise ValueError("one reference slot per group (-1: none)")
+        if not G:
+            refs = np.full(1, -1, np.int32)   # never NULL
+        refs_p = ptr(refs)
+        if not to_host:
+            self._check(self.lib.rf_score_dense_ref(self.ctx, G, ptr(slot_off), ptr(slots), refs_p, None))
+            return None
+        if rows is None:
+            rows = [self.geometry(int(slots[slot_off[g]]), RF_BAND_B)[1] for g in range(G)]
+        out = np.empty((int(sum(rows)), 9))
+        self._check(self.lib.rf_score_dense_ref(self.ctx, G, ptr(slot_off), ptr(slots), refs_p, ptr(out)))
+        res, at = [], 0
+        for r in rows:
+            res.append(out[at:at + r])
+            at += r
+        return res
+
     def score_dense_dev(self, groups, dev_ptr: int):
         """rf_score_dense_dev: dense totals written to device memory at
         dev_ptr (sum_g (m_g+1)*9 doubles on this engine's device)."""
@@ -598,6 +624,12 @@ class Engine:
         """k_codon ms of the last score call (the reference's codon moves)."""
         v = c_double()
         self._check(self.lib.rf_last_codon_ms(self.ctx, byref(v)))
+        return v.value
+
+    def last_codon_dense_ms(self) -> float:
+        """k_codon_dense ms of the last score_dense_ref call."""
+        v = c_double()
+        self._check(self.lib.rf_last_codon_dense_ms(self.ctx, byref(v)))
         return v.value
 
     def last_timing(self):

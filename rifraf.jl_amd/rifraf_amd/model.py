@@ -616,8 +616,12 @@ def estimate_probs(state: RifrafState, run: _Run, use_ref_for_qvs: bool) -> Esti
     del_scores = np.zeros(m) + state.score
     ins_scores = np.zeros((m + 1, 4))
     use_ref_ = len(state.reference) > 0 and use_ref_for_qvs
-    kind, pos, base = score_proposal_arrays(m, state.consensus)
     slots = np.arange(len(state.batch_seqs), dtype=np.int32)
+    if use_ref_ and hasattr(run.e, "score_dense_ref"):
+        # the full set with the reference: the dense table, the reference's
+        # score added last in every slot (the same bits as the list below)
+        return estimate_probs_from_dense(state, run.e.score_dense_ref([slots], [run.REF])[0])
+    kind, pos, base = score_proposal_arrays(m, state.consensus)
     scores = run.e.score([(slots, run.REF if use_ref_ else -1, (kind, pos, base))])[0]
     k = kind.astype(np.int64)
     p = pos.astype(np.int64)
