@@ -7,12 +7,22 @@ and the consensus base's own Sub slot.
 
 The codon reference is the one correct_shifts builds: constant
 error_log_p = -1 and Scores.from_errors(ErrorModel(10, 1e-5, 1e-5, 1, 1)).
+Its six tables hold one number each, so a table read one position off is
+the same value; varying_reference (error_log_p = log10(U(0.01, 0.3)) per
+position, every table different at every position) is the reference of the
+second half of this file: the edge grid again, m at which 9 (m + 1) fills
+its last workgroup, groups without a reference between groups with one,
+tall and skewed bands, a frameshifted reference, the reads' scorers and
+folds under the in-place add, and the reference changing from call to call
+over one cached dense plan.
 """
+import functools
+
 import numpy as np
 import pytest
 
 import oracle
-from _util import all_proposals_arrays, dense_slot, make_read, random_seq
+from _util import REF_SCORES, all_proposals_arrays, dense_slot, make_read, random_seq
 from rifraf_amd import ErrorModel, RifrafSequence, Scores
 from rifraf_amd._lib import ptr
 from rifraf_amd.engine import RF_BWD, RF_FWD, Engine, RifrafError
@@ -55,25 +65,44 @@ def reference(n, bw, rng, scores=CODON):
     return RifrafSequence(random_seq(n, rng), np.full(n, -1.0), bw, scores)
 
 
+def varying_reference(n, bw, rng, scores, seq=None):
+    """A reference whose tables differ at every position: error_log_p =
+    log10(U(0.01, 0.3)) (random bases unless seq is given)."""
+    seq = random_seq(n, rng) if seq is None else seq
+    assert len(seq) == n
+    return RifrafSequence(seq, np.log10(rng.uniform(0.01, 0.3, n)), bw, scores)
+
+
 class Case:
     """One group: a template, 1-3 ordinary reads and a reference."""
 
     def __init__(self, t, reads, ref):
         self.t, self.reads, self.ref = t, reads, ref
         self.props = all_proposals_arrays(t)
+        self._oracle = None
 
     def oracle_table(self):
-        t, rs = self.t, self.reads
-        tot = oracle.score_list(self.props, [oracle.forward(t, r)[0] for r in rs],
-                                [oracle.backward(t, r) for r in rs], rs, t,
-                                oracle.forward(t, self.ref)[0], oracle.backward(t, self.ref), self.ref, nthreads=1)
-        return table(t, self.props, tot)
+        """Computed once: the cases that several tests share keep it."""
+        if self._oracle is None:
+            t, rs = self.t, self.reads
+            tot = oracle.score_list(self.props, [oracle.forward(t, r)[0] for r in rs],
+                                    [oracle.backward(t, r) for r in rs], rs, t,
+                                    oracle.forward(t, self.ref)[0], oracle.backward(t, self.ref), self.ref,
+                                    nthreads=1)
+            self._oracle = table(t, self.props, tot)
+        return self._oracle
 
 
 def make_case(m, n, bw, rng, nreads, scores=CODON):
     t = random_seq(m, rng)
     reads = [make_read(t, rng, bandwidth=3) for _ in range(nreads)]
     return Case(t, reads, reference(n, bw, rng, scores))
+
+
+def make_varying_case(m, n, bw, rng, nreads, scores=CODON, read_bw=3):
+    t = random_seq(m, rng)
+    reads = [make_read(t, rng, bandwidth=read_bw) for _ in range(nreads)]
+    return Case(t, reads, varying_reference(n, bw, rng, scores))
 
 
 def load(engine, cases):
@@ -94,18 +123,28 @@ def load(engine, cases):
     return ids
 
 
-def check_cases(engine, cases, label):
+def check_cases(engine, cases, label, noref=()):
+    """One rf_score_dense_ref call of all cases against the list path and the
+    oracle.  The cases whose index is in noref are called with ref_slot -1
+    (their reference is uploaded and unused): every slot of theirs has
+    rf_score_dense's bits.  Returns load()'s slots."""
     ids = load(engine, cases)
-    got = engine.score_dense_ref([b for b, _ in ids], [r for _, r in ids])
+    groups = [b for b, _ in ids]
+    got = engine.score_dense_ref(groups, [-1 if c in noref else r for c, (_, r) in enumerate(ids)])
     lists = engine.score([(b, r, cs.props) for (b, r), cs in zip(ids, cases)])
+    plain = engine.score_dense(groups) if noref else None
     for c, cs in enumerate(cases):
         mask = dense_mask(cs.t)
         key = (label, c, len(cs.t), len(cs.ref), cs.ref.bandwidth)
+        if c in noref:
+            assert same(got[c], plain[c]).all(), ("no reference",) + key
+            continue
         assert np.isnan(got[c][0, :5]).all(), key
         exp = table(cs.t, cs.props, lists[c])
         assert same(got[c][mask], exp[mask]).all(), ("list path",) + key
         assert same(got[c][mask], cs.oracle_table()[mask]).all(), ("oracle",) + key
         assert np.isfinite(got[c][mask]).all(), key
+    return ids
 
 
 def test_edges(engine):
@@ -297,3 +336,115 @@ def test_device_memory():
         assert same(got[mask], table(cs.t, cs.props, lists)[mask]).all()
     finally:
         e.close()
+
+
+# ---------------------------------------------------------------------
+# References whose tables differ at every position
+# ---------------------------------------------------------------------
+
+@pytest.mark.parametrize("scores", [CODON, REF_SCORES], ids=["CODON", "REF_SCORES"])
+def test_varying_tables_edges(engine, scores):
+    """The edge grid of test_edges with match, mismatch, insertion, deletion
+    and codon tables that differ at every position, under the scores
+    correct_shifts builds and the reference's default ones."""
+    rng = np.random.default_rng(2711)
+    cases = [make_varying_case(m, m + dn, bw, rng, 1 + k % 3, scores) for k, (m, dn, bw) in enumerate(EDGES)]
+    assert len(cases) == 80
+    check_cases(engine, cases, "varying edges")
+
+
+def test_workgroup_edges(engine):
+    """m = 62, 63, 64, 127, 128 (n = m + 2, bandwidth 5) in one call: 9 (m + 1)
+    is 576 = 9 * 64 at m = 63 and 1152 = 18 * 64 at m = 127, so those groups'
+    last workgroups have no idle lane and the next group starts on the very
+    next workgroup; m one below and above leave 55 idle lanes and 9 used ones.
+    Three groups with ref_slot -1 stand at the front, in the middle and at the
+    end: they take no workgroup and no descriptor, and have rf_score_dense's
+    bits."""
+    rng = np.random.default_rng(2712)
+    ms = [63, 62, 63, 30, 64, 127, 128, 128]
+    noref = (0, 3, 7)
+    assert 9 * (63 + 1) == 9 * 64 and 9 * (127 + 1) == 18 * 64
+    cases = [make_varying_case(m, m + 2, 5, rng, 1 + k % 2) for k, m in enumerate(ms)]
+    check_cases(engine, cases, "workgroup edges", noref)
+
+
+def test_tall_and_skewed_bands_varying(engine):
+    """Bands taller than one and two waves, and n far from m at a narrow band
+    (|n - m| = 40 and 60 against bandwidths 9 and 30: the row ranges are
+    clipped at both ends), with varying tables."""
+    rng = np.random.default_rng(2713)
+    shapes = [(150, 150, 40), (150, 150, 70), (120, 160, 9), (160, 120, 9), (200, 260, 30)]
+    cases = [make_varying_case(m, n, bw, rng, 1) for m, n, bw in shapes]
+    ids = check_cases(engine, cases, "tall and skewed")
+    assert [engine.geometry(r)[3] for _, r in ids] == [81, 141, 59, 59, 121]
+
+
+def test_frameshifted_reference(engine):
+    """A template of 300 bases that is the reference with two single-base
+    indels and a three-base insertion and deletion -- the consensus
+    correct_shifts meets -- under varying tables.  By the oracle's backtrace
+    alone the reference's alignment takes a codon insertion (move 4) and a
+    codon deletion (move 5)."""
+    rng = np.random.default_rng(2714)
+    m = 300
+    t = random_seq(m, rng)
+    s = t
+    for at, cut, add in ((240, 3, 0), (180, 0, 3), (120, 1, 0), (60, 0, 1)):   # back to front
+        s = np.concatenate([s[:at], random_seq(add, rng), s[at + cut:]]).astype(np.uint8)
+    ref = varying_reference(len(s), 9, rng, CODON, seq=s)
+    _, moves = oracle.forward(t, ref, moves=True)
+    walk = oracle.backtrace(moves, len(s) + 1, m + 1, ref.bandwidth)
+    assert (walk == 4).any() and (walk == 5).any()
+    cs = Case(t, [make_read(t, rng, bandwidth=9) for _ in range(2)], ref)
+    check_cases(engine, [cs], "frameshifted")
+
+
+@functools.lru_cache(maxsize=None)
+def crossing_cases():
+    """m = 260, three reads and a varying codon reference, all at bandwidth 9
+    and all at bandwidth 25: shared by the legs of test_scorer_crossing."""
+    rng = np.random.default_rng(2715)
+    return [make_varying_case(260, n, bw, rng, 3, read_bw=bw) for n, bw in ((257, 9), (266, 25))]
+
+
+@pytest.mark.parametrize("kern", ["general", "ws", "seg"])
+@pytest.mark.parametrize("mode", ["fused", "split"])
+def test_scorer_crossing(engine, opts, mode, kern):
+    """The in-place add after each of the reads' scorers (k_score,
+    k_score_ws, k_score_segl) and folds (fused; split, where k_reduce writes
+    the totals last): one group of three reads per call."""
+    opts("score_mode", mode)
+    opts("score_kernel", kern)
+    for cs in crossing_cases():
+        check_cases(engine, [cs], f"crossing {mode} {kern}")
+
+
+def test_reference_follows_the_call(engine):
+    """One batch and two reference slots (other sequences, bandwidths 3 and
+    9) against the same template: calls with r1, r2, no reference and r1
+    again.  The batch slot list is the same in every call, so the dense plan
+    of the preceding rf_score_dense is reused throughout; each result is its
+    own oracle table."""
+    rng = np.random.default_rng(2716)
+    t = random_seq(50, rng)
+    reads = [make_read(t, rng, bandwidth=3) for _ in range(2)]
+    refs = [varying_reference(48, 3, rng, CODON), varying_reference(53, 9, rng, REF_SCORES)]
+    engine.release_bands()
+    seqs = reads + refs
+    engine.set_sequences(0, seqs)
+    engine.set_templates(0, [t])
+    k = np.arange(len(seqs))
+    engine.realign(k, k, 0, [s.bandwidth for s in seqs], RF_FWD | RF_BWD)
+    b, (r1, r2) = k[:2], k[2:]
+    engine.score_dense([b], to_host=False)
+    got = [engine.score_dense_ref([b], [r])[0] for r in (r1, r2, -1, r1)]
+    mask = dense_mask(t)
+    exp1, exp2 = (Case(t, reads, ref).oracle_table() for ref in refs)
+    assert same(got[0][mask], exp1[mask]).all()
+    assert same(got[1][mask], exp2[mask]).all()
+    assert same(got[2][mask], oracle.cpu_pass(t, reads, nthreads=1)[0][mask]).all()
+    assert same(got[3], got[0]).all()
+    assert not same(got[0][mask], got[1][mask]).any() and not same(got[0][mask], got[2][mask]).any()
+    for g in (got[0], got[1]):
+        assert np.isnan(g[0, :5]).all()

@@ -3,10 +3,17 @@ and bw in {1, 2, 3, 5} -- 576 alignments per input class, one slot and one
 template each, uploaded once and realigned in one call -- against the CPU
 oracle, bit for bit: bands, A[end, end], skew / trim fills, backtraces, error
 counts, proposal marking, read scoring (dense, proposal lists, 48-read ragged
-groups) and reference (codon) scoring of every STAGE_SCORE proposal.  Nothing
+groups), reference (codon) scoring of every STAGE_SCORE proposal (k_codon) and
+the dense table with the reference's score added in every slot
+(rf_score_dense_ref, k_codon_dense: 576 groups in one call, then with every
+third group's reference taken out; the codon classes as the reference under
+the fused and the split fold and both row strides, the non-codon classes as
+a reference without codon tables).  Nothing
 is sampled and nothing is masked beyond the dense table's non-proposal slots
 (p = 0 sub / del and the consensus base's own slot).  The oracle raises on no
-alignment and no proposal of any class; an OracleError fails the test.
+alignment and no proposal of any class; an OracleError fails the test (in
+the non-codon reference sweep it would be a NaN that the engine has to meet;
+there is none).
 
 Input classes (fixed seeds): `seq` / `ref` (SEQ_SCORES / REF_SCORES, random
 bases, error_log_p = log10(U(0.01, 0.3))), `seq0` / `ref0` (the same with
@@ -189,6 +196,31 @@ class _Class:
             return out
         return self.memo("mixed", run)
 
+    def plain_ref_totals(self):
+        """mixed_totals for a non-codon class: the two companions, then the
+        class's sequence as a reference without codon tables (score_nocodon /
+        seq_score_deletion).  Where score_list raises, the alignment is
+        evaluated proposal by proposal and a proposal the oracle raises on is
+        NaN."""
+        def run():
+            A, B, comp = self.fills(), self.backward(), self.companions()
+            out = []
+            for k in range(NA):
+                t, rs, ref = self.templates[k], comp[2 * k:2 * k + 2], self.seqs[k]
+                As, Bs = [oracle.forward(t, r)[0] for r in rs], [oracle.backward(t, r) for r in rs]
+                try:
+                    tot = oracle.score_list(self.props[k], As, Bs, rs, t, A[k][0], B[k], ref, nthreads=1)
+                except oracle.OracleError:
+                    tot = np.empty(len(self.props[k][0]))
+                    for j, prop in enumerate(zip(*self.props[k])):
+                        try:
+                            tot[j] = oracle.score_total(prop, As, Bs, rs, t, A[k][0], B[k], ref)
+                        except oracle.OracleError:
+                            tot[j] = np.nan
+                out.append(tot)
+            return out
+        return self.memo("plainref", run)
+
 
 _CLASSES = {}
 
@@ -252,6 +284,19 @@ def upload(engine, c, flags, tpl=None, per_direction=False):
     scores = engine.realign(ids, ids, tpl, c.bws, flags & ~RF_BWD)
     engine.realign(ids, ids, tpl, c.bws, RF_BWD)
     return scores
+
+
+def upload_with_companions(engine, c):
+    """Upload a class's sequences (slots 0 .. NA - 1) and its two companions
+    per alignment (slots NA + 2 k, NA + 2 k + 1) and fill every band in one
+    rf_realign.  Returns the batch slots of each alignment's group."""
+    engine.set_sequences(0, c.seqs + c.companions())
+    engine.set_templates(0, c.templates)
+    ids = np.arange(3 * NA)
+    tpl = np.concatenate([np.arange(NA), np.repeat(np.arange(NA), 2)])
+    bws = np.concatenate([c.bws, np.repeat(c.bws, 2)])
+    engine.realign(ids, ids, tpl, bws, RF_FWD | RF_BWD)
+    return [np.array([NA + 2 * k, NA + 2 * k + 1]) for k in range(NA)]
 
 
 def check_A(engine, c, scores, fills):
@@ -441,14 +486,8 @@ def test_sweep_reads_plus_reference(engine, opts, name, mode):
     oracle.score_total (reads folded first, the reference last)."""
     c = cls_of(name)
     opts("score_mode", mode)
-    comp = c.companions()
-    engine.set_sequences(0, c.seqs + comp)
-    engine.set_templates(0, c.templates)
-    ids = np.arange(3 * NA)
-    tpl = np.concatenate([np.arange(NA), np.repeat(np.arange(NA), 2)])
-    bws = np.concatenate([c.bws, np.repeat(c.bws, 2)])
-    engine.realign(ids, ids, tpl, bws, RF_FWD | RF_BWD)
-    tot = engine.score([([NA + 2 * k, NA + 2 * k + 1], k, c.props[k]) for k in range(NA)])
+    batches = upload_with_companions(engine, c)
+    tot = engine.score([(batches[k], k, c.props[k]) for k in range(NA)])
     for k, e in enumerate(c.mixed_totals()):
         bad = ~same(tot[k], e)
         if bad.any():
@@ -456,6 +495,87 @@ def test_sweep_reads_plus_reference(engine, opts, name, mode):
             kd, p, b = (int(x[j]) for x in c.props[k])
             raise AssertionError(f"{name} {SHAPES[k]} proposal (kind {kd}, pos {p}, base {b}): "
                                  f"{tot[k][j]!r} != {e[j]!r}")
+
+
+def dense_table(c, k, totals):
+    """The totals of alignment k's proposal list in the dense layout (NaN in
+    the slots that are no proposal)."""
+    kd, p, b = c.props[k]
+    out = np.full((len(c.templates[k]) + 1, 9), np.nan)
+    out[p, dense_slot(kd, b)] = totals
+    return out
+
+
+def check_dense_reference(engine, c, batches, exp):
+    """rf_score_dense_ref of all 576 groups in one call (reference slot k for
+    group k) against the expected proposal totals under dense_mask; then the
+    same call with ref_slot -1 for every k % 3 == 1, so that the kernel's
+    descriptor list is a strict subset of the groups with gaps in it: those
+    groups have rf_score_dense's bits in every slot, the others the first
+    call's."""
+    first = engine.score_dense_ref(batches, np.arange(NA))
+    masks = [dense_mask(t) for t in c.templates]
+    for k in range(NA):
+        assert np.isnan(first[k][0, :5]).all(), (c.name, "p = 0 sub / del", SHAPES[k])
+        bad = ~same(first[k], dense_table(c, k, exp[k])) & masks[k]
+        if bad.any():
+            p, slot = (int(x) for x in np.argwhere(bad)[0])
+            raise AssertionError(f"{c.name} {SHAPES[k]} pos {p} slot {slot}: "
+                                 f"{first[k][p, slot]!r} != {dense_table(c, k, exp[k])[p, slot]!r}")
+    refs = np.arange(NA)
+    refs[1::3] = -1
+    second = engine.score_dense_ref(batches, refs)
+    plain = engine.score_dense(batches)
+    for k in range(NA):
+        if k % 3 == 1:
+            assert same(second[k], plain[k]).all(), (c.name, "no reference: rf_score_dense", SHAPES[k])
+        else:
+            assert np.isnan(second[k][0, :5]).all(), (c.name, "p = 0 sub / del, second call", SHAPES[k])
+            assert same(second[k][masks[k]], first[k][masks[k]]).all(), (c.name, "second call", SHAPES[k])
+
+
+@pytest.mark.parametrize("pad", [64, 1])
+@pytest.mark.parametrize("mode", ["fused", "split"])
+@pytest.mark.parametrize("name", CODON)
+def test_sweep_dense_reference(engine, opts, name, mode, pad):
+    """k_codon_dense on every slot of all 576 alignments: groups of two
+    non-codon reads with the class's codon sequence as the reference slot, in
+    one rf_score_dense_ref call, against oracle.score_total (mixed_totals)
+    laid out as the dense table; the reads' fold fused and split (k_reduce
+    writes the totals the kernel then adds to), default and all-padded row
+    strides.  The tables of `ref` and `ref0` differ at every position, so a
+    table read one position off is a different number.  Then the call with
+    every third group's reference taken out (check_dense_reference)."""
+    c = cls_of(name)
+    opts("score_mode", mode)
+    opts("band_pad", pad)
+    batches = upload_with_companions(engine, c)
+    check_dense_reference(engine, c, batches, c.mixed_totals())
+
+
+@pytest.mark.parametrize("name", NONCODON)
+def test_sweep_dense_plain_reference(engine, name):
+    """The `ncins == 0 && ncdel == 0` branch of k_codon_dense (score_nocodon
+    and seq_score_deletion) on every slot of all 576 alignments: the class's
+    sequence, which has no codon tables, as the reference slot beside the two
+    companions, against oracle.score_list over the three
+    (plain_ref_totals; a proposal the oracle raises on is NaN and must meet
+    NaN).  From the oracle alone, asserted before the engine runs: every
+    compared slot of `seq` and `tie_seq` is finite, and every alignment of
+    every class has a finite compared slot.  No shape of `seq0` is exempt:
+    its -Inf match scores leave the mismatch, insertion and deletion moves,
+    and the oracle gives all 32,256 slots of each of the three classes a
+    finite total and raises on none."""
+    c = cls_of(name)
+    exp = c.plain_ref_totals()
+    finite = [np.isfinite(e) for e in exp]     # a proposal list holds exactly the compared slots
+    print(f"{name}: {sum(int(f.sum()) for f in finite)} finite and "
+          f"{sum(int(np.isnan(e).sum()) for e in exp)} NaN compared slots of {sum(len(e) for e in exp)}")
+    if name in LEAN:
+        assert all(f.all() for f in finite), name
+    assert all(f.any() for f in finite), name
+    batches = upload_with_companions(engine, c)
+    check_dense_reference(engine, c, batches, exp)
 
 
 def test_qv_probs_extended_precision(engine):
