@@ -18,6 +18,9 @@
  *                        correct_shifts)  src/align.jl:114-153,229-260
  *   rf_pair_align_smart <- smart_forward_moves! (band doubling) over many
  *                        pairs  src/model.jl:643-672
+ *   rf_pair_align_text <- align / moves_to_aligned_seqs, moves_to_indices and
+ *                        band_tolerance over many pairs
+ *                        src/align.jl:262-311,322-335,346-353
  *   rf_backtrace      <- backtrace + count_errors   src/align.jl:229-245
  *   rf_alignment_proposals <- alignment_proposals / moves_to_proposals
  *                        src/model.jl:458-497
@@ -339,6 +342,48 @@ int rf_pair_align_smart(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const i
                         int32_t max_doublings, int32_t flags, double *out_score, int8_t *moves,
                         const int64_t *moves_off, int32_t *nmoves, int32_t *nerrors,
                         int32_t *out_bw, int32_t *out_rounds);
+
+/* rf_pair_align_smart that hands back what callers make of the moves instead
+ * of the moves, computed on the device from the walk's output (k_pa_emit):
+ *   aln_t, aln_s  align(t, s) (align.jl:346-353), i.e. moves_to_aligned_seqs
+ *                 (align.jl:286-311): ASCII 'A' 'C' 'G' 'T' '-' at
+ *                 aln_t / aln_s[aln_off[k] ...] (capacity n + m each, no
+ *                 terminator), aln_len[k] bytes each.  A codon insertion is
+ *                 "---" over s[i-2..i], a codon deletion t[j-2..j] over "---".
+ *   t2s           moves_to_indices (align.jl:322-335) at t2s[t2s_off[k] ...]
+ *                 (capacity m), t2s_len[k] entries: for every move that
+ *                 advances j, the 1-based i reached (0 before the first
+ *                 sequence base).  A codon deletion advances j by 3 and adds
+ *                 one entry, as in the reference, so t2s_len < m then.
+ *   tolerance     band_tolerance (align.jl:262-284) of the band
+ *                 (n + 1, m + 1, out_bw[k]): the least |i - start| over the
+ *                 path's cells with start > 1 and |i - stop| over those with
+ *                 stop < n + 1, (start, stop) = row_range(band, j)
+ *                 (bandedarrays.jl:133-137); n + 1 if no cell qualifies.
+ * All describe the pair's last fill, like out_score, nerrors, out_bw and
+ * out_rounds, which are rf_pair_align_smart's.  Every output pointer may be
+ * NULL; aln_t and aln_s are NULL together and need aln_off, t2s needs
+ * t2s_off (else RF_ERR_ARG).  If aln_t, aln_len, t2s, t2s_len and tolerance
+ * are all NULL the kernel is not launched and the call is
+ * rf_pair_align_smart without moves.  Checks, messages, flags (RF_FWD
+ * implied, RF_BWD is RF_ERR_ARG), the 5,114-row limit at max_bw and the
+ * return value are rf_pair_align_smart's, with one addition: with
+ * max_doublings == 0 the call is rf_pair_align at bw and threshold may be
+ * NULL.  A pair the reference raises on, or whose walk fails, gets
+ * aln_len = t2s_len = tolerance = -1 and none of its bytes or entries are
+ * written; the call still returns 0.  The moves are not downloaded.  The call
+ * touches no slot, no band and not the band arena; its device memory is
+ * bounded by RF_OPT_PAIR_CHUNK / RF_OPT_PAIR_TRACE_MB (per launch set: the
+ * trace, n + m bytes of moves and of each text, and 4 m bytes of map). */
+int rf_pair_align_text(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl,
+                       const int32_t *bw, const double *threshold, const uint8_t *fixed,
+                       int32_t max_doublings, int32_t flags, double *out_score,
+                       uint8_t *aln_t, uint8_t *aln_s, const int64_t *aln_off, int32_t *aln_len,
+                       int32_t *t2s, const int64_t *t2s_off, int32_t *t2s_len,
+                       int32_t *tolerance, int32_t *nerrors, int32_t *out_bw, int32_t *out_rounds);
+/* Summed k_pa_emit time of the last rf_pair_align_text call, milliseconds
+ * (0 if it launched none); rf_last_pair_align_ms reports its fills and walks. */
+int rf_last_pair_text_ms(const rf_ctx *ctx, double *emit_ms);
 
 /* Backtrace of the A band of each slot (align.jl:229-238), moves in
  * alignment order written at moves[moves_off[k] ...] (capacity n+m each);

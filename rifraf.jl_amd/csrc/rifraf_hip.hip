@@ -17,6 +17,8 @@
 //   k_pa / k_pa_gen / k_pa_walk / k_pa_walk_w  alignments of independent pairs
 //               (rf_pair_align): k_ps / k_ps_gen writing a 4-bit move per
 //               cell, and a walk over the moves  src/align.jl:114-153,229-245
+//   k_pa_emit   gapped texts, index maps and band tolerances from those moves
+//               (rf_pair_align_text)  src/align.jl:262-311,322-335
 //   k_score_ws / k_score_segl / k_score
 //               dense per-position proposal scoring of every batch read,
 //               left-folded over the batch in batch order
@@ -1978,6 +1980,112 @@ k_pa_walk_w(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restr
     if (lane == 0) {
         nmoves[oi] = ok ? cnt : -1;
         nerr[oi] = ok ? errs + lerr : -1;
+    }
+}
+
+// k_pa_emit (rf_pair_align_text): what a caller makes of a pair's moves, on
+// the moves the walk left in device memory.  One wave per pair; the lanes take
+// 64 consecutive moves, in alignment order.  A lane's move gives (di, dj)
+// (offset_forward, align.jl:20-23), its width in the text (3 for the codon
+// moves, else 1) and whether it advances j; the four go through one inclusive
+// wave scan packed in bytes (a chunk sums to at most 3 * 64 per field), on
+// top of the running totals of the chunks before.  With i, j after its move a
+// lane writes
+//   - its 1 or 3 bytes of both gapped texts, "ACGT-" (moves_to_aligned_seqs,
+//     align.jl:286-311), from the start of the pair's n + m slot;
+//   - i into the template -> sequence map if dj > 0: j only grows, so that is
+//     the reference's j > last_j, and a codon deletion pushes once
+//     (moves_to_indices, align.jl:322-335);
+//   - nothing for band_tolerance (align.jl:262-284), but keeps the minimum
+//     distance of its cell (i + 1, j + 1) to the band's row_range where that
+//     range is cut by the band and not by the matrix; lane 0 starts from cell
+//     (1, 1), the value starts at nrows, and the lanes' minima meet once after
+//     the loop.
+// Any of the three products may be off (NULL).  lens: aln_len, t2s_len and
+// tolerance, ntasks of each; a pair the walk gave up (-1) gets -1 in all three
+// and no bytes.
+// types.dna_str's letter of a base code: the arenas hold what the caller
+// uploaded, 0..3 by the ABI's convention; 4 is the host's gap letter
+__device__ __forceinline__ uint8_t pa_char(uint8_t b) { return b < 4 ? (uint8_t)"ACGT"[b] : (uint8_t)'-'; }
+
+__global__ void __launch_bounds__(64 * PAW_NW)
+k_pa_emit(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+          const int8_t *__restrict__ moves, const int64_t *__restrict__ moves_off,
+          const int32_t *__restrict__ nmoves, uint8_t *__restrict__ aln_t, uint8_t *__restrict__ aln_s,
+          int32_t *__restrict__ t2s, const int64_t *__restrict__ t2s_off, int32_t *__restrict__ lens)
+{
+    const int lane = threadIdx.x & 63;
+    const int t = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * PAW_NW + (threadIdx.x >> 6)));
+    if (t >= ntasks)
+        return;
+    const DPTask &T = tasks[t];
+    const int n = T.n, m = T.m, bw = T.bw, oi = T.out_idx;
+    const int cnt = nmoves[oi];
+    if (cnt < 0) {
+        if (lane < 3)
+            lens[(size_t)lane * ntasks + oi] = -1;
+        return;
+    }
+    const uint8_t *s = bases + T.sb;
+    const uint8_t *tt = bases + T.tb;
+    const int64_t slot = moves_off[oi];
+    const int8_t *mvs = moves + slot + (n + m - cnt);   // end-aligned by the walk
+    uint8_t *at = aln_t ? aln_t + slot : nullptr;
+    uint8_t *as = aln_t ? aln_s + slot : nullptr;
+    int32_t *ix = t2s ? t2s + t2s_off[oi] : nullptr;
+    const int nrows = n + 1, hoff = max(m - n, 0), voff = max(n - m, 0);
+    // |i - start| where start > 1, |i - stop| where stop < nrows, else nrows (row_range, bandedarrays.jl:133-137)
+    auto edge = [&](int i, int j) {
+        const int start = max(1, j - hoff - bw), stop = min(j + voff + bw, nrows);
+        const int a = start > 1 ? abs(i - start) : nrows, b = stop < nrows ? abs(i - stop) : nrows;
+        return min(a, b);
+    };
+    int tol = lane == 0 ? edge(1, 1) : nrows;
+    int bi = 0, bj = 0, bo = 0, bk = 0;   // i, j, text bytes and map entries of the chunks before
+    for (int x0 = 0; x0 < cnt; x0 += 64) {
+        const bool on = x0 + lane < cnt;
+        const int mv = on ? mvs[x0 + lane] : 0;
+        const int di = (mv == 1 || mv == 2) ? 1 : (mv == 4 ? 3 : 0);
+        const int dj = (mv == 1 || mv == 3) ? 1 : (mv == 5 ? 3 : 0);
+        const int w = mv >= 4 ? 3 : (mv >= 1 ? 1 : 0);
+        int sc = di | (dj << 8) | (w << 16) | ((dj > 0 ? 1 : 0) << 24);
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(sc, d, 64);
+            sc += lane >= d ? up : 0;
+        }
+        const int i = bi + (sc & 255), j = bj + ((sc >> 8) & 255);
+        const int o = bo + ((sc >> 16) & 255) - w, k = bk + ((sc >> 24) & 255);
+        if (on) {
+            if (at) {
+                if (mv <= 3) {
+                    at[o] = mv == 2 ? '-' : pa_char(tt[j - 1]);
+                    as[o] = mv == 3 ? '-' : pa_char(s[i - 1]);
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 3; ++u) {
+                        at[o + u] = mv == 4 ? '-' : pa_char(tt[j - 3 + u]);
+                        as[o + u] = mv == 5 ? '-' : pa_char(s[i - 3 + u]);
+                    }
+                }
+            }
+            if (ix && dj > 0)
+                ix[k - 1] = i;
+            tol = min(tol, edge(i + 1, j + 1));
+        }
+        const int tot = __builtin_amdgcn_readlane(sc, 63);
+        bi += tot & 255;
+        bj += (tot >> 8) & 255;
+        bo += (tot >> 16) & 255;
+        bk += (tot >> 24) & 255;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+        tol = min(tol, __shfl_xor(tol, d, 64));
+    if (lane == 0) {
+        lens[oi] = bo;
+        lens[(size_t)ntasks + oi] = bk;
+        lens[2 * (size_t)ntasks + oi] = tol;
     }
 }
 
@@ -5653,9 +5761,10 @@ struct rf_ctx {
     // a plan validated at the current epoch with the same job / slot list
     // needs no per-slot validation again
     uint64_t state_epoch = 1;
-    DevBuf scratch[35];   // 28, 29: rf_pair_scores' / rf_pair_align's descriptors and scores;
+    DevBuf scratch[40];   // 28, 29: rf_pair_scores' / rf_pair_align's descriptors and scores;
                           // 30-33: rf_pair_align's trace, moves, move offsets and counts;
-                          // 34: rf_score_dense_ref's group descriptors
+                          // 34: rf_score_dense_ref's group descriptors;
+                          // 35-39: rf_pair_align_text's two texts, index maps, map offsets and lengths
     // pinned host staging for sequence uploads (pageable H2D copies of a few
     // MB took ~14 ms per cluster upload on the box: page locking per call)
     void *pinned = nullptr;
@@ -5679,6 +5788,7 @@ struct rf_ctx {
     double codon_dense_ms = 0;  // k_codon_dense of the last rf_score_dense_ref (inside score_ms)
     double pair_ms = 0;         // kernels of the last rf_pair_scores
     double pa_fill_ms = 0, pa_walk_ms = 0;   // fills / walks of the last rf_pair_align
+    double pa_emit_ms = 0;                   // k_pa_emit of the last rf_pair_align_text
     hipEvent_t ev_codon = nullptr;
     hipEvent_t ev_block = nullptr;   // blocking-sync event (RF_OPT_SYNC_BLOCK)
     Opts opt;
@@ -7501,7 +7611,7 @@ static int pair_check(rf_ctx *ctx, const std::string &fn, bool align, bool args_
         return fail(ctx, RF_ERR_ARG, fn + ": unknown flags");
     (void)hipSetDevice(ctx->device);
     if (align)
-        ctx->pa_fill_ms = ctx->pa_walk_ms = 0;
+        ctx->pa_fill_ms = ctx->pa_walk_ms = ctx->pa_emit_ms = 0;
     else
         ctx->pair_ms = 0;
     for (int64_t k = 0; k < npairs; ++k) {
@@ -7700,11 +7810,23 @@ static bool pair_walk_wave(const rf_ctx *ctx, int64_t cn, int64_t mv_total)
 // device memory a call needs.  seq, tpl, bw and every output are indexed by
 // the pair's own k.  `walk`: run the walk (counts, and moves with `moves`).
 // `ended` (may be empty) sees a pair's score and counts and says whether its
-// moves go to the caller; without it every pair's do.
+// moves go to the caller; without it every pair's do.  `tx` (may be NULL):
+// k_pa_emit runs after the walk of each set, over the moves in scratch[31],
+// and its products (scratch[35-39]) go to the caller under the same `ended`
+// rule; the moves themselves are downloaded only if `moves` asks for them.
+struct PairText {   // rf_pair_align_text's outputs, each NULL or indexed by the pair's own k
+    uint8_t *aln_t, *aln_s;
+    const int64_t *aln_off;
+    int32_t *aln_len, *t2s;
+    const int64_t *t2s_off;
+    int32_t *t2s_len, *tolerance;
+    bool any() const { return aln_t || aln_len || t2s || t2s_len || tolerance; }
+};
 static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const int32_t *seq, const int32_t *tpl,
                           const int32_t *bw, int fl, bool walk, double *out_score, int8_t *moves,
                           const int64_t *moves_off, int32_t *nmoves, int32_t *nerrors,
-                          const std::function<bool(int64_t, double, int32_t, int32_t)> &ended)
+                          const std::function<bool(int64_t, double, int32_t, int32_t)> &ended,
+                          const PairText *tx = nullptr)
 {
     const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
     const int64_t budget = (int64_t)std::max(ctx->opt.pair_trace_mb, 1) << 20;   // bytes of trace per set
@@ -7717,7 +7839,9 @@ static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const i
         return (int64_t)pa_blocks(H + 2 * T.m) * pa_hp(H);
     };
     PairPlan pl;
-    std::vector<int64_t> mvoff;
+    std::vector<int64_t> mvoff, ixoff;
+    const bool emit = walk && tx && tx->any();
+    const bool want_txt = emit && tx->aln_t, want_ix = emit && tx->t2s;
     for (int64_t p0 = 0; p0 < nidx;) {
         // the set [p0, p0 + cn): at least one pair, then while both bounds hold
         int64_t cn = 0, words = 0;
@@ -7730,7 +7854,8 @@ static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const i
         }
         pl.clear();
         mvoff.assign((size_t)cn, 0);
-        int64_t tr_at = 0, mv_total = 0;
+        ixoff.assign((size_t)cn, 0);
+        int64_t tr_at = 0, mv_total = 0, ix_total = 0;
         for (int64_t i = p0; i < p0 + cn; ++i) {
             const int64_t k = at(i);
             const SeqObj &S = ctx->seqs[seq[k]];
@@ -7742,13 +7867,22 @@ static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const i
             tr_at += (int64_t)t.pad * t.P;
             mvoff[(size_t)(i - p0)] = mv_total;
             mv_total += S.n + T.m;
+            ixoff[(size_t)(i - p0)] = ix_total;
+            ix_total += T.m;
             pl.add(t, S);
         }
         pl.finish();
-        const bool want_mv = moves != nullptr;
-        // downloads: scores, then nmoves and nerrors, then the moves
+        const bool get_mv = moves != nullptr;    // the moves go to the caller
+        const bool want_mv = get_mv || emit;     // the walk writes them
+        // downloads: scores, then nmoves and nerrors, then the moves; with k_pa_emit
+        // its lengths, the two texts and the index maps follow
         const size_t cb = sizeof(double) * (size_t)cn, nbytes = sizeof(int32_t) * 2 * (size_t)cn;
         const size_t mv_at = (cb + nbytes + 15) & ~(size_t)15;
+        const size_t mv_len = (size_t)std::max<int64_t>(mv_total, 16), lb = sizeof(int32_t) * 3 * (size_t)cn;
+        const size_t len_at = (mv_at + (get_mv ? (size_t)mv_total : 0) + 15) & ~(size_t)15;
+        const size_t txt_at = (len_at + (emit ? lb : 0) + 15) & ~(size_t)15;
+        const size_t ix_at = (txt_at + (want_txt ? 2 * (size_t)mv_total : 0) + 15) & ~(size_t)15;
+        const size_t h_end = ix_at + (want_ix ? sizeof(int32_t) * (size_t)ix_total : 0);
         if (int e = upload(ctx, ctx->scratch[28], pl.all))
             return e;
         if (int e = ensure_buf(ctx, ctx->scratch[29], cb))
@@ -7757,7 +7891,7 @@ static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const i
             return e;
         if (walk) {
             if (want_mv) {
-                if (int e = ensure_buf(ctx, ctx->scratch[31], (size_t)std::max<int64_t>(mv_total, 16)))
+                if (int e = ensure_buf(ctx, ctx->scratch[31], mv_len))
                     return e;
                 if (int e = upload(ctx, ctx->scratch[32], mvoff))
                     return e;
@@ -7765,7 +7899,22 @@ static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const i
             if (int e = ensure_buf(ctx, ctx->scratch[33], nbytes))
                 return e;
         }
-        if (int e = ensure_hdn(ctx, mv_at + (want_mv ? (size_t)mv_total : 0)))
+        if (want_txt) {
+            if (int e = ensure_buf(ctx, ctx->scratch[35], mv_len))
+                return e;
+            if (int e = ensure_buf(ctx, ctx->scratch[36], mv_len))
+                return e;
+        }
+        if (want_ix) {
+            if (int e = ensure_buf(ctx, ctx->scratch[37], sizeof(int32_t) * (size_t)std::max<int64_t>(ix_total, 4)))
+                return e;
+            if (int e = upload(ctx, ctx->scratch[38], ixoff))
+                return e;
+        }
+        if (emit)
+            if (int e = ensure_buf(ctx, ctx->scratch[39], lb))
+                return e;
+        if (int e = ensure_hdn(ctx, h_end))
             return e;
         const DPTask *d_tasks = (const DPTask *)ctx->scratch[28].p;
         double *d_out = (double *)ctx->scratch[29].p;
@@ -7789,16 +7938,39 @@ static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const i
             HIPCHK(ctx, hipGetLastError());
         }
         HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+        if (emit) {
+            hipLaunchKernelGGL(k_pa_emit, dim3((unsigned)((cn + PAW_NW - 1) / PAW_NW)), dim3(64 * PAW_NW), 0,
+                               ctx->stream, d_tasks, (int)cn, d_bases, (const int8_t *)ctx->scratch[31].p,
+                               (const int64_t *)ctx->scratch[32].p, (const int32_t *)d_cnt,
+                               want_txt ? (uint8_t *)ctx->scratch[35].p : nullptr,
+                               want_txt ? (uint8_t *)ctx->scratch[36].p : nullptr,
+                               want_ix ? (int32_t *)ctx->scratch[37].p : nullptr,
+                               (const int64_t *)ctx->scratch[38].p, (int32_t *)ctx->scratch[39].p);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+        }
         char *h = (char *)ctx->hdn + HDN_RES;
         HIPCHK(ctx, hipMemcpyAsync(h, d_out, cb, hipMemcpyDeviceToHost, ctx->stream));
         if (walk)
             HIPCHK(ctx, hipMemcpyAsync(h + cb, d_cnt, nbytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (walk && want_mv && mv_total > 0)
+        if (walk && get_mv && mv_total > 0)
             HIPCHK(ctx, hipMemcpyAsync(h + mv_at, ctx->scratch[31].p, (size_t)mv_total, hipMemcpyDeviceToHost,
                                        ctx->stream));
+        if (emit)
+            HIPCHK(ctx, hipMemcpyAsync(h + len_at, ctx->scratch[39].p, lb, hipMemcpyDeviceToHost, ctx->stream));
+        if (want_txt && mv_total > 0) {
+            HIPCHK(ctx, hipMemcpyAsync(h + txt_at, ctx->scratch[35].p, (size_t)mv_total, hipMemcpyDeviceToHost,
+                                       ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(h + txt_at + mv_total, ctx->scratch[36].p, (size_t)mv_total,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (want_ix && ix_total > 0)
+            HIPCHK(ctx, hipMemcpyAsync(h + ix_at, ctx->scratch[37].p, sizeof(int32_t) * (size_t)ix_total,
+                                       hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, stream_wait(ctx));
         const double *sc = (const double *)h;
         const int32_t *cnt = (const int32_t *)(h + cb);
+        const int32_t *len = (const int32_t *)(h + len_at);   // aln_len, t2s_len, tolerance: cn of each
         for (int64_t i = 0; i < cn; ++i) {
             const int64_t k = at(p0 + i);
             if (out_score)
@@ -7811,16 +7983,36 @@ static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const i
                 nerrors[k] = cnt[cn + i];
             if (ended && !ended(k, sc[i], cnt[i], cnt[cn + i]))
                 continue;
-            if (want_mv && cnt[i] > 0) {   // the walk leaves the moves at the end of the pair's n + m slot
-                const int64_t len = (i + 1 < cn ? mvoff[(size_t)i + 1] : mv_total) - mvoff[(size_t)i];
-                std::memcpy(moves + moves_off[k], h + mv_at + mvoff[(size_t)i] + len - cnt[i], (size_t)cnt[i]);
+            if (get_mv && cnt[i] > 0) {   // the walk leaves the moves at the end of the pair's n + m slot
+                const int64_t slot = (i + 1 < cn ? mvoff[(size_t)i + 1] : mv_total) - mvoff[(size_t)i];
+                std::memcpy(moves + moves_off[k], h + mv_at + mvoff[(size_t)i] + slot - cnt[i], (size_t)cnt[i]);
             }
+            if (!emit)
+                continue;
+            const int32_t al = len[i], il = len[cn + i];
+            if (tx->aln_len)
+                tx->aln_len[k] = al;
+            if (tx->t2s_len)
+                tx->t2s_len[k] = il;
+            if (tx->tolerance)
+                tx->tolerance[k] = len[2 * cn + i];
+            if (want_txt && al > 0) {   // k_pa_emit writes the texts from the start of the slot
+                std::memcpy(tx->aln_t + tx->aln_off[k], h + txt_at + mvoff[(size_t)i], (size_t)al);
+                std::memcpy(tx->aln_s + tx->aln_off[k], h + txt_at + mv_total + mvoff[(size_t)i], (size_t)al);
+            }
+            if (want_ix && il > 0)
+                std::memcpy(tx->t2s + tx->t2s_off[k], h + ix_at + sizeof(int32_t) * (size_t)ixoff[(size_t)i],
+                            sizeof(int32_t) * (size_t)il);
         }
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
         ctx->pa_fill_ms += ms;
         (void)hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]);
         ctx->pa_walk_ms += ms;
+        if (emit) {
+            (void)hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]);
+            ctx->pa_emit_ms += ms;
+        }
         p0 += cn;
     }
     return 0;
@@ -7844,16 +8036,18 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
 // smart_forward_moves! (model.jl:643-672) of independent pairs: rounds of
 // pair_align_run over the pairs still pending, each at its current bandwidth;
 // the loop's decisions are taken here from the downloaded counts.
-int rf_pair_align_smart(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
-                        const double *threshold, const uint8_t *fixed, int32_t max_doublings, int32_t flags,
-                        double *out_score, int8_t *moves, const int64_t *moves_off, int32_t *nmoves,
-                        int32_t *nerrors, int32_t *out_bw, int32_t *out_rounds)
+// `fn` names the entry point (rf_pair_align_smart, rf_pair_align_text); `tx`
+// (may be NULL) is rf_pair_align_text's outputs, which also lets threshold be
+// NULL when max_doublings is 0: no pair then gets past its first fill.
+static int pair_smart_run(rf_ctx *ctx, const std::string &fn, bool args_ok, int64_t npairs, const int32_t *seq,
+                          const int32_t *tpl, const int32_t *bw, const double *threshold, const uint8_t *fixed,
+                          int32_t max_doublings, int32_t flags, double *out_score, int8_t *moves,
+                          const int64_t *moves_off, int32_t *nmoves, int32_t *nerrors, int32_t *out_bw,
+                          int32_t *out_rounds, const PairText *tx)
 {
-    const std::string fn = "rf_pair_align_smart";
-    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && (!moves == !moves_off);
     if (int e = pair_check(ctx, fn, true, args_ok, npairs, seq, tpl, bw, flags))
         return e;
-    if (npairs > 0 && !threshold)
+    if (npairs > 0 && !threshold && !(tx && max_doublings == 0))
         return fail(ctx, RF_ERR_ARG, fn + ": threshold is NULL");
     if (max_doublings < 0 || max_doublings > 5)
         return fail(ctx, RF_ERR_ARG, fn + ": max_doublings must be 0..5");
@@ -7872,7 +8066,7 @@ int rf_pair_align_smart(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const i
         maxbw[(size_t)k] = (int32_t)mb;
     }
     const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
-    const bool want = moves || nmoves || nerrors;
+    const bool want = moves || nmoves || nerrors || (tx && tx->any());
     // the loop reads every pair's score and error count, whatever the caller asked for
     std::vector<double> sc_own;
     std::vector<int32_t> ne_own;
@@ -7907,7 +8101,7 @@ int rf_pair_align_smart(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const i
         for (int64_t k : pending)
             walk = walk || !stops_at_fill(k);
         if (int e = pair_align_run(ctx, (int64_t)pending.size(), pending.data(), seq, tpl, cur.data(), fl, walk,
-                                   out_score, moves, moves_off, nmoves, nerrors, ended))
+                                   out_score, moves, moves_off, nmoves, nerrors, ended, tx))
             return e;
         next.clear();
         for (int64_t k : pending) {
@@ -7924,6 +8118,41 @@ int rf_pair_align_smart(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const i
     }
     if (out_bw)
         std::copy(cur.begin(), cur.end(), out_bw);
+    return 0;
+}
+
+int rf_pair_align_smart(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
+                        const double *threshold, const uint8_t *fixed, int32_t max_doublings, int32_t flags,
+                        double *out_score, int8_t *moves, const int64_t *moves_off, int32_t *nmoves,
+                        int32_t *nerrors, int32_t *out_bw, int32_t *out_rounds)
+{
+    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && (!moves == !moves_off);
+    return pair_smart_run(ctx, "rf_pair_align_smart", args_ok, npairs, seq, tpl, bw, threshold, fixed, max_doublings,
+                          flags, out_score, moves, moves_off, nmoves, nerrors, out_bw, out_rounds, nullptr);
+}
+
+// rf_pair_align_smart whose products are k_pa_emit's: align (align.jl:346-353,
+// moves_to_aligned_seqs :286-311), moves_to_indices (:322-335) and
+// band_tolerance (:262-284) of each pair's last fill.  The moves stay on the
+// device.
+int rf_pair_align_text(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
+                       const double *threshold, const uint8_t *fixed, int32_t max_doublings, int32_t flags,
+                       double *out_score, uint8_t *aln_t, uint8_t *aln_s, const int64_t *aln_off, int32_t *aln_len,
+                       int32_t *t2s, const int64_t *t2s_off, int32_t *t2s_len, int32_t *tolerance,
+                       int32_t *nerrors, int32_t *out_bw, int32_t *out_rounds)
+{
+    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && (!aln_t == !aln_s) &&
+                         (!aln_t || aln_off) && (!t2s || t2s_off);
+    const PairText tx{aln_t, aln_s, aln_off, aln_len, t2s, t2s_off, t2s_len, tolerance};
+    return pair_smart_run(ctx, "rf_pair_align_text", args_ok, npairs, seq, tpl, bw, threshold, fixed, max_doublings,
+                          flags, out_score, nullptr, nullptr, nullptr, nerrors, out_bw, out_rounds, &tx);
+}
+
+int rf_last_pair_text_ms(const rf_ctx *ctx, double *emit_ms)
+{
+    if (!ctx || !emit_ms)
+        return RF_ERR_ARG;
+    *emit_ms = ctx->pa_emit_ms;
     return 0;
 }
 

@@ -2,8 +2,9 @@
 
 The DP fills (forward!, forward_moves!, backward!) and backtraces run on the
 HIP engine (rf_realign / rf_backtrace).  The move-list helpers below
-(moves_to_aligned_seqs, moves_to_indices, moves_to_proposals) are host-side
-bookkeeping over the engine's move lists, as in the reference.
+(moves_to_aligned_seqs, moves_to_indices, band_tolerance, moves_to_proposals)
+are host-side bookkeeping over the engine's move lists, as in the reference;
+pairalign.py has the first three for many pairs on the device.
 """
 from __future__ import annotations
 
@@ -150,6 +151,27 @@ def moves_to_indices(moves, tlen, slen):                          # align.jl:322
             result.append(i)
             last_j = j
     return result
+
+
+def band_tolerance(moves, nrows, ncols, bandwidth):               # align.jl:262-284
+    """Distance of an alignment's path to the edge of its band.  The
+    reference walks the band's trace back from (nrows, ncols); the same cells
+    are visited here forwards from (1, 1) over the path's move list, against
+    the row_range of a BandedArray of that shape and bandwidth."""
+    from .bandedarrays import BandedArray
+    band = BandedArray.geometry((nrows, ncols), bandwidth)
+    dist = nrows
+    cells = [(1, 1)]
+    for mv in moves:
+        a, b = OFFSETS[int(mv)]
+        cells.append((cells[-1][0] + a, cells[-1][1] + b))
+    for i, j in cells:
+        start, stop = band.row_range(j)
+        if start > 1:
+            dist = min(dist, abs(i - start))
+        if stop < nrows:
+            dist = min(dist, abs(i - stop))
+    return dist
 
 
 def moves_to_proposals(moves, consensus, seq: RifrafSequence):   # model.jl:458-480

@@ -68,6 +68,19 @@ class BandedArray:
             raise ValueError("data is wrong shape")
         self.data = data
 
+    @classmethod
+    def geometry(cls, shape, bandwidth: int):
+        """A band of this shape and bandwidth without data: inband, data_row
+        and row_range work, element access does not."""
+        if bandwidth < 1:
+            raise ValueError("bandwidth must be positive")
+        self = cls.__new__(cls)
+        self.dtype = self.default = self.data = None
+        self.row_padding = self.col_padding = 0
+        self.bandwidth = int(bandwidth)
+        self._set_shape(shape)
+        return self
+
     def _set_shape(self, shape):
         nrows, ncols = shape
         self.nrows, self.ncols = int(nrows), int(ncols)

@@ -45,6 +45,42 @@ def pack_groups(groups) -> PackedGroups:
     return PackedGroups(slot_off, slots)
 
 
+class PairText:
+    """What Engine.pair_align_text returns beside the scores, over the
+    flattened pairs: the raw byte buffers aln_t / aln_s with their offsets
+    aln_off and lengths aln_len, the index maps t2s with t2s_off / t2s_len,
+    tolerance, nerrors, bandwidths and rounds.  Products that were not asked
+    for are None; a pair the reference raises on has lengths and tolerance
+    -1."""
+    __slots__ = ("n", "aln_t", "aln_s", "aln_off", "aln_len", "t2s", "t2s_off", "t2s_len", "tolerance",
+                 "nerrors", "bandwidths", "rounds")
+
+    def __init__(self, n):
+        self.n = n
+        self.aln_t = self.aln_s = self.aln_off = self.t2s = self.t2s_off = None
+        self.aln_len, self.t2s_len, self.tolerance, self.nerrors, self.bandwidths, self.rounds = (
+            np.empty(max(n, 1), np.int32)[:n] for _ in range(6))
+
+    def text(self, k):
+        """(aligned t, aligned s) of pair k as str; None for an invalid pair."""
+        ln = int(self.aln_len[k])
+        if ln < 0:
+            return None
+        o = int(self.aln_off[k])
+        return self.aln_t[o:o + ln].tobytes().decode("ascii"), self.aln_s[o:o + ln].tobytes().decode("ascii")
+
+    def texts(self):
+        return [self.text(k) for k in range(self.n)]
+
+    def indices(self, k):
+        """moves_to_indices of pair k as an int32 array; None for an invalid pair."""
+        ln = int(self.t2s_len[k])
+        if ln < 0:
+            return None
+        o = int(self.t2s_off[k])
+        return self.t2s[o:o + ln].copy()
+
+
 class Engine:
     """One device context.  Sequence ids, template ids and slot ids are small
     integers chosen by the caller (see model.py for the RIFRAF mapping)."""
@@ -452,6 +488,77 @@ class Engine:
             out = [moves[moves_off[k]:moves_off[k] + nmoves[k]].copy() if nmoves[k] >= 0 else None
                    for k in range(n)]
         return scores[:n], out, nerr[:n].copy(), out_bw[:n].copy(), rounds[:n].copy()
+
+    def pair_align_text(self, seqs, tpls, bws, thresholds=None, fixed=None, max_doublings: int = 0, flags=0,
+                        want_text: bool = True, want_indices: bool = False, want_tolerance: bool = False,
+                        caps=None):
+        """rf_pair_align_text: pair_align_smart whose products are made on
+        the device from the moves, which stay there: the two gapped texts of
+        align (align.jl:346-353), moves_to_indices (:322-335) and
+        band_tolerance (:262-284) of each pair's last fill.  Arguments
+        broadcast as pair_align_smart's; thresholds may be None with
+        max_doublings=0 (pair_align at bws).  caps: (n + m, m) of each pair,
+        the capacities of its texts and its map.  Pass them whenever the
+        lengths are at hand, as pairalign does: without caps and with
+        want_text or want_indices the whole call -- fills, walks and emit --
+        runs twice, first for the lengths alone to size the buffers exactly,
+        so it costs double on the GPU, and last_pair_align_ms /
+        last_pair_text_ms report the second run only.
+        Returns (scores, PairText)."""
+        arrs = [np.asarray(seqs), np.asarray(tpls), np.asarray(bws)]
+        if thresholds is not None:
+            arrs.append(np.asarray(thresholds, np.float64))
+        if fixed is not None:
+            arrs.append(np.asarray(fixed))
+        arrs = np.broadcast_arrays(*arrs)
+        seqs = np.ascontiguousarray(arrs[0].reshape(-1), np.int32)
+        tpls = np.ascontiguousarray(arrs[1].reshape(-1), np.int32)
+        bws = np.ascontiguousarray(arrs[2].reshape(-1), np.int32)
+        thr = np.ascontiguousarray(arrs[3].reshape(-1), np.float64) if thresholds is not None else None
+        fx = np.ascontiguousarray(arrs[-1].reshape(-1) != 0, np.uint8) if fixed is not None else None
+        n = seqs.shape[0]
+        r = PairText(n)
+        scores = np.empty(max(n, 1))
+
+        def call(sc, at, as_, aoff, alen, ix, ioff, ilen, tol, ne, ob, rd):
+            self._check(self.lib.rf_pair_align_text(self.ctx, n, ptr(seqs), ptr(tpls), ptr(bws), ptr(thr), ptr(fx),
+                                                    int(max_doublings), int(flags), ptr(sc), ptr(at), ptr(as_),
+                                                    ptr(aoff), ptr(alen), ptr(ix), ptr(ioff), ptr(ilen), ptr(tol),
+                                                    ptr(ne), ptr(ob), ptr(rd)))
+
+        if want_text or want_indices:
+            if caps is None:
+                # the engine knows the lengths, this object does not: a first
+                # call for the lengths alone sizes the buffers exactly
+                call(None, None, None, None, r.aln_len, None, None, r.t2s_len, None, None, None, None)
+                caps = (np.maximum(r.aln_len[:n], 0), np.maximum(r.t2s_len[:n], 0))
+            for want, cap, name in ((want_text, caps[0], "aln"), (want_indices, caps[1], "t2s")):
+                if want:
+                    off = np.zeros(n + 1, np.int64)
+                    np.cumsum(np.broadcast_to(np.asarray(cap, np.int64).reshape(-1), (n,)), out=off[1:])
+                    setattr(r, name + "_off", off)
+            if want_text:
+                r.aln_t = np.empty(max(int(r.aln_off[-1]), 1), np.uint8)
+                r.aln_s = np.empty(max(int(r.aln_off[-1]), 1), np.uint8)
+            if want_indices:
+                r.t2s = np.empty(max(int(r.t2s_off[-1]), 1), np.int32)
+        call(scores, r.aln_t, r.aln_s, r.aln_off, r.aln_len if want_text else None, r.t2s, r.t2s_off,
+             r.t2s_len if want_indices else None, r.tolerance if want_tolerance else None, r.nerrors, r.bandwidths,
+             r.rounds)
+        if not want_text:
+            r.aln_len = None
+        if not want_indices:
+            r.t2s_len = None
+        if not want_tolerance:
+            r.tolerance = None
+        return scores[:n], r
+
+    def last_pair_text_ms(self) -> float:
+        """k_pa_emit ms of the last pair_align_text call (all its launch sets
+        and rounds); last_pair_align_ms reports its fills and walks."""
+        v = c_double()
+        self._check(self.lib.rf_last_pair_text_ms(self.ctx, byref(v)))
+        return v.value
 
     def last_pair_align_ms(self):
         """(fill ms, walk ms) of the last pair_align / pair_align_smart call

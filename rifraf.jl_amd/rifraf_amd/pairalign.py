@@ -1,4 +1,5 @@
-"""Alignments of many pairs in one engine call (rf_pair_align).
+"""Alignments of many pairs in one engine call (rf_pair_align,
+rf_pair_align_text).
 
 The pairwise half of the reference's API over lists: align_moves / align
 (src/align.jl:337-353), edit_distance (:253-260) and the loop of
@@ -6,6 +7,10 @@ scripts/correct_shifts.jl (:61-68, correct_shifts model.jl:1303-1316).  The
 engine fills each pair with the scores on chip, keeps a 4-bit move per band
 cell and walks it: no FP64 band, no slot.  align.py's one-pair functions and
 model.correct_shifts keep their slot path; the results are the same.
+Where only the gapped texts, the index maps (moves_to_indices, :322-335) or
+the band tolerances (:262-284) are wanted, the engine makes them from the
+moves on the device (Engine.pair_align_text) and the moves are not downloaded;
+an engine without that call gets the moves and align.py's per-move loops.
 """
 from __future__ import annotations
 
@@ -13,7 +18,7 @@ import math
 
 import numpy as np
 
-from .align import moves_to_aligned_seqs
+from .align import band_tolerance, moves_to_aligned_seqs, moves_to_indices
 from .engine import RF_SKEW, RF_TRIM, RifrafError
 from .errormodel import ErrorModel, Scores
 from .poisson import cquantile_poisson_many
@@ -51,11 +56,13 @@ def max_bandwidths(bws, fixed, slen, tlen, max_doublings):
     return np.where(np.asarray(fixed, bool), bws, grown)
 
 
-def _run(e, seqs, templates, si, ti, bws, flags, want_moves, smart=None):
+def _run(e, seqs, templates, si, ti, bws, flags, want_moves, smart=None, text=None):
     """One rf_pair_align call over pairs (si[k], ti[k]); sequences and
     templates are uploaded as ids 0.. of the engine.  smart = (thresholds,
     fixed, max_doublings): one rf_pair_align_smart call, and the band that
-    must fit is the one at the largest bandwidth a pair can reach."""
+    must fit is the one at the largest bandwidth a pair can reach.  text =
+    (want_text, want_indices, want_tolerance): one rf_pair_align_text call
+    instead (len(si) > 0) -> (scores, engine.PairText)."""
     if len(si) == 0:
         empty = (np.empty(0), ([] if want_moves else None), np.empty(0, np.int32))
         return empty if smart is None else empty + (np.empty(0, np.int32), np.empty(0, np.int32))
@@ -72,6 +79,10 @@ def _run(e, seqs, templates, si, ti, bws, flags, want_moves, smart=None):
                           f"{at} is wider than the {MAX_BAND_ROWS} the engine aligns without bands")
     e.set_sequences(0, seqs)
     e.set_templates(0, templates)
+    if text is not None:
+        thr, fixed, md = smart if smart is not None else (None, None, 0)
+        return e.pair_align_text(si, ti, bws, thr, fixed=fixed, max_doublings=md, flags=flags, want_text=text[0],
+                                 want_indices=text[1], want_tolerance=text[2], caps=(slen[si] + tlen[ti], tlen[ti]))
     if smart is None:
         return e.pair_align(si, ti, bws, flags, want_moves=want_moves, caps=slen[si] + tlen[ti])
     return e.pair_align_smart(si, ti, bws, smart[0], fixed=smart[1], max_doublings=smart[2], flags=flags,
@@ -95,16 +106,54 @@ def align_moves_many(seqs, templates, pairs=None, bandwidth=None, skew_matches=F
     return moves
 
 
-def align_many(seqs, templates, pairs=None, bandwidth=None, skew_matches=False, trim=False, engine=None):
-    """align (align.jl:346-353) per pair -> [(aligned t, aligned s)] with '-'
-    gaps; None for a pair the reference raises on."""
+def _products(seqs, templates, pairs, bandwidth, skew_matches, trim, engine, smart, text):
+    """The products text = (texts, indices, tolerances) of every pair, from
+    one engine call: pair_align_text where the engine has it, else the moves
+    and align.py's host functions.  smart: None, or (pvalue, max_doublings).
+    -> ({"text": [...], "indices": [...], "tolerance": int32 array} of those
+    asked for, final bandwidths); None / -1 for a pair the reference raises on."""
     seqs = list(seqs)
     templates = [DNASeq(t) for t in templates]
     si, ti = _pairs(pairs, len(seqs), len(templates))
-    moves = align_moves_many(seqs, templates, pairs=pairs, bandwidth=bandwidth, skew_matches=skew_matches,
-                             trim=trim, engine=engine)
-    return [None if mv is None else moves_to_aligned_seqs(mv, templates[int(j)], seqs[int(i)].seq)
-            for mv, i, j in zip(moves, si, ti)]
+    if bandwidth is None:
+        bws = np.array([s.bandwidth for s in seqs], np.int64)[si]
+    else:
+        bws = np.full(si.shape, int(bandwidth), np.int64)
+    if smart is not None:
+        smart = smart_inputs(seqs, si, smart[0]) + (smart[1],)
+    flags = (RF_SKEW if skew_matches else 0) | (RF_TRIM if trim else 0)
+    e = _engine(engine)
+    out = {}
+    if len(si) and hasattr(e, "pair_align_text"):
+        _, r = _run(e, seqs, templates, si, ti, bws, flags, False, smart=smart, text=text)
+        if text[0]:
+            out["text"] = r.texts()
+        if text[1]:
+            out["indices"] = [r.indices(k) for k in range(r.n)]
+        if text[2]:
+            out["tolerance"] = r.tolerance.copy()
+        return out, r.bandwidths.copy()
+    res = _run(e, seqs, templates, si, ti, bws, flags, True, smart=smart)
+    moves, out_bw = res[1], (res[3] if smart is not None else bws.astype(np.int32))
+    if text[0]:
+        out["text"] = [None if mv is None else moves_to_aligned_seqs(mv, templates[int(j)], seqs[int(i)].seq)
+                       for mv, i, j in zip(moves, si, ti)]
+    if text[1]:
+        out["indices"] = [None if mv is None else
+                          np.array(moves_to_indices(mv, len(templates[int(j)]), len(seqs[int(i)])), np.int32)
+                          for mv, i, j in zip(moves, si, ti)]
+    if text[2]:
+        out["tolerance"] = np.array([-1 if mv is None else
+                                     band_tolerance(mv, len(seqs[int(i)]) + 1, len(templates[int(j)]) + 1, int(b))
+                                     for mv, i, j, b in zip(moves, si, ti, out_bw)], np.int32)
+    return out, out_bw
+
+
+def align_many(seqs, templates, pairs=None, bandwidth=None, skew_matches=False, trim=False, engine=None):
+    """align (align.jl:346-353) per pair -> [(aligned t, aligned s)] with '-'
+    gaps; None for a pair the reference raises on."""
+    out, _ = _products(seqs, templates, pairs, bandwidth, skew_matches, trim, engine, None, (True, False, False))
+    return out["text"]
 
 
 def smart_inputs(seqs, si, pvalue):
@@ -140,16 +189,38 @@ def smart_align_moves_many(seqs, templates, pairs=None, pvalue=BANDWIDTH_PVALUE,
 
 def smart_align_many(seqs, templates, pairs=None, pvalue=BANDWIDTH_PVALUE, max_doublings=5, bandwidth=None,
                      skew_matches=False, trim=False, engine=None):
-    """align_many over smart_align_moves_many
+    """align_many with smart_align_moves_many's band doubling
     -> ([(aligned t, aligned s)] with None for a pair the reference raises
     on, int32 bandwidths)."""
-    seqs = list(seqs)
-    templates = [DNASeq(t) for t in templates]
-    si, ti = _pairs(pairs, len(seqs), len(templates))
-    moves, out_bw = smart_align_moves_many(seqs, templates, pairs=pairs, pvalue=pvalue, max_doublings=max_doublings,
-                                           bandwidth=bandwidth, skew_matches=skew_matches, trim=trim, engine=engine)
-    return [None if mv is None else moves_to_aligned_seqs(mv, templates[int(j)], seqs[int(i)].seq)
-            for mv, i, j in zip(moves, si, ti)], out_bw
+    out, out_bw = _products(seqs, templates, pairs, bandwidth, skew_matches, trim, engine, (pvalue, max_doublings),
+                            (True, False, False))
+    return out["text"], out_bw
+
+
+def align_indices_many(seqs, templates, pairs=None, pvalue=BANDWIDTH_PVALUE, max_doublings=0, bandwidth=None,
+                       skew_matches=False, trim=False, engine=None):
+    """moves_to_indices (align.jl:322-335) of every pair's alignment: for
+    each move that advances in the template, the 1-based sequence position
+    reached (0 before the first sequence base).  A codon deletion covers
+    three template bases with one entry, as in the reference.  max_doublings
+    > 0 aligns with smart_align_many's band doubling, 0 (default) at the
+    given bandwidth like align_many.  One engine call.
+    -> list of int32 arrays; None for a pair the reference raises on."""
+    out, _ = _products(seqs, templates, pairs, bandwidth, skew_matches, trim, engine,
+                       (pvalue, max_doublings) if max_doublings else None, (False, True, False))
+    return out["indices"]
+
+
+def band_tolerances(seqs, templates, pairs=None, pvalue=BANDWIDTH_PVALUE, max_doublings=0, bandwidth=None,
+                    skew_matches=False, trim=False, engine=None):
+    """band_tolerance (align.jl:262-284) of every pair's alignment in the band
+    of its last fill: how close the path comes to a band edge that is not the
+    matrix's (len(seq) + 1 if the band is never such an edge).  Arguments as
+    align_indices_many's.  One engine call.
+    -> int32 array; -1 for a pair the reference raises on."""
+    out, _ = _products(seqs, templates, pairs, bandwidth, skew_matches, trim, engine,
+                       (pvalue, max_doublings) if max_doublings else None, (False, False, True))
+    return out["tolerance"]
 
 
 def edit_distances(templates, seqs, engine=None) -> np.ndarray:
@@ -222,5 +293,5 @@ def correct_shifts_many(consensuses, references, log_p=-1.0, bandwidth=-1, score
     return out
 
 
-__all__ = ["align_moves_many", "align_many", "smart_align_moves_many", "smart_align_many", "edit_distances",
-           "correct_shifts_many", "MAX_BAND_ROWS"]
+__all__ = ["align_moves_many", "align_many", "smart_align_moves_many", "smart_align_many", "align_indices_many",
+           "band_tolerances", "edit_distances", "correct_shifts_many", "MAX_BAND_ROWS"]
