@@ -201,6 +201,18 @@ int rf_code_stats(const rf_ctx *ctx, int64_t *entries3, int64_t *entries1, int64
  * ("sequence changed since the bands were computed") until rf_realign fills
  * it again; a fill of only one of its two bands leaves the other stale.
  * rf_download_band still returns the old cells.
+ * A failed fill does the same: when rf_realign / rf_realign_jobs returns
+ * RF_ERR_NUMERIC ("new score is invalid"), the reference's error() has left
+ * no state behind, so the same calls refuse every band that call was asked to
+ * fill -- the bands of its good jobs too -- with RF_ERR_STATE ("the last fill
+ * of this band failed") until a later fill of the band succeeds.  Any other
+ * failure of the call past its argument checks (RF_ERR_ARG changes nothing)
+ * marks the bands it named in the same way.  The mark belongs to this
+ * context: a caller that spreads one logical call over several contexts
+ * applies it to the other contexts' bands itself.  The
+ * partner band a forward-only or backward-only call did not name, and the
+ * bands of slots it did not name, stay as they were; rf_download_band and
+ * rf_slot_geometry still answer for a failed band.
  * Per sequence k (n_k = off[k+1]-off[k]):
  *   bases    off[k]..off[k+1]                    (n_k codes)
  *   match, mismatch, ins at off[k]..off[k+1]     (rifrafsequences.jl:45-47)

@@ -5543,6 +5543,10 @@ struct TplObj {
 
 struct Band {
     bool valid = false;
+    // the last fill this band was planned for raised (RF_ERR_NUMERIC): the
+    // geometry stands and rf_download_band returns the cells, but no call
+    // reads them as an alignment until a later fill of the band succeeds
+    bool failed = false;
     int32_t seq = -1, tpl = -1, bw = 0, n = 0, m = 0, H = 0, flags = 0;
     int32_t P = 0;   // kappa row stride (band_stride at the fill)
     uint64_t tplver = 0;
@@ -5858,6 +5862,9 @@ bool seq_stale(const rf_ctx *ctx, const Band &b)
 {
     return b.seq < 0 || b.seq >= (int32_t)ctx->seqs.size() || ctx->seqs[b.seq].version != b.seqver;
 }
+
+// The refusal of a band whose last fill raised (Band::failed).
+const char *const FILL_FAILED = "the last fill of this band failed";
 
 #define HIPCHK(ctx, call)                                                          \
     do {                                                                           \
@@ -6471,6 +6478,7 @@ int rf_release_bands(rf_ctx *ctx)
     for (auto &s : ctx->slots)
         for (Band *b : {&s.a, &s.b}) {
             b->valid = false;
+            b->failed = false;
             b->r.off = -1;
             b->r.cap = 0;
         }
@@ -7072,8 +7080,38 @@ int rf_set_templates_ids(rf_ctx *ctx, int32_t ntpl, const int32_t *ids, const ui
     return 0;
 }
 
+static int realign_run(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32_t *seq, const int32_t *tpl,
+                       const int32_t *bw, const int32_t *jf, double *out_score);
+
+// rf_realign / rf_realign_jobs.  A call that gets past its argument checks and
+// then fails -- the reference's error() (RF_ERR_NUMERIC), an allocation, a HIP
+// error -- leaves no band behind that reads as filled: the reference's
+// error() leaves no state, so every band the call named, the good jobs' too,
+// is refused by the read-back calls until a later fill succeeds.  The plan is
+// dropped, so that fill plans again (and clears the mark); the epoch moves for
+// the scorers' validation skip.
 static int realign_impl(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32_t *seq, const int32_t *tpl,
                         const int32_t *bw, const int32_t *jf, double *out_score)
+{
+    const int e = realign_run(ctx, njobs, slot, seq, tpl, bw, jf, out_score);
+    if (e == 0 || e == RF_ERR_ARG)   // RF_ERR_ARG: refused before anything was planned
+        return e;
+    for (int32_t k = 0; k < njobs; ++k) {
+        if (slot[k] < 0 || slot[k] >= (int32_t)ctx->slots.size())
+            continue;
+        Slot &S = ctx->slots[slot[k]];
+        if ((jf[k] & RF_FWD) && S.a.valid)
+            S.a.failed = true;
+        if ((jf[k] & RF_BWD) && S.b.valid)
+            S.b.failed = true;
+    }
+    ctx->rplan.valid = false;
+    ++ctx->state_epoch;
+    return e;
+}
+
+static int realign_run(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32_t *seq, const int32_t *tpl,
+                       const int32_t *bw, const int32_t *jf, double *out_score)
 {
     if (!ctx || njobs < 0 || (njobs > 0 && (!slot || !seq || !tpl || !bw || !jf)))
         return fail(ctx, RF_ERR_ARG, "rf_realign: bad arguments");
@@ -7159,6 +7197,7 @@ static int realign_impl(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const i
                         b.n != S.n || b.m != T.m || b.H != H || b.P != P;
                 b.P = P;
                 b.valid = true;
+                b.failed = false;
                 b.seq = seq[k];
                 b.tpl = tpl[k];
                 b.bw = bw[k];
@@ -8214,6 +8253,8 @@ static int build_bt_tasks(rf_ctx *ctx, int32_t nslots, const int32_t *slot, std:
         if (slot[k] < 0 || slot[k] >= (int32_t)ctx->slots.size() || !ctx->slots[slot[k]].a.valid)
             return fail(ctx, RF_ERR_STATE, "rf_backtrace: slot has no A band");
         const Band &b = ctx->slots[slot[k]].a;
+        if (b.failed)
+            return fail(ctx, RF_ERR_STATE, std::string("rf_backtrace: ") + FILL_FAILED);
         if (seq_stale(ctx, b))
             return fail(ctx, RF_ERR_STATE, "rf_backtrace: sequence changed since the bands were computed");
         const SeqObj &S = ctx->seqs[b.seq];
@@ -8350,6 +8391,10 @@ static bool score_band_ok(const rf_ctx *ctx, int32_t s, std::string &why)
     const Slot &S = ctx->slots[s];
     if (!S.a.valid || !S.b.valid) {
         why = "slot has no A/B bands";
+        return false;
+    }
+    if (S.a.failed || S.b.failed) {
+        why = FILL_FAILED;
         return false;
     }
     if (S.a.seq != S.b.seq || S.a.tpl != S.b.tpl || S.a.bw != S.b.bw || S.a.tplver != S.b.tplver ||
@@ -8671,6 +8716,8 @@ static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_of
             if (sl < 0 || sl >= (int32_t)ctx->slots.size())
                 return fail(ctx, RF_ERR_ARG, "rf_score_dense: unknown slot");
             const Slot &S = ctx->slots[sl];
+            if (S.a.valid && S.b.valid && (S.a.failed || S.b.failed))
+                return fail(ctx, RF_ERR_STATE, std::string("rf_score_dense: ") + FILL_FAILED);
             if (!S.a.valid || !S.b.valid || S.a.seq != S.b.seq || S.a.tpl != S.b.tpl ||
                 S.a.bw != S.b.bw || S.a.tplver != S.b.tplver || S.a.m != S.b.m || S.a.seqver != S.b.seqver ||
                 S.a.n != S.b.n)
@@ -8985,6 +9032,8 @@ int rf_internal_aln_sums_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_o
     for (int32_t k = 0; k < ns; ++k) {
         if (slots[k] < 0 || slots[k] >= (int32_t)ctx->slots.size() || !ctx->slots[slots[k]].a.valid)
             return fail(ctx, RF_ERR_STATE, "rf_aln_error_sums: slot has no A band");
+        if (ctx->slots[slots[k]].a.failed)
+            return fail(ctx, RF_ERR_STATE, std::string("rf_aln_error_sums: ") + FILL_FAILED);
         if (seq_stale(ctx, ctx->slots[slots[k]].a))
             return fail(ctx, RF_ERR_STATE, "rf_aln_error_sums: sequence changed since the bands were computed");
         const SeqObj &S = ctx->seqs[ctx->slots[slots[k]].a.seq];
