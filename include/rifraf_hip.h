@@ -641,6 +641,50 @@ int rf_last_codon_ms(const rf_ctx *ctx, double *ms);
 /* k_codon_dense ms of the last rf_score_dense_ref (inside its score_ms). */
 int rf_last_codon_dense_ms(const rf_ctx *ctx, double *ms);
 
+/* The DP launch planner made observable (DESIGN.md §4 "DP launch planner").
+ * Every kernel family computes the same bits, so only these two calls show
+ * which one a task took.  A launch is a record of RF_DPL_FIELDS int32:
+ * kernel (RF_DPK_*), npi (NP = 1 << npi per lane; the k_dpr families), pmi
+ * (stride class, RF_DPK_DPR_LEAN_PM), first task, task count, stream (-1: the
+ * context's stream, else side stream 0..2), grid x, block size, dynamic LDS
+ * bytes (RF_DPK_DPM runs in chunks: the first chunk's grid).  No reference
+ * counterpart. */
+#define RF_DPK_DPR          0   /* k_dpr<NP, general>: four 16-lane tasks per wave     */
+#define RF_DPK_DPR_LEAN     1   /* k_dpr<NP, lean>                                      */
+#define RF_DPK_DPR_LEAN_PM  2   /* k_dpr<NP, lean, stride class pmi> (NP 1: exact P)    */
+#define RF_DPK_DPR_WIDE64   3   /* lean H 128..255: one 64-lane task per wave           */
+#define RF_DPK_DPR_WIDE32   4   /* lean H 64..127: two 32-lane tasks per wave           */
+#define RF_DPK_DPX_CODON    5   /* k_dpx, few non-lean H <= 127 tasks, one per wave     */
+#define RF_DPK_DPX_LEAN     6   /* k_dpx, latency mode: lean H <= 127, one per wave     */
+#define RF_DPK_DP64         7   /* k_dp<64>: H <= 2040, one task per wave               */
+#define RF_DPK_DPW_LDS      8   /* k_dp of 1,024 threads, ring in LDS                   */
+#define RF_DPK_DPW_GLOBAL   9   /* k_dp of 1,024 threads, ring in global memory         */
+#define RF_DPK_DPM         10   /* k_dpm: band slices across the CUs of an XCD          */
+#define RF_DPL_FIELDS       9
+/* rf_realign's planner on the host alone: no context, no GPU.  Job k is a read
+ * of n[k] bases (ncins[k] / ncdel[k] codon table entries, finite[k]: no -Inf
+ * table entry) against a template of m[k] at bandwidth bw[k] with flags[k]
+ * (RF_FWD and / or RF_BWD, RF_SKEW, RF_TRIM).  stride_a / stride_b (each may be
+ * NULL: the unpadded stride of the band's H) are the row strides of the A and
+ * B bands.  Options: nopt pairs (opt_key[i] = RF_OPT_DP_*, opt_val[i]), the
+ * rest at their defaults.  Outputs, each with room for 2 * njobs tasks / launch_cap
+ * launches: per task in device order its job, direction (0 forward, 1
+ * backward), launch (index into the launch records, which are in issue
+ * order) and score slot (the job's own when the task's score is the one
+ * rf_realign's out_score[job] reports, njobs + job for a backward fill beside
+ * a forward one).  RF_ERR_ARG: bad arguments (a negative length or table
+ * count, bw < 1, no direction, H + 2 m above 2^30, a stride below the band's
+ * row pairs or more than 16 above them), an unknown key, or more launches
+ * than launch_cap. */
+int rf_host_dp_plan(int32_t njobs, const int32_t *n, const int32_t *m, const int32_t *bw, const int32_t *flags,
+                    const int32_t *ncins, const int32_t *ncdel, const uint8_t *finite, const int32_t *stride_a,
+                    const int32_t *stride_b, int32_t nopt, const int32_t *opt_key, const int32_t *opt_val,
+                    int32_t *task_job, int32_t *task_dir, int32_t *task_launch, int32_t *task_out,
+                    int32_t *ntasks, int32_t launch_cap, int32_t *launches, int32_t *nlaunches);
+/* The launch records of the context's last successful rf_realign /
+ * rf_realign_jobs, in issue order; RF_ERR_ARG when there are more than cap. */
+int rf_last_dp_launches(const rf_ctx *ctx, int32_t cap, int32_t *launches, int32_t *nlaunches);
+
 #ifdef __cplusplus
 }
 #endif

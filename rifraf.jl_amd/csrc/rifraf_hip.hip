@@ -59,6 +59,7 @@
 #include <vector>
 
 #include "../../include/rifraf_hip.h"
+#include "rifraf_dp_plan.h"
 
 #define RF_INF (__builtin_inf())
 
@@ -89,18 +90,6 @@ typedef double dvec2 __attribute__((ext_vector_type(2)));
 #define DP_STORE(p, v) (*(p) = (v))
 #endif
 
-__host__ __device__ inline int band_P(int H) { return ((H + 1) >> 1) | 1; }
-// Row stride of a band as allocated: H >= pad_h (> 0) gives rows of a whole
-// number of 128-B lines, so that the wide-band scorer's 32-diagonal segments
-// read exactly one line per kappa row (k_score_segl); else the odd stride.
-// rf_realign pads every band of a call whose widest band has H >=
-// RF_OPT_BAND_PAD (pad_h 1 for the call), none otherwise.
-inline int band_stride(int H, int pad_h)
-{
-    return (pad_h > 0 && H >= pad_h) ? (((H + 1) >> 1) + 15) & ~15 : band_P(H);
-}
-__host__ __device__ inline int64_t band_K(int H, int m) { return (int64_t)H + 2 * (int64_t)m; }
-
 __device__ __forceinline__ size_t bidx(int d, int jj, int P)
 {
     return (size_t)(d + 2 * jj) * (size_t)P + (size_t)(d >> 1);
@@ -110,29 +99,7 @@ __device__ __forceinline__ size_t bidx(int d, int jj, int P)
 // device-side descriptors
 // ---------------------------------------------------------------------
 
-// One DP fill task = (slot, direction).
-struct alignas(16) DPTask {
-    int64_t band;   // output band offset (doubles)
-    int64_t sb;     // sequence bases offset (bytes)
-    int64_t tab;    // sequence tables offset (doubles)
-    int64_t tb;     // template bases offset (bytes)
-    int32_t n, m, bw, H;
-    int32_t c;      // h_off + bw
-    int32_t ncins, ncdel;
-    int32_t flags;  // 1 = reverse, 2 = skew, 4 = trim
-    int32_t out_idx;
-    int32_t klen;   // number of anti-diagonals K = H + 2m
-    int32_t P;      // kappa row stride
-    int32_t pad;
-};
-
-// DPTask.flags bit: the read carries row codes (rf_set_sequences) -- one
-// 8-B record per read position i: bits 0-15 the code of (match, mismatch,
-// ins)[i], 16-31 / 32-47 the codes of del[i] / del[i+1], 48-55 the base.
-// Codes index the context's dictionary: RF_CODES entries of 4 doubles
-// {match, mismatch, ins, 0}, then RF_CODES del values.
-constexpr int RF_TASK_CODED = 1024;
-constexpr int RF_CODES = 1 << 16;
+constexpr int RF_CODES = 1 << 16;   // entries of the row codes' dictionary (DPTask: rifraf_dp_plan.h)
 // doubles from a read's table start to its row-code records
 __host__ __device__ inline int64_t row_code_off(int64_t n, int64_t nci, int64_t ncd) { return 4 * n + 1 + nci + ncd; }
 
@@ -786,7 +753,6 @@ struct alignas(16) EdgeRec {
     double mt, mm, is, ds;
     int sb, col, pad0, pad1;
 };
-__host__ __device__ constexpr int dpl_pmax(int np, int lpt = 16) { return (lpt * np) | 1; }   // band_P(2*LPT*NP-1)
 // carry slots on either side of a task's band-output rows: a flush writes
 // whole 128-B lines only and carries the partial line into the next block
 constexpr int DPL_CARRY = 16;
@@ -800,14 +766,6 @@ __host__ __device__ constexpr int dpl_flush_stores(int np, int pm, int lpt = 16)
 {
     return (dpl_b(np, lpt) * pm + DPL_CARRY / 2 + lpt - 1) / lpt;
 }
-// stride classes of the lean DP launches: k_dpr<1 << npi, true, dpr_pm(npi, pmi)>
-// takes the lean tasks of NP class npi with P <= dpr_pm (the largest is the
-// class maximum 16 * NP | 1)
-__host__ __device__ constexpr int dpr_pm(int npi, int pmi)
-{
-    // NP = 1: P <= 17 (H <= 31); NP = 2: 17..33; NP = 4: 33..65; NP = 8: 65..129
-    return npi == 0 ? 11 + 2 * pmi : npi == 1 ? 19 + 4 * pmi + (pmi == 3 ? 2 : 0) : (((16 << npi) * (pmi + 5)) / 8) | 1;
-}
 extern __shared__ __attribute__((aligned(16))) char dpl_smem[];
 
 // PM: the largest band row stride P of the launch's tasks (default: the
@@ -820,12 +778,7 @@ extern __shared__ __attribute__((aligned(16))) char dpl_smem[];
 #ifndef DPR_WPE64
 #define DPR_WPE64 2   // minimum waves per SIMD requested for the 64-lane kernels
 #endif
-// PFIX: every task of the launch has row stride exactly PM (the host routes
-// only such tasks to it), so the blocked interior's LDS offsets i * P are
-// compile-time immediates instead of one address register per step.
-#ifndef DPR_PFIX
-#define DPR_PFIX 1
-#endif
+// PFIX (DPR_PFIX, rifraf_dp_plan.h): every task of the launch has stride PM
 template <int NP, bool LEAN, int PM, int LPT, bool PFIX>
 __device__ __forceinline__ void dpr_body(const int blk, const DPTask *__restrict__ tasks, int ntasks,
                                          const uint8_t *__restrict__ bases, const double *__restrict__ tabs,
@@ -1330,6 +1283,7 @@ k_dpr(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ 
 constexpr int PS_B = 16;           // periods per edge-record block of the fast tier (one record per lane)
 constexpr int PS_FAST_H = 255;     // widest band of the fast tier (k_ps<2, 64>)
 constexpr int PS_GEN64_H = 2040;   // widest band of the one-wave general tier (ring < 64 KB); above: DPW_NT threads
+static_assert(DPW_LDS_H == DP_LDS_H && PS_FAST_H == DP_FAST_H && PS_GEN64_H == DP_GEN64_H, "rifraf_dp_plan.h's limits");
 constexpr int PS_CHUNK = 65536;    // pairs per launch set of rf_pair_scores (RF_OPT_PAIR_CHUNK's default)
 constexpr int PA_TRACE_MB = 1024;  // RF_OPT_PAIR_TRACE_MB's default
 __host__ __device__ inline int pa_hp(int H) { return (H + 1) & ~1; }
@@ -2129,18 +2083,7 @@ k_pa_emit(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restric
 // Same candidates, FP64 sums and strict-'>' values as k_dp: bit-identical;
 // cells left of the DP (jj < 0) are stored as -Inf, which k_dp leaves out.
 // ---------------------------------------------------------------------
-// geometry (profiles/r06p_exp_dpm.out, configs[2]'s band, ms per call):
-// 1 pair per lane, hand-off every 32 steps 0.745; every 16 0.822; 2 pairs
-// per lane, every 32 1.064, every 64 0.984 (k_dpw: 3.35)
-#ifndef DPM_NPL_
-#define DPM_NPL_ 1
-#endif
-#ifndef DPM_B_
-#define DPM_B_ 32
-#endif
-constexpr int DPM_NPL = DPM_NPL_;                 // pairs per lane
-constexpr int DPM_B = DPM_B_;                     // anti-diagonals per hand-off
-constexpr int DPM_OWN = 64 * DPM_NPL - DPM_B;     // pairs per slice
+// DPM_NPL / DPM_B / DPM_OWN, dpm_slices and the slice limits: rifraf_dp_plan.h
 constexpr int DPM_RING = 512;                     // staged rows / columns (8 blocks of 64)
 constexpr int DPM_RINGX = DPM_RING + 64 * DPM_NPL;   // + the mirrored tail
 constexpr int DPM_SPIN = 1 << 22;                 // polls before error 4
@@ -2148,17 +2091,6 @@ constexpr unsigned DPM_NOSTORE = 0x80000000u;     // past every band (K * P * 8 
 constexpr long long DPM_UNSET = -1;               // the fill pattern of a band not yet stored
 constexpr int DPM_SC1 = 16;                       // buffer-store cache policy: sc1 (write-through)
 static_assert(DPM_OWN > 0 && (DPM_B / 2) % DPM_NPL == 0 && 128 % DPM_B == 0, "slice geometry");
-
-__host__ __device__ constexpr int dpm_slices(int H) { return ((H + 1) / 2 + DPM_OWN - 1) / DPM_OWN; }
-// A band's slices spin on each other, so they must be resident together:
-// at most DPM_TASK_SLICES per band (an XCD holds 8 of these 20-KB workgroups
-// per CU, 32 CUs: 256).  Workgroups of one launch dispatch in order, so the
-// bands of one XCD become resident one after another (each waits only for
-// earlier bands, which are whole); wider bands take k_dp.  Launches from
-// other streams (a second engine) interleave with it, so one launch keeps
-// to DPM_XCD_SLICES per XCD (more bands: further launches on its stream).
-constexpr int DPM_TASK_SLICES = 160;
-constexpr int DPM_XCD_SLICES = 64;
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -2529,9 +2461,6 @@ struct DpxStage {
 };
 
 constexpr unsigned DPX_NOSTORE = 0x80000000u;   // buffer offset past any band: the store is dropped
-// a k_dpx task: H <= 127 (lanes hold diagonal pairs) and a band below 2 GiB
-// (32-bit buffer offsets, DPX_NOSTORE past it)
-inline bool dpx_fits(const DPTask &t) { return t.H <= 127 && (int64_t)t.klen * t.P * 8 < ((int64_t)1 << 31); }
 
 template <int PAR, bool FAST, bool CODON, bool CHECK>
 __device__ __forceinline__ double dpx_cell(const DPTask &T, bool trim, int d, int ii, int jj, double v1,
@@ -5704,37 +5633,24 @@ struct CodeDict {
 // Tuning options (rf_set_option keys, include/rifraf_hip.h).  Every option
 // selects between bit-identical code paths; defaults come from the RIFRAF_*
 // environment once, at rf_create, and never from a hot path.
-#ifndef DP_WIDE_DEFAULT
-#define DP_WIDE_DEFAULT 3
-#endif
-struct Opts {
+// The DP launch planner's options are DpOpts (rifraf_dp_plan.h).
+struct Opts : DpOpts {
     int score_mode = 0;     // RF_OPT_SCORE_MODE: 0 auto, 1 fused, 2 split
     int score_kernel = 0;   // RF_OPT_SCORE_KERNEL: 0 auto, 1 general, 2 seg, 3 ws (k_score_ws when it fits)
     int lean_lds_kb = 0;    // RF_OPT_LEAN_LDS_KB: k_score_ws LDS budget (0 = default 160 KB)
-    int dp_wide = DP_WIDE_DEFAULT;   // RF_OPT_DP_WIDE: wide lean tasks (bit 0: H 128..255 in 64 lanes,
-                                     // bit 1: H 64..127 in 32 lanes)
     int band_pad_h = 64;    // RF_OPT_BAND_PAD: a realign call whose widest band has H >= this gets
                             // 128-B-line rows for all its bands (0: never, 1: always)
     int bt_win_kb = 16;     // RF_OPT_BT_WIN_KB: k_bt_win A window (16 or 32 KB of LDS)
     int stage_kb = 262144;  // RF_OPT_STAGE_KB: rf_set_sequences staging chunk (KB of tables)
-    int dp_psplit = -1;     // RF_OPT_DP_PSPLIT: lean stride-class split mask (-1 auto)
-    int dp_np8 = 1;         // RF_OPT_DP_NP8: H 128..255 in k_dpr<8> (0: k_dp<64>)
-    int dp_np8_lean = 1;    // RF_OPT_DP_NP8_LEAN: lean k_dpr<8> path
-    int dp_streams = 1;     // RF_OPT_DP_STREAMS: DP classes on concurrent streams
     int aln_sums_host = 0;  // RF_OPT_ALN_SUMS_HOST: 1 = rf_aln_error_sums folds the moves on the host
     int aln_marks_min = 128;   // RF_OPT_ALN_MARKS_MIN: device QV sums in two launches above this many reads per group
     int sync_block = 2;     // RF_OPT_SYNC_BLOCK: 1 host waits yield / sleep instead of spinning; 2 (default)
                             // auto: when the waiting thread may run on fewer than 4 CPUs
-    int dp_nl64 = 1024;     // RF_OPT_DP_NL64: at most this many non-lean H <= 127 tasks run in k_dpx
     int score_wgs = 2048;   // RF_OPT_SCORE_WGS: split-mode k_score_ws takes reads in chunks so that about
                             // this many workgroups remain
     int seg_wgs = 262144;   // RF_OPT_SEG_WGS: split-mode k_score_segl takes reads in chunks so that about
                             // this many workgroups remain
-    int dp_mc = 1;          // RF_OPT_DP_MC: H > 2040 bands without codon moves in k_dpm (0: k_dp)
     int bt_nw = 4;          // RF_OPT_BT_NW: waves per walk in launches of at most BTW_FEW walks (4 or 1)
-    int dp_pfit = 1;        // RF_OPT_DP_PFIT: lean NP >= 2 class launched at its tasks' stride class
-    int dp_lat = 2048;      // RF_OPT_DP_LAT: a call with at most this many lean H <= 127 tasks runs them all as
-                            // one k_dpx launch (latency mode: the launch cannot fill the GPU)
     int pair_chunk = PS_CHUNK;   // RF_OPT_PAIR_CHUNK: pairs per launch set of rf_pair_scores / rf_pair_align
     int pair_trace_mb = PA_TRACE_MB;   // RF_OPT_PAIR_TRACE_MB: MB of move trace per launch set of rf_pair_align
     int pair_walk = 0;                 // RF_OPT_PAIR_WALK: 0 auto, 1 k_pa_walk (lane per pair), 2 k_pa_walk_w (wave per pair)
@@ -5805,17 +5721,9 @@ struct rf_ctx {
         uint64_t gen = 0;
         uint64_t val_epoch = 0;   // state_epoch at which the job list was last validated
         std::vector<int32_t> slot, seq, tpl, bw, flags;   // flags: per job (rf_realign_jobs)
-        size_t nr[4][2] = {};   // k_dpr<1,2,4,8> x {general, lean}
-        size_t nrp[4][4] = {};  // lean k_dpr<NP, true, PM> split by band row stride (dpr_pm)
-        size_t nw[2] = {};     // lean wide-task classes (RF_OPT_DP_WIDE)
-        size_t nx = 0;         // latency-bound non-lean tasks, k_dpx (RF_OPT_DP_NL64)
-        size_t nl = 0;         // latency-mode lean tasks, one k_dpx<false, false> class (RF_OPT_DP_LAT)
-        size_t nwm = 0;        // very wide bands without codon moves across CUs (k_dpm, RF_OPT_DP_MC)
-        int gm = 0;            // their most slices
-        size_t n64 = 0, ng = 0;
-        int hmax64 = 0, hmaxg = 0;
-        std::vector<DPTask> tasks;   // host copy of the uploaded descriptors
+        DpPlan dp;   // host copy of the uploaded descriptors, and their launches
     } rplan;
+    std::vector<DpLaunch> last_dp;   // launches of the last successful rf_realign (rf_last_dp_launches)
     std::vector<int32_t> jflags;   // rf_realign: the call's flags for every job
     struct {
         bool valid = false;
@@ -6155,8 +6063,6 @@ int check_err(rf_ctx *ctx)
     return check_err_hdn(ctx);
 }
 
-int band_rows(int n, int m, int bw) { return 2 * bw + std::abs(n - m) + 1; }
-
 // k_score stages the kappa rows of a work item through LDS; size the
 // per-band buffer for the 90th-percentile window (at most 24 KB per band,
 // two bands per single-wave block), larger windows read in place.
@@ -6407,28 +6313,19 @@ static int *opt_slot(rf_ctx *ctx, int32_t key)
     case RF_OPT_SCORE_MODE: return &o.score_mode;
     case RF_OPT_SCORE_KERNEL: return &o.score_kernel;
     case RF_OPT_LEAN_LDS_KB: return &o.lean_lds_kb;
-    case RF_OPT_DP_PSPLIT: return &o.dp_psplit;
-    case RF_OPT_DP_NP8: return &o.dp_np8;
-    case RF_OPT_DP_NP8_LEAN: return &o.dp_np8_lean;
-    case RF_OPT_DP_STREAMS: return &o.dp_streams;
     case RF_OPT_BT_WIN_KB: return &o.bt_win_kb;
     case RF_OPT_STAGE_KB: return &o.stage_kb;
     case RF_OPT_BAND_PAD: return &o.band_pad_h;
-    case RF_OPT_DP_WIDE: return &o.dp_wide;
     case RF_OPT_ALN_SUMS_HOST: return &o.aln_sums_host;
     case RF_OPT_ALN_MARKS_MIN: return &o.aln_marks_min;
     case RF_OPT_SYNC_BLOCK: return &o.sync_block;
-    case RF_OPT_DP_NL64: return &o.dp_nl64;
-    case RF_OPT_DP_LAT: return &o.dp_lat;
     case RF_OPT_SCORE_WGS: return &o.score_wgs;
     case RF_OPT_SEG_WGS: return &o.seg_wgs;
-    case RF_OPT_DP_PFIT: return &o.dp_pfit;
-    case RF_OPT_DP_MC: return &o.dp_mc;
     case RF_OPT_BT_NW: return &o.bt_nw;
     case RF_OPT_PAIR_CHUNK: return &o.pair_chunk;
     case RF_OPT_PAIR_TRACE_MB: return &o.pair_trace_mb;
     case RF_OPT_PAIR_WALK: return &o.pair_walk;
-    default: return nullptr;
+    default: return dp_opt(o, key);   // the DP launch planner's
     }
 }
 
@@ -7110,6 +7007,290 @@ static int realign_impl(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const i
     return e;
 }
 
+// The DPTask of one alignment, the single place one is filled (no slot, no
+// band: the caller adds those); fl: 1 = reverse, 2 = skew, 4 = trim
+static DPTask pair_task(const SeqObj &S, const TplObj &T, int bw, int fl, int32_t out_idx)
+{
+    DPTask t{};
+    t.sb = S.bases.off;
+    t.tab = S.tabs.off / 8;
+    t.tb = T.bases.off;
+    t.n = S.n;
+    t.m = T.m;
+    t.bw = bw;
+    t.H = band_rows(S.n + 1, T.m + 1, bw);
+    t.c = std::max(T.m - S.n, 0) + bw;
+    t.ncins = S.ncins;
+    t.ncdel = S.ncdel;
+    t.flags = fl | (S.coded ? RF_TASK_CODED : 0);
+    t.out_idx = out_idx;
+    t.klen = t.H + 2 * t.m;
+    return t;
+}
+
+// The task of fill (dir, k) of an rf_realign call of njobs jobs into a band at
+// `band` (doubles) with row stride P.  Skew and trim are the forward fill's;
+// forward scores win out_score when both directions run.
+static DPTask realign_task(const SeqObj &S, const TplObj &T, int bw, int jf, int dir, int32_t k, int32_t njobs,
+                           int64_t band, int P)
+{
+    const int fl = dir == 1 ? 1 : ((jf & RF_SKEW) ? 2 : 0) | ((jf & RF_TRIM) ? 4 : 0);
+    DPTask t = pair_task(S, T, bw, fl, (dir == 0 || !(jf & RF_FWD)) ? k : njobs + k);
+    t.band = band;
+    t.P = P;
+    return t;
+}
+
+static int realign_check(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32_t *seq, const int32_t *tpl,
+                         const int32_t *bw)
+{
+    for (int32_t k = 0; k < njobs; ++k) {
+        if (slot[k] < 0 || seq[k] < 0 || seq[k] >= (int32_t)ctx->seqs.size() || !ctx->seqs[seq[k]].valid ||
+            tpl[k] < 0 || tpl[k] >= (int32_t)ctx->tpls.size() || !ctx->tpls[tpl[k]].valid)
+            return fail(ctx, RF_ERR_ARG, "rf_realign: unknown slot / sequence / template");
+        if (bw[k] < 1)
+            return fail(ctx, RF_ERR_ARG, "bandwidth must be positive");
+    }
+    return 0;
+}
+
+static Band &job_band(rf_ctx *ctx, int32_t slot, int dir) { return dir == 0 ? ctx->slots[slot].a : ctx->slots[slot].b; }
+
+// An identical job list on an unchanged layout: the descriptors on the device
+// are still exact; only the band bookkeeping (template / sequence version) moves
+static void realign_restamp(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32_t *seq, const int32_t *tpl,
+                            const int32_t *jf)
+{
+    bool changed = false;
+    for_each_fill(njobs, jf, [&](int dir, int32_t k) {
+        Band &b = job_band(ctx, slot[k], dir);
+        const uint64_t v = ctx->tpls[tpl[k]].version, sv = ctx->seqs[seq[k]].version;
+        changed = changed || b.tplver != v || b.seqver != sv;
+        b.tplver = v;
+        b.seqver = sv;
+        return 0;
+    });
+    if (changed)
+        ++ctx->state_epoch;
+}
+
+// Band bookkeeping of a new job list: every band's region, stride and metadata
+static int realign_bands(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32_t *seq, const int32_t *tpl,
+                         const int32_t *bw, const int32_t *jf)
+{
+    ++ctx->state_epoch;   // band metadata changes below
+    int32_t maxslot = -1;
+    for (int32_t k = 0; k < njobs; ++k)
+        maxslot = std::max(maxslot, slot[k]);
+    if (maxslot >= (int32_t)ctx->slots.size())
+        ctx->slots.resize(maxslot + 1);
+    bool moved = false;   // a band now describes another alignment
+    // RF_OPT_BAND_PAD: a call whose widest band reaches the threshold lays out
+    // all its bands with line-padded rows (the wide-band scorer reads them a
+    // line per row); narrower calls (c4-like) keep the odd stride, which the
+    // window scorer k_score_ws stages in fewer passes
+    int hmax_call = 0;
+    for (int32_t k = 0; k < njobs; ++k)
+        hmax_call = std::max(hmax_call, band_rows(ctx->seqs[seq[k]].n + 1, ctx->tpls[tpl[k]].m + 1, bw[k]));
+    const bool pad_call = ctx->opt.band_pad_h > 0 && hmax_call >= ctx->opt.band_pad_h;
+    const int e = for_each_fill(njobs, jf, [&](int dir, int32_t k) {
+        const SeqObj &S = ctx->seqs[seq[k]];
+        const TplObj &T = ctx->tpls[tpl[k]];
+        Band &b = job_band(ctx, slot[k], dir);
+        const int H = band_rows(S.n + 1, T.m + 1, bw[k]);
+        // A and B of one alignment share a row stride: every scorer reads
+        // both bands with one P, and the two are often filled by different
+        // calls (forward_moves with band doubling, then backward!) that
+        // may differ in pad_call
+        const Band &o = job_band(ctx, slot[k], 1 - dir);
+        const bool partner = o.valid && o.seq == seq[k] && o.tpl == tpl[k] && o.bw == bw[k] &&
+                             o.n == S.n && o.m == T.m && o.H == H && o.tplver == T.version &&
+                             o.seqver == S.version;
+        const int P = partner ? o.P : band_stride(H, pad_call ? 1 : 0);
+        if (int e = region_ensure(ctx, ctx->band_arena, b.r, band_K(H, T.m) * P * 8))
+            return e;
+        moved = moved || !b.valid || b.seq != seq[k] || b.tpl != tpl[k] || b.bw != bw[k] ||
+                b.n != S.n || b.m != T.m || b.H != H || b.P != P;
+        b.P = P;
+        b.valid = true;
+        b.failed = false;
+        b.seq = seq[k];
+        b.tpl = tpl[k];
+        b.bw = bw[k];
+        b.n = S.n;
+        b.m = T.m;
+        b.H = H;
+        b.flags = dir == 0 ? (jf[k] & (RF_SKEW | RF_TRIM)) : 0;
+        b.tplver = T.version;
+        b.seqver = S.version;
+        return 0;
+    });
+    if (e)
+        return e;
+    // scorer descriptors (rf_score_dense's plan) hold band geometry and
+    // sequence offsets: a band that now describes another read, template or
+    // bandwidth invalidates them even when its region did not move
+    if (moved)
+        ++ctx->layout_gen;
+    return 0;
+}
+
+// The call's tasks sorted into launches (dp_plan, rifraf_dp_plan.h).  Band
+// offsets are only final after every allocation (arena growth moves them), so
+// this follows realign_bands.
+static DpPlan realign_plan(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32_t *seq, const int32_t *tpl,
+                           const int32_t *bw, const int32_t *jf)
+{
+    std::vector<DPTask> tasks;
+    std::vector<uint8_t> finite;
+    tasks.reserve(2 * (size_t)njobs);
+    finite.reserve(2 * (size_t)njobs);
+    for_each_fill(njobs, jf, [&](int dir, int32_t k) {
+        const SeqObj &S = ctx->seqs[seq[k]];
+        const Band &b = job_band(ctx, slot[k], dir);
+        tasks.push_back(realign_task(S, ctx->tpls[tpl[k]], bw[k], jf[k], dir, k, njobs, b.r.off / 8, b.P));
+        finite.push_back(S.finite);
+        return 0;
+    });
+    return dp_plan(tasks, finite, ctx->opt);
+}
+
+// k_dpm runs a launch's bands in chunks: at most DPM_XCD_SLICES slices per
+// XCD per launch, the launches in sequence on one stream.  A launch's bands
+// become resident in order, but two launches from different streams
+// interleave, so each keeps to a share of an XCD (four such launches fit at
+// once)
+static int dpm_chunk(int gm) { return 8 * std::max(1, DPM_XCD_SLICES / gm); }
+
+// Grid, block and dynamic LDS of a launch (k_dpm: of its first chunk)
+struct DpGeom { unsigned grid, block; size_t lds; };
+static DpGeom dp_geom(const DpLaunch &L)
+{
+    const unsigned n = (unsigned)L.n;
+    switch (L.k) {
+    case DpKernel::Dpr: return {(n + 3) / 4, 64, 0};
+    case DpKernel::DprLean: return {(n + 3) / 4, 64, 4 * (size_t)dpl_task_bytes(1 << L.npi)};
+    case DpKernel::DprLeanPm: return {(n + 3) / 4, 64, 4 * (size_t)dpl_task_bytes(1 << L.npi, dpr_pm(L.npi, L.pmi))};
+    case DpKernel::DprWide64: return {n, 64, (size_t)dpl_task_bytes(2, dpl_pmax(2, 64), 64)};
+    case DpKernel::DprWide32: return {(n + 1) / 2, 64, 2 * (size_t)dpl_task_bytes(2, dpl_pmax(2, 32), 32)};
+    case DpKernel::DpxCodon:
+    case DpKernel::DpxLean: return {n, 128, 0};
+    case DpKernel::Dp64: return {n, 64, 4 * (size_t)(L.hmax + 6) * 8};   // the LDS ring: 4 anti-diagonals
+    case DpKernel::DpwLds: return {n, DPW_NT, 4 * (size_t)(L.hmax + 6) * 8};
+    case DpKernel::DpwGlobal: return {n, DPW_NT, 0};
+    case DpKernel::Dpm: return {8 * ((std::min(n, (unsigned)dpm_chunk(L.hmax)) + 7) / 8) * L.hmax, 64, 0};
+    }
+    return {0, 0, 0};
+}
+
+// The k_dpr instance of a 16-lane launch
+using DprFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, double *, int *, double *,
+                       const double *);
+static DprFn dpr_kernel(const DpLaunch &L)
+{
+#define KP(a, b) k_dpr<1 << (a), true, dpr_pm(a, b), 16, (a) == 0 && DPR_PFIX>
+#define KP4(a) KP(a, 0), KP(a, 1), KP(a, 2), KP(a, 3)
+    static const DprFn whole[4][2] = {{k_dpr<1, false>, k_dpr<1, true>}, {k_dpr<2, false>, k_dpr<2, true>},
+                                      {k_dpr<4, false>, k_dpr<4, true>}, {k_dpr<8, false>, k_dpr<8, true>}};
+    static const DprFn pm[4][4] = {{KP4(0)}, {KP4(1)}, {KP4(2)}, {KP4(3)}};
+#undef KP4
+#undef KP
+    return L.k == DpKernel::DprLeanPm ? pm[L.npi][L.pmi] : whole[L.npi][L.k == DpKernel::DprLean];
+}
+
+// The launches of a plan whose tasks are in scratch[8], scores into d_out.
+// The side streams fork from the context's stream and join it again.
+static int launch_dp(rf_ctx *ctx, const DpPlan &plan, double *d_out)
+{
+    const DPTask *d_tasks = (const DPTask *)ctx->scratch[8].p;
+    const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
+    const double *d_tabs = (const double *)ctx->tab_arena.d;
+    double *d_bands = (double *)ctx->band_arena.d;
+    const double *d_lut = (const double *)ctx->codes.lut.p;
+    if (int e = ensure_buf(ctx, ctx->scratch[7], 4 * (size_t)dpl_task_bytes(4)))  // lean padding-task sink
+        return e;
+    bool fork = false;
+    for (const DpLaunch &L : plan.launches) {
+        fork = fork || L.stream >= 0;
+        if (L.k == DpKernel::DpwLds || L.k == DpKernel::DpwGlobal)   // the global ring (sized for either)
+            if (int e = ensure_buf(ctx, ctx->scratch[10], L.n * 4 * (size_t)(L.hmax + 6) * 8))
+                return e;
+    }
+    if (fork)
+        HIPCHK(ctx, hipEventRecord(ctx->fork, ctx->stream));
+    std::vector<int> used_side;
+    for (const DpLaunch &L : plan.launches) {
+        hipStream_t st = ctx->stream;
+        if (L.stream >= 0) {
+            st = ctx->side[L.stream];
+            if (std::find(used_side.begin(), used_side.end(), L.stream) == used_side.end()) {
+                HIPCHK(ctx, hipStreamWaitEvent(st, ctx->fork, 0));
+                used_side.push_back(L.stream);
+            }
+        }
+        const int n = (int)L.n;
+        const DPTask *tk = d_tasks + L.at;
+        const DpGeom g = dp_geom(L);
+        const int ld = L.hmax + 6;   // k_dp's ring: doubles per anti-diagonal
+        switch (L.k) {
+        case DpKernel::Dpr:
+        case DpKernel::DprLean:
+        case DpKernel::DprLeanPm:
+            hipLaunchKernelGGL(dpr_kernel(L), dim3(g.grid), dim3(g.block), g.lds, st, tk, n, d_bases, d_tabs, d_bands,
+                               d_out, ctx->d_err, (double *)ctx->scratch[7].p, d_lut);
+            break;
+        case DpKernel::DpxCodon:
+        case DpKernel::DpxLean:
+            hipLaunchKernelGGL((L.k == DpKernel::DpxCodon ? k_dpx<true, true> : k_dpx<false, false>), dim3(g.grid),
+                               dim3(g.block), 0, st, tk, n, d_bases, d_tabs, d_bands, d_out, ctx->d_err);
+            break;
+        case DpKernel::DprWide64:
+        case DpKernel::DprWide32: {
+            const DprFn fn = L.k == DpKernel::DprWide64 ? k_dpr<2, true, dpl_pmax(2, 64), 64> : k_dpr<2, true, dpl_pmax(2, 32), 32>;
+            hipLaunchKernelGGL(fn, dim3(g.grid), dim3(g.block), g.lds, st, tk, n, d_bases, d_tabs, d_bands, d_out,
+                               ctx->d_err, (double *)ctx->scratch[7].p, d_lut);
+            break;
+        }
+        case DpKernel::Dp64:
+            hipLaunchKernelGGL((k_dp<64, false>), dim3(g.grid), dim3(g.block), g.lds, st, tk, n, d_bases, d_tabs,
+                               d_bands, d_out, ctx->d_err, ld, nullptr);
+            break;
+        case DpKernel::Dpm: {
+            // one workgroup per slice, a band's slices on one XCD; each band is
+            // filled with the not-yet-stored pattern first (the slices poll
+            // their halo cells)
+            const int gm = L.hmax, per = dpm_chunk(gm);
+            for (int c0 = 0; c0 < n; c0 += per) {
+                const int nc = std::min(per, n - c0);
+                bool trim = false;
+                for (int i = c0; i < c0 + nc; ++i) {
+                    const DPTask &t = plan.tasks[L.at + i];
+                    trim = trim || (t.flags & 4);
+                    HIPCHK(ctx, hipMemsetAsync(d_bands + t.band, 0xFF, (size_t)t.klen * t.P * 8, st));
+                }
+                hipLaunchKernelGGL(trim ? k_dpm<true> : k_dpm<false>, dim3((unsigned)(8 * ((nc + 7) / 8) * gm)),
+                                   dim3(64), 0, st, tk + c0, nc, gm, d_bases, d_tabs, d_bands, d_out, ctx->d_err);
+            }
+            break;
+        }
+        case DpKernel::DpwLds:
+        case DpKernel::DpwGlobal: {
+            const bool gring = L.k == DpKernel::DpwGlobal;
+            hipLaunchKernelGGL((gring ? k_dp<DPW_NT, true, DPW_NT> : k_dp<DPW_NT, false, DPW_NT>), dim3(g.grid),
+                               dim3(g.block), g.lds, st, tk, n, d_bases, d_tabs, d_bands, d_out, ctx->d_err, ld,
+                               gring ? (double *)ctx->scratch[10].p : nullptr);
+            break;
+        }
+        }
+    }
+    for (int si : used_side) {
+        HIPCHK(ctx, hipEventRecord(ctx->join[si], ctx->side[si]));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->join[si], 0));
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
 static int realign_run(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32_t *seq, const int32_t *tpl,
                        const int32_t *bw, const int32_t *jf, double *out_score)
 {
@@ -7130,260 +7311,19 @@ static int realign_run(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const in
     // its band bookkeeping would come out the same
     const bool fresh = same && P.val_epoch == ctx->state_epoch;
     if (!fresh)
-        for (int32_t k = 0; k < njobs; ++k) {
-            if (slot[k] < 0 || seq[k] < 0 || seq[k] >= (int32_t)ctx->seqs.size() || !ctx->seqs[seq[k]].valid ||
-                tpl[k] < 0 || tpl[k] >= (int32_t)ctx->tpls.size() || !ctx->tpls[tpl[k]].valid)
-                return fail(ctx, RF_ERR_ARG, "rf_realign: unknown slot / sequence / template");
-            if (bw[k] < 1)
-                return fail(ctx, RF_ERR_ARG, "bandwidth must be positive");
-        }
+        if (int e = realign_check(ctx, njobs, slot, seq, tpl, bw))
+            return e;
     if (same) {
-        // identical job list on an unchanged layout: descriptors on the device
-        // are still exact; only the band bookkeeping (template version) moves
         if (!fresh) {
-            bool changed = false;
-            for (int dir = 0; dir < 2; ++dir) {
-                for (int32_t k = 0; k < njobs; ++k) {
-                    if (!(jf[k] & (dir == 0 ? RF_FWD : RF_BWD)))
-                        continue;
-                    Band &b = dir == 0 ? ctx->slots[slot[k]].a : ctx->slots[slot[k]].b;
-                    const uint64_t v = ctx->tpls[tpl[k]].version, sv = ctx->seqs[seq[k]].version;
-                    changed = changed || b.tplver != v || b.seqver != sv;
-                    b.tplver = v;
-                    b.seqver = sv;
-                }
-            }
-            if (changed)
-                ++ctx->state_epoch;
+            realign_restamp(ctx, njobs, slot, seq, tpl, jf);
             P.val_epoch = ctx->state_epoch;
         }
     } else {
         P.valid = false;
-        ++ctx->state_epoch;   // band metadata changes below
-        int32_t maxslot = -1;
-        for (int32_t k = 0; k < njobs; ++k)
-            maxslot = std::max(maxslot, slot[k]);
-        if (maxslot >= (int32_t)ctx->slots.size())
-            ctx->slots.resize(maxslot + 1);
-        bool moved = false;   // a band now describes another alignment
-        // RF_OPT_BAND_PAD: a call whose widest band reaches the threshold lays out
-        // all its bands with line-padded rows (the wide-band scorer reads them a
-        // line per row); narrower calls (c4-like) keep the odd stride, which the
-        // window scorer k_score_ws stages in fewer passes
-        int hmax_call = 0;
-        for (int32_t k = 0; k < njobs; ++k)
-            hmax_call = std::max(hmax_call, band_rows(ctx->seqs[seq[k]].n + 1, ctx->tpls[tpl[k]].m + 1, bw[k]));
-        const bool pad_call = ctx->opt.band_pad_h > 0 && hmax_call >= ctx->opt.band_pad_h;
-        for (int dir = 0; dir < 2; ++dir) {
-            for (int32_t k = 0; k < njobs; ++k) {
-                if (!(jf[k] & (dir == 0 ? RF_FWD : RF_BWD)))
-                    continue;
-                const SeqObj &S = ctx->seqs[seq[k]];
-                const TplObj &T = ctx->tpls[tpl[k]];
-                Band &b = dir == 0 ? ctx->slots[slot[k]].a : ctx->slots[slot[k]].b;
-                const int H = band_rows(S.n + 1, T.m + 1, bw[k]);
-                // A and B of one alignment share a row stride: every scorer reads
-                // both bands with one P, and the two are often filled by different
-                // calls (forward_moves with band doubling, then backward!) that
-                // may differ in pad_call
-                const Band &o = dir == 0 ? ctx->slots[slot[k]].b : ctx->slots[slot[k]].a;
-                const bool partner = o.valid && o.seq == seq[k] && o.tpl == tpl[k] && o.bw == bw[k] &&
-                                     o.n == S.n && o.m == T.m && o.H == H && o.tplver == T.version &&
-                                     o.seqver == S.version;
-                const int P = partner ? o.P : band_stride(H, pad_call ? 1 : 0);
-                if (int e = region_ensure(ctx, ctx->band_arena, b.r, band_K(H, T.m) * P * 8))
-                    return e;
-                moved = moved || !b.valid || b.seq != seq[k] || b.tpl != tpl[k] || b.bw != bw[k] ||
-                        b.n != S.n || b.m != T.m || b.H != H || b.P != P;
-                b.P = P;
-                b.valid = true;
-                b.failed = false;
-                b.seq = seq[k];
-                b.tpl = tpl[k];
-                b.bw = bw[k];
-                b.n = S.n;
-                b.m = T.m;
-                b.H = H;
-                b.flags = dir == 0 ? (jf[k] & (RF_SKEW | RF_TRIM)) : 0;
-                b.tplver = T.version;
-                b.seqver = S.version;
-            }
-        }
-        // scorer descriptors (rf_score_dense's plan) hold band geometry and
-        // sequence offsets: a band that now describes another read, template or
-        // bandwidth invalidates them even when its region did not move
-        if (moved)
-            ++ctx->layout_gen;
-        // band offsets are only final after every allocation (arena growth moves them)
-        std::vector<DPTask> cr[4][2], c64, cg, cp[4][4], cw[2], cwm;
-        int hmax64 = 0, hmaxg = 0, gm = 0;
-        // RF_OPT_DP_PSPLIT: bit npi set = split lean class NP = 1 << npi by stride
-        // (default: NP = 1 only, and only when that class holds at least half
-        // of the tasks -- measured: c4 DP -5..9 %; splitting the wide classes,
-        // or a small NP = 1 class next to them (c5), made the fill slower)
-        int psplit = ctx->opt.dp_psplit >= 0 ? ctx->opt.dp_psplit : 1;
-        if (ctx->opt.dp_psplit < 0) {
-            size_t n1 = 0, nall = 0;
-            for (int dir = 0; dir < 2; ++dir) {
-                for (int32_t k = 0; k < njobs; ++k) {
-                    if (!(jf[k] & (dir == 0 ? RF_FWD : RF_BWD)))
-                        continue;
-                    const Band &b = dir == 0 ? ctx->slots[slot[k]].a : ctx->slots[slot[k]].b;
-                    n1 += b.H <= 31;
-                    ++nall;
-                }
-            }
-            if (2 * n1 < nall)
-                psplit = 0;
-        }
-        // latency mode (RF_OPT_DP_LAT, round 5): few lean tasks of H <= 127 --
-        // e.g. configs[2]'s 1,000 reads, or one cluster -- cannot fill the GPU
-        // whatever their class, so each runs at its own step latency; they all
-        // go to one 64-lane NP = 1 launch (one task per wave, one band pair
-        // per lane: the shortest step), on one stream
-        bool latmode = false;
-        {
-            size_t nl = 0;
-            for (int dir = 0; dir < 2; ++dir) {
-                for (int32_t k = 0; k < njobs; ++k) {
-                    if (!(jf[k] & (dir == 0 ? RF_FWD : RF_BWD)))
-                        continue;
-                    const SeqObj &S = ctx->seqs[seq[k]];
-                    const Band &b = dir == 0 ? ctx->slots[slot[k]].a : ctx->slots[slot[k]].b;
-                    const bool ln = S.ncins == 0 && S.ncdel == 0 && S.finite && !(dir == 0 && (jf[k] & (RF_SKEW | RF_TRIM)));
-                    nl += ln && b.H <= 127;
-                }
-            }
-            latmode = nl > 0 && nl <= (size_t)std::max(ctx->opt.dp_lat, 0);
-        }
-        std::vector<DPTask> cl;
-        for (int dir = 0; dir < 2; ++dir) {
-            for (int32_t k = 0; k < njobs; ++k) {
-                if (!(jf[k] & (dir == 0 ? RF_FWD : RF_BWD)))
-                    continue;
-                const SeqObj &S = ctx->seqs[seq[k]];
-                const TplObj &T = ctx->tpls[tpl[k]];
-                const Band &b = dir == 0 ? ctx->slots[slot[k]].a : ctx->slots[slot[k]].b;
-                DPTask t{};
-                t.band = b.r.off / 8;
-                t.sb = S.bases.off;
-                t.tab = S.tabs.off / 8;
-                t.tb = T.bases.off;
-                t.n = S.n;
-                t.m = T.m;
-                t.bw = bw[k];
-                t.H = b.H;
-                t.c = std::max(T.m - S.n, 0) + bw[k];
-                t.ncins = S.ncins;
-                t.ncdel = S.ncdel;
-                t.flags = (dir == 1 ? 1 : 0) | (dir == 0 && (jf[k] & RF_SKEW) ? 2 : 0) |
-                          (dir == 0 && (jf[k] & RF_TRIM) ? 4 : 0) | (S.coded ? RF_TASK_CODED : 0);
-                // out_score: forward scores win when both directions run
-                t.out_idx = (dir == 0 || !(jf[k] & RF_FWD)) ? k : njobs + k;
-                t.klen = t.H + 2 * t.m;
-                t.P = b.P;
-                // classes: k_dpr<NP> for H <= 32*NP-1 (NP = 1, 2, 4, 8), lean when
-                // there are no codon moves and no skew / trim; k_dp beyond
-                const int lean = (S.ncins == 0 && S.ncdel == 0 && S.finite && !(t.flags & 6)) ? 1 : 0;
-                const int npi = t.H <= 31 ? 0 : t.H <= 63 ? 1 : t.H <= 127 ? 2 : 3;
-                const bool np8 = npi < 3 || (t.H <= 255 && ctx->opt.dp_np8 && ctx->opt.dp_np8_lean);
-                // wide tasks for the wide lean bands: H 128..255 as one 64-lane
-                // task per wave, H 64..127 as two 32-lane tasks per wave, both NP = 2
-                // (the 16-lane NP = 4 / 8 kernels need > 256 registers: one wave
-                // per SIMD)
-                const int wide = npi == 3 && t.H <= 255 ? 0 : (npi == 2 ? 1 : -1);
-                if (lean && latmode && t.H <= 127 && dpx_fits(t)) {
-                    cl.push_back(t);
-                } else if (lean && wide >= 0 && ((ctx->opt.dp_wide >> wide) & 1)) {
-                    cw[wide].push_back(t);
-                } else if (lean && ((psplit >> npi) & 1) && np8 &&
-                           !(npi == 0 && DPR_PFIX && (t.P < dpr_pm(0, 0) || t.P > dpr_pm(0, 3) || !(t.P & 1)))) {
-                    // NP = 1 stride classes take exactly P = 11, 13, 15, 17 (PFIX
-                    // kernels); other strides stay in the generic lean class
-                    int pmi = 0;
-                    while (pmi < 3 && t.P > dpr_pm(npi, pmi))
-                        ++pmi;
-                    cp[npi][pmi].push_back(t);
-                } else if (t.H <= 31)
-                    cr[0][lean].push_back(t);
-                else if (t.H <= 63)
-                    cr[1][lean].push_back(t);
-                else if (t.H <= 127)
-                    cr[2][lean].push_back(t);
-                else if (t.H <= 255 && ctx->opt.dp_np8)
-                    cr[3][ctx->opt.dp_np8_lean ? lean : 0].push_back(t);
-                else if (t.H <= 2040) {
-                    c64.push_back(t);
-                    hmax64 = std::max(hmax64, t.H);
-                } else if (S.ncins == 0 && S.ncdel == 0 && ctx->opt.dp_mc && dpm_slices(t.H) <= DPM_TASK_SLICES &&
-                           (int64_t)t.klen * t.P * 8 < ((int64_t)1 << 31)) {
-                    cwm.push_back(t);   // k_dpm: across CUs, no codon moves (edit_distance's band)
-                    gm = std::max(gm, dpm_slices(t.H));
-                } else {
-                    cg.push_back(t);
-                    hmaxg = std::max(hmaxg, t.H);
-                }
-            }
-        }
-        // Few non-lean tasks of H <= 127 (the reference's codon DP: one long
-        // task per call) run as one latency-bound task per wave (k_dpx, round
-        // 5; round 4: k_dpr's general step in 64 lanes): such a launch cannot
-        // fill the GPU, so the step latency is the time
-        std::vector<DPTask> cx;
-        if (cr[0][0].size() + cr[1][0].size() + cr[2][0].size() <= (size_t)std::max(ctx->opt.dp_nl64, 0)) {
-            for (int a = 0; a <= 2; ++a) {
-                std::vector<DPTask> keep;
-                for (const DPTask &t : cr[a][0])
-                    (dpx_fits(t) ? cx : keep).push_back(t);
-                cr[a][0].swap(keep);
-            }
-        }
-        // A lean NP >= 2 class launched whole (no stride split) takes the
-        // smallest stride class that holds its widest task (RF_OPT_DP_PFIT,
-        // round 6): the blocked flush issues dpl_flush_stores(NP, PM) 16-B
-        // stores per lane and lanes past a block's end repeat its last pair,
-        // so at the class maximum PM = 33 the c4 NP = 2 class (P <= 19)
-        // rewrote 18 % of its bytes (0.7 GB per step, r05j PMC)
-        if (ctx->opt.dp_pfit)
-            for (int a = 1; a <= 3; ++a) {
-                if (cr[a][1].empty() || ((psplit >> a) & 1))
-                    continue;
-                int pmax = 0;
-                for (const DPTask &t : cr[a][1])
-                    pmax = std::max(pmax, t.P);
-                int pmi = 0;
-                while (pmi < 3 && pmax > dpr_pm(a, pmi))
-                    ++pmi;
-                cp[a][pmi].insert(cp[a][pmi].end(), cr[a][1].begin(), cr[a][1].end());
-                cr[a][1].clear();
-            }
-        auto by_len = [](const DPTask &x, const DPTask &y) { return x.klen > y.klen; };
-        std::vector<DPTask> &all = P.tasks;
-        all.clear();
-        for (auto &cc : cr)
-            for (auto &c : cc) {
-                std::stable_sort(c.begin(), c.end(), by_len);
-                all.insert(all.end(), c.begin(), c.end());
-            }
-        for (auto &cc : cp)
-            for (auto &c : cc) {
-                std::stable_sort(c.begin(), c.end(), by_len);
-                all.insert(all.end(), c.begin(), c.end());
-            }
-        for (auto &c : cw) {
-            std::stable_sort(c.begin(), c.end(), by_len);
-            all.insert(all.end(), c.begin(), c.end());
-        }
-        std::stable_sort(cx.begin(), cx.end(), by_len);
-        all.insert(all.end(), cx.begin(), cx.end());
-        std::stable_sort(cl.begin(), cl.end(), by_len);
-        all.insert(all.end(), cl.begin(), cl.end());
-        std::stable_sort(c64.begin(), c64.end(), by_len);
-        std::stable_sort(cg.begin(), cg.end(), by_len);
-        all.insert(all.end(), c64.begin(), c64.end());
-        all.insert(all.end(), cg.begin(), cg.end());
-        all.insert(all.end(), cwm.begin(), cwm.end());
-        if (int e = upload(ctx, ctx->scratch[8], all))
+        if (int e = realign_bands(ctx, njobs, slot, seq, tpl, bw, jf))
+            return e;
+        P.dp = realign_plan(ctx, njobs, slot, seq, tpl, bw, jf);
+        if (int e = upload(ctx, ctx->scratch[8], P.dp.tasks))
             return e;
         P.valid = true;
         P.gen = ctx->layout_gen;
@@ -7393,214 +7333,13 @@ static int realign_run(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const in
         P.seq.assign(seq, seq + njobs);
         P.tpl.assign(tpl, tpl + njobs);
         P.bw.assign(bw, bw + njobs);
-        for (int a = 0; a < 4; ++a)
-            for (int b = 0; b < 2; ++b)
-                P.nr[a][b] = cr[a][b].size();
-        for (int a = 0; a < 4; ++a)
-            for (int b = 0; b < 4; ++b)
-                P.nrp[a][b] = cp[a][b].size();
-        for (int a = 0; a < 2; ++a)
-            P.nw[a] = cw[a].size();
-        P.nx = cx.size();
-        P.nl = cl.size();
-        P.n64 = c64.size();
-        P.ng = cg.size();
-        P.nwm = cwm.size();
-        P.gm = gm;
-        P.hmax64 = hmax64;
-        P.hmaxg = hmaxg;
     }
     if (int e = ensure_buf(ctx, ctx->scratch[9], sizeof(double) * 2 * std::max(njobs, 1)))
         return e;
     double *d_out = (double *)ctx->scratch[9].p;
-    const DPTask *d_tasks = (const DPTask *)ctx->scratch[8].p;
-    const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
-    const double *d_tabs = (const double *)ctx->tab_arena.d;
-    double *d_bands = (double *)ctx->band_arena.d;
-    const double *d_lut = (const double *)ctx->codes.lut.p;
-
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    // Each kernel class is its own launch.  The classes are independent (disjoint
-    // bands), so the smaller ones run on side streams concurrently with the
-    // largest: the machine stays full through every launch's tail.
-    struct Launch {
-        int kind;      // 0..7 = k_dpr<1<<(kind>>1), kind&1>, 8 = k_dp<64,false>, 9 = k_dp<DPW_NT,..>, 11 = k_dpm,
-                       // 32 / 33 = lean wide tasks, 34 = k_dpx (few non-lean),
-                       // 35 = latency-mode lean,
-                       // 16 + 4 * npi + pmi = k_dpr<1 << npi, true, dpr_pm(npi, pmi)>
-        size_t at, n;
-    };
-    std::vector<Launch> launches;
-    {
-        size_t at = 0;
-        for (int a = 0; a < 4; ++a)
-            for (int b = 0; b < 2; ++b)
-                if (P.nr[a][b]) {
-                    launches.push_back({2 * a + b, at, P.nr[a][b]});
-                    at += P.nr[a][b];
-                }
-        for (int a = 0; a < 4; ++a)
-            for (int b = 0; b < 4; ++b)
-                if (P.nrp[a][b]) {
-                    launches.push_back({16 + 4 * a + b, at, P.nrp[a][b]});
-                    at += P.nrp[a][b];
-                }
-        for (int a = 0; a < 2; ++a)
-            if (P.nw[a]) {
-                launches.push_back({32 + a, at, P.nw[a]});
-                at += P.nw[a];
-            }
-        if (P.nx) {
-            launches.push_back({34, at, P.nx});
-            at += P.nx;
-        }
-        if (P.nl) {
-            launches.push_back({35, at, P.nl});
-            at += P.nl;
-        }
-        if (P.n64) {
-            launches.push_back({8, at, P.n64});
-            at += P.n64;
-        }
-        if (P.ng) {
-            launches.push_back({9, at, P.ng});
-            at += P.ng;
-        }
-        if (P.nwm)
-            launches.push_back({11, at, P.nwm});
-    }
-    // (Round 5: the lean 16-lane classes as ONE launch -- a kernel choosing the
-    // class body per block, dynamic LDS of the largest class -- was slower:
-    // c4 DP 9.86 against 8.75 ms, profiles/r05p_exp_dp_merge.jsonl; splitting
-    // the lean NP = 2 class by stride too: 9.61 against 8.72 ms,
-    // r05o_exp_dp_psplit.jsonl.  Concurrent launches pack workgroups of
-    // different LDS sizes on a CU; one launch holds every workgroup to the
-    // largest.)
-    if (int e = ensure_buf(ctx, ctx->scratch[7], 4 * (size_t)dpl_task_bytes(4)))  // lean padding-task sink
+    if (int e = launch_dp(ctx, P.dp, d_out))
         return e;
-    if (P.ng) {
-        if (int e = ensure_buf(ctx, ctx->scratch[10], P.ng * 4 * (size_t)(P.hmaxg + 6) * 8))
-            return e;
-    }
-    // The latency-bound classes (few long tasks: k_dpx, k_dp) go first, on
-    // the main stream: the others run beside them on the side streams, which
-    // may share hardware queues with each other (round 5: the reference's
-    // codon DP waited behind a read class on a shared queue, c3).  Otherwise
-    // the largest launch stays on the main stream.
-    std::stable_partition(launches.begin(), launches.end(),
-                          [](const Launch &L) { return L.kind == 34 || (L.kind >= 8 && L.kind <= 11); });
-    size_t big = 0;
-    const bool lat_first = !launches.empty() &&
-                           (launches[0].kind == 34 || (launches[0].kind >= 8 && launches[0].kind <= 11));
-    for (size_t i = 1; i < launches.size() && !lat_first; ++i)
-        if (launches[i].n > launches[big].n)
-            big = i;
-    const bool concurrent = launches.size() > 1 && ctx->opt.dp_streams;
-    // stream of each launch: -1 = the main stream, else a side stream.  (Round
-    // 5: balancing the classes over the main stream and two side streams by
-    // their stores, largest or smallest first, was slower at c4: 8.42-8.48
-    // against 8.25 ms, profiles/r05l_exp_dp_sched.jsonl.)
-    std::vector<int> lstream(launches.size(), -1);
-    if (concurrent) {
-        int nside = 0;
-        for (size_t i = 0; i < launches.size(); ++i)
-            if (i != big)
-                lstream[i] = nside++ % 3;
-    }
-    if (concurrent)
-        HIPCHK(ctx, hipEventRecord(ctx->fork, ctx->stream));
-    std::vector<int> used_side;
-    for (size_t i = 0; i < launches.size(); ++i) {
-        const Launch &L = launches[i];
-        hipStream_t st = ctx->stream;
-        if (lstream[i] >= 0) {
-            const int si = lstream[i];
-            st = ctx->side[si];
-            if (std::find(used_side.begin(), used_side.end(), si) == used_side.end()) {
-                HIPCHK(ctx, hipStreamWaitEvent(st, ctx->fork, 0));
-                used_side.push_back(si);
-            }
-        }
-        const int n = (int)L.n;
-        if (L.kind < 8) {
-            using KFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, double *, int *,
-                                 double *, const double *);
-            const KFn kr[8] = {k_dpr<1, false>, k_dpr<1, true>, k_dpr<2, false>, k_dpr<2, true>,
-                               k_dpr<4, false>, k_dpr<4, true>, k_dpr<8, false>, k_dpr<8, true>};
-            const int np = 1 << (L.kind >> 1);
-            const size_t lds = (L.kind & 1) ? 4 * (size_t)dpl_task_bytes(np) : 0;
-            hipLaunchKernelGGL(kr[L.kind], dim3((n + 3) / 4), dim3(64), lds, st, d_tasks + L.at, n, d_bases,
-                               d_tabs, d_bands, d_out, ctx->d_err, (double *)ctx->scratch[7].p, d_lut);
-        } else if (L.kind >= 16 && L.kind < 32) {
-            using KFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, double *, int *,
-                                 double *, const double *);
-#define KP(a, b) k_dpr<1 << (a), true, dpr_pm(a, b), 16, (a) == 0 && DPR_PFIX>
-            const KFn kp[16] = {KP(0, 0), KP(0, 1), KP(0, 2), KP(0, 3), KP(1, 0), KP(1, 1), KP(1, 2), KP(1, 3),
-                                KP(2, 0), KP(2, 1), KP(2, 2), KP(2, 3), KP(3, 0), KP(3, 1), KP(3, 2), KP(3, 3)};
-#undef KP
-            const int c = L.kind - 16, npi = c >> 2, pmi = c & 3;
-            hipLaunchKernelGGL(kp[c], dim3((n + 3) / 4), dim3(64), 4 * (size_t)dpl_task_bytes(1 << npi, dpr_pm(npi, pmi)),
-                               st, d_tasks + L.at, n, d_bases, d_tabs, d_bands, d_out, ctx->d_err,
-                               (double *)ctx->scratch[7].p, d_lut);
-        } else if (L.kind == 34) {
-            // few non-lean tasks (H <= 127): one latency-bound task per wave (k_dpx)
-            hipLaunchKernelGGL((k_dpx<true, true>), dim3(n), dim3(128), 0, st, d_tasks + L.at, n, d_bases, d_tabs,
-                               d_bands, d_out, ctx->d_err);
-        } else if (L.kind == 35) {
-            // latency mode: lean tasks of H <= 127, one latency-bound task per wave
-            hipLaunchKernelGGL((k_dpx<false, false>), dim3(n), dim3(128), 0, st, d_tasks + L.at, n, d_bases, d_tabs,
-                               d_bands, d_out, ctx->d_err);
-        } else if (L.kind >= 32) {
-            // task-width classes, both NP 2: 32 = 64 lanes (H <= 255), 33 = 32 lanes
-            // (H <= 127)
-            using KFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, double *, int *,
-                                 double *, const double *);
-            const KFn kw[2] = {k_dpr<2, true, dpl_pmax(2, 64), 64>, k_dpr<2, true, dpl_pmax(2, 32), 32>};
-            const int a = L.kind - 32, lpt = a == 0 ? 64 : 32, tpw = 64 / lpt;
-            hipLaunchKernelGGL(kw[a], dim3((n + tpw - 1) / tpw), dim3(64),
-                               (size_t)tpw * dpl_task_bytes(2, dpl_pmax(2, lpt), lpt), st, d_tasks + L.at, n,
-                               d_bases, d_tabs, d_bands, d_out, ctx->d_err, (double *)ctx->scratch[7].p, d_lut);
-        } else if (L.kind == 8) {
-            const int ld = P.hmax64 + 6;
-            hipLaunchKernelGGL((k_dp<64, false>), dim3(n), dim3(64), 4 * ld * 8, st, d_tasks + L.at, n, d_bases,
-                               d_tabs, d_bands, d_out, ctx->d_err, ld, nullptr);
-        } else if (L.kind == 11) {
-            // H > 2040 without codon moves across CUs (k_dpm): one workgroup per
-            // slice, a band's slices on one XCD; each band filled with the
-            // not-yet-stored pattern first (the slices poll their halo cells)
-            // At most DPM_XCD_SLICES slices per XCD per launch, launches in
-            // sequence on this stream: a launch's bands become resident in
-            // order, but two launches from different streams interleave, so
-            // each keeps to a share of an XCD (four such launches fit at once)
-            const int per = 8 * std::max(1, DPM_XCD_SLICES / P.gm);
-            for (int c0 = 0; c0 < n; c0 += per) {
-                const int nc = std::min(per, n - c0);
-                bool trim = false;
-                for (int i = c0; i < c0 + nc; ++i) {
-                    const DPTask &t = P.tasks[L.at + i];
-                    trim = trim || (t.flags & 4);
-                    HIPCHK(ctx, hipMemsetAsync(d_bands + t.band, 0xFF, (size_t)t.klen * t.P * 8, st));
-                }
-                hipLaunchKernelGGL(trim ? k_dpm<true> : k_dpm<false>, dim3((unsigned)(8 * ((nc + 7) / 8) * P.gm)),
-                                   dim3(64), 0, st, d_tasks + L.at + c0, nc, P.gm, d_bases, d_tabs, d_bands, d_out,
-                                   ctx->d_err);
-            }
-        } else {
-            // H > 2040: one task per DPW_NT-thread block, the ring in LDS when it fits
-            const int ld = P.hmaxg + 6;
-            if (P.hmaxg <= DPW_LDS_H)
-                hipLaunchKernelGGL((k_dp<DPW_NT, false, DPW_NT>), dim3(n), dim3(DPW_NT), 4 * ld * 8, st, d_tasks + L.at, n,
-                                   d_bases, d_tabs, d_bands, d_out, ctx->d_err, ld, nullptr);
-            else
-                hipLaunchKernelGGL((k_dp<DPW_NT, true, DPW_NT>), dim3(n), dim3(DPW_NT), 0, st, d_tasks + L.at, n, d_bases,
-                                   d_tabs, d_bands, d_out, ctx->d_err, ld, (double *)ctx->scratch[10].p);
-        }
-    }
-    for (int si : used_side) {
-        HIPCHK(ctx, hipEventRecord(ctx->join[si], ctx->side[si]));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->join[si], 0));
-    }
-    HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     // scores and the error flag into pinned memory, one synchronize
     const size_t ob = (out_score && njobs > 0) ? sizeof(double) * njobs : 0;
@@ -7615,7 +7354,91 @@ static int realign_run(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const in
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
     ctx->dp_ms = ms;
-    return check_err_landed(ctx);
+    if (int e = check_err_landed(ctx))
+        return e;
+    ctx->last_dp = P.dp.launches;
+    return 0;
+}
+
+// Kernel id, class indices, tasks, stream and launch geometry of a launch, as
+// the RF_DPL_FIELDS int32 of the C-ABI
+static void dp_launch_record(const DpLaunch &L, int32_t *out)
+{
+    const DpGeom g = dp_geom(L);
+    const int32_t rec[RF_DPL_FIELDS] = {(int32_t)L.k, L.npi, L.pmi, (int32_t)L.at, (int32_t)L.n,
+                                        L.stream, (int32_t)g.grid, (int32_t)g.block, (int32_t)g.lds};
+    std::copy(rec, rec + RF_DPL_FIELDS, out);
+}
+
+int rf_last_dp_launches(const rf_ctx *ctx, int32_t cap, int32_t *launches, int32_t *nlaunches)
+{
+    if (!ctx || !nlaunches || cap < 0 || (cap > 0 && !launches) || ctx->last_dp.size() > (size_t)cap)
+        return RF_ERR_ARG;
+    *nlaunches = (int32_t)ctx->last_dp.size();
+    for (size_t i = 0; i < ctx->last_dp.size(); ++i)
+        dp_launch_record(ctx->last_dp[i], launches + i * RF_DPL_FIELDS);
+    return 0;
+}
+
+int rf_host_dp_plan(int32_t njobs, const int32_t *n, const int32_t *m, const int32_t *bw, const int32_t *flags,
+                    const int32_t *ncins, const int32_t *ncdel, const uint8_t *finite, const int32_t *stride_a,
+                    const int32_t *stride_b, int32_t nopt, const int32_t *opt_key, const int32_t *opt_val,
+                    int32_t *task_job, int32_t *task_dir, int32_t *task_launch, int32_t *task_out,
+                    int32_t *ntasks, int32_t launch_cap, int32_t *launches, int32_t *nlaunches)
+{
+    if (njobs < 0 || nopt < 0 || launch_cap < 0 || !ntasks || !nlaunches || (launch_cap > 0 && !launches) ||
+        (nopt > 0 && (!opt_key || !opt_val)) ||
+        (njobs > 0 && (!n || !m || !bw || !flags || !ncins || !ncdel || !finite || !task_job || !task_dir ||
+                       !task_launch || !task_out)))
+        return RF_ERR_ARG;
+    DpOpts o;
+    for (int32_t i = 0; i < nopt; ++i) {
+        int *v = dp_opt(o, opt_key[i]);
+        if (!v)
+            return RF_ERR_ARG;
+        *v = opt_val[i];
+    }
+    for (int32_t k = 0; k < njobs; ++k) {
+        // H, K = H + 2 m and K P 8 in range: a stride holds its row pairs and is no wider than a band's
+        const int64_t H = 2 * (int64_t)bw[k] + std::abs((int64_t)n[k] - m[k]) + 1;
+        if (n[k] < 0 || m[k] < 0 || bw[k] < 1 || ncins[k] < 0 || ncdel[k] < 0 || !(flags[k] & (RF_FWD | RF_BWD)) ||
+            H + 2 * (int64_t)m[k] > INT32_MAX / 2)
+            return RF_ERR_ARG;
+        for (const int32_t *stride : {stride_a, stride_b})
+            if (stride && (stride[k] < (H + 1) / 2 || stride[k] > (H + 1) / 2 + 16))
+                return RF_ERR_ARG;
+    }
+    std::vector<DPTask> tasks;
+    std::vector<uint8_t> fin;
+    for_each_fill(njobs, flags, [&](int dir, int32_t k) {
+        SeqObj S;
+        TplObj T;
+        S.n = n[k];
+        S.ncins = ncins[k];
+        S.ncdel = ncdel[k];
+        T.m = m[k];
+        const int32_t *stride = dir == 0 ? stride_a : stride_b;
+        const int P = stride ? stride[k] : band_P(band_rows(S.n + 1, T.m + 1, bw[k]));
+        tasks.push_back(realign_task(S, T, bw[k], flags[k], dir, k, njobs, k, P));   // band: the job, for the report
+        fin.push_back(finite[k]);
+        return 0;
+    });
+    const DpPlan plan = dp_plan(tasks, fin, o);
+    if (plan.launches.size() > (size_t)launch_cap)
+        return RF_ERR_ARG;
+    *ntasks = (int32_t)plan.tasks.size();
+    *nlaunches = (int32_t)plan.launches.size();
+    for (size_t i = 0; i < plan.launches.size(); ++i) {
+        const DpLaunch &L = plan.launches[i];
+        dp_launch_record(L, launches + i * RF_DPL_FIELDS);
+        for (size_t j = L.at; j < L.at + L.n; ++j) {
+            task_job[j] = (int32_t)plan.tasks[j].band;
+            task_dir[j] = plan.tasks[j].flags & 1;
+            task_launch[j] = (int32_t)i;
+            task_out[j] = plan.tasks[j].out_idx;
+        }
+    }
+    return 0;
 }
 
 int rf_realign(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32_t *seq,
@@ -7669,65 +7492,6 @@ static int pair_check(rf_ctx *ctx, const std::string &fn, bool align, bool args_
     }
     return 0;
 }
-
-// The DPTask of one pair (no slot, no band); fl: 2 = skew, 4 = trim
-static DPTask pair_task(const SeqObj &S, const TplObj &T, int bw, int fl, int32_t out_idx)
-{
-    DPTask t{};
-    t.sb = S.bases.off;
-    t.tab = S.tabs.off / 8;
-    t.tb = T.bases.off;
-    t.n = S.n;
-    t.m = T.m;
-    t.bw = bw;
-    t.H = band_rows(S.n + 1, T.m + 1, bw);
-    t.c = std::max(T.m - S.n, 0) + bw;
-    t.ncins = S.ncins;
-    t.ncdel = S.ncdel;
-    t.flags = fl | (S.coded ? RF_TASK_CODED : 0);
-    t.out_idx = out_idx;
-    t.klen = t.H + 2 * t.m;
-    return t;
-}
-
-// The tasks of one launch set in their six width classes, like rf_realign's:
-// 0-2: H <= 31, 63, 127 as 16-lane tasks of 1, 2, 4 band-row pairs per lane;
-// 3: H <= PS_FAST_H as 64-lane tasks of 2 (k_dpr's wide class: 8 pairs per
-// lane in 16 lanes leave one wave per SIMD); 4, 5: the general tier in one
-// wave (H <= PS_GEN64_H) or DPW_NT threads.
-struct PairPlan {
-    std::vector<DPTask> cls[6], all;   // all: the classes in order, each longest first
-    size_t at[7];                      // class a is all[at[a] .. at[a + 1])
-    int hmax[2];                       // widest band of classes 4 and 5
-
-    void clear()
-    {
-        for (auto &c : cls)
-            c.clear();
-        hmax[0] = hmax[1] = 0;
-    }
-    void add(const DPTask &t, const SeqObj &S)
-    {
-        // fast tier: k_dpr's lean condition, bands that live in registers
-        const bool lean = S.ncins == 0 && S.ncdel == 0 && S.finite && !(t.flags & (2 | 4));
-        const int a = lean && t.H <= PS_FAST_H ? (t.H <= 31 ? 0 : t.H <= 63 ? 1 : t.H <= 127 ? 2 : 3)
-                                               : (t.H <= PS_GEN64_H ? 4 : 5);
-        cls[a].push_back(t);
-        if (a >= 4)
-            hmax[a - 4] = std::max(hmax[a - 4], t.H);
-    }
-    void finish()
-    {
-        all.clear();
-        for (int a = 0; a < 6; ++a) {
-            std::stable_sort(cls[a].begin(), cls[a].end(),
-                             [](const DPTask &x, const DPTask &y) { return x.klen > y.klen; });
-            at[a] = all.size();
-            all.insert(all.end(), cls[a].begin(), cls[a].end());
-        }
-        at[6] = all.size();
-    }
-};
 
 // The fill launches of a plan whose tasks are in scratch[28]: k_pa* into the
 // trace d_tr, k_ps* without one.
@@ -7792,7 +7556,7 @@ int rf_pair_scores(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_
         pl.clear();
         for (int64_t k = p0; k < p0 + cn; ++k) {
             const SeqObj &S = ctx->seqs[seq[k]];
-            pl.add(pair_task(S, ctx->tpls[tpl[k]], bw[k], fl, (int32_t)(k - p0)), S);
+            pl.add(pair_task(S, ctx->tpls[tpl[k]], bw[k], fl, (int32_t)(k - p0)), S.finite);
         }
         pl.finish();
         if (int e = upload(ctx, ctx->scratch[28], pl.all))
@@ -7908,7 +7672,7 @@ static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const i
             mv_total += S.n + T.m;
             ixoff[(size_t)(i - p0)] = ix_total;
             ix_total += T.m;
-            pl.add(t, S);
+            pl.add(t, S.finite);
         }
         pl.finish();
         const bool get_mv = moves != nullptr;    // the moves go to the caller

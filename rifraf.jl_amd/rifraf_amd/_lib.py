@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections import namedtuple
 from ctypes import POINTER, c_char_p, c_double, c_int, c_int8, c_int32, c_int64, c_uint8, c_void_p
 
 import numpy as np
@@ -79,6 +80,9 @@ _SIGNATURES = {
     "rf_last_backtrace_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rf_last_codon_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rf_last_codon_dense_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rf_host_dp_plan": (c_int, [c_int32] + [c_void_p] * 9 + [c_int32] + [c_void_p] * 6 + [POINTER(c_int32), c_int32,
+                                c_void_p, POINTER(c_int32)]),
+    "rf_last_dp_launches": (c_int, [c_void_p, c_int32, c_void_p, POINTER(c_int32)]),
     "rf_set_option": (c_int, [c_void_p, c_int32, c_int32]),
     "rf_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int32)]),
 }
@@ -95,6 +99,16 @@ OPTION_VALUES = {"score_mode": {"auto": 0, "fused": 1, "split": 2},
                  "score_kernel": {"auto": 0, "general": 1, "seg": 2, "ws": 3},
                  "pair_walk": {"auto": 0, "lane": 1, "wave": 2}}
 
+# kernel families of the DP launches (include/rifraf_hip.h RF_DPK_*, by value)
+DP_KERNELS = ("dpr", "dpr_lean", "dpr_lean_pm", "dpr_wide64", "dpr_wide32", "dpx_codon", "dpx_lean", "dp64",
+              "dpw_lds", "dpw_global", "dpm")
+# one launch record (RF_DPL_FIELDS int32): kernel is a DP_KERNELS name, stream -1 the context's stream
+DpLaunch = namedtuple("DpLaunch", "kernel npi pmi first count stream grid block lds")
+DP_LAUNCH_CAP = 64   # more than the planner's classes
+
+
+def dp_launch_records(buf, n):
+    return [DpLaunch(DP_KERNELS[int(r[0])], *(int(x) for x in r[1:])) for r in buf[:n]]
 
 
 class BatchParams(ctypes.Structure):
@@ -153,6 +167,31 @@ def load(path: str | None = None):
     if path is None:
         _lib = lib
     return lib
+
+
+def host_dp_plan(n, m, bw, flags, ncins=None, ncdel=None, finite=None, stride_a=None, stride_b=None, **opts):
+    """rf_host_dp_plan: rf_realign's launch planner for the jobs (n[k], m[k],
+    bw[k], flags[k]) on the host alone (no context, no GPU).  ncins / ncdel
+    default to 0 and finite to True (lean reads); stride_a / stride_b to the
+    unpadded stride; opts are OPTIONS names (dp_lat=0, ...).  Returns (job,
+    direction, launch index, score slot) per task in device order and the
+    DpLaunch records in issue order."""
+    nj = len(n)
+    i32 = lambda a, fill: np.ascontiguousarray(np.full(nj, fill) if a is None else a, np.int32)
+    flags = np.full(nj, flags) if np.isscalar(flags) else flags
+    arrs = [i32(n, 0), i32(m, 0), i32(bw, 0), i32(flags, 0), i32(ncins, 0), i32(ncdel, 0),
+            np.ascontiguousarray(np.ones(nj) if finite is None else finite, np.uint8),
+            None if stride_a is None else i32(stride_a, 0), None if stride_b is None else i32(stride_b, 0)]
+    keys = np.array([OPTIONS[k] for k in opts], np.int32)
+    vals = np.array([opts[k] for k in opts], np.int32)
+    out = [np.zeros(max(2 * nj, 1), np.int32) for _ in range(4)]
+    rec = np.zeros((DP_LAUNCH_CAP, len(DpLaunch._fields)), np.int32)
+    nt, nl = c_int32(), c_int32()
+    rc = load().rf_host_dp_plan(nj, *(ptr(a) for a in arrs), len(keys), ptr(keys), ptr(vals),
+                                *(ptr(a) for a in out), ctypes.byref(nt), DP_LAUNCH_CAP, ptr(rec), ctypes.byref(nl))
+    if rc != 0:
+        raise ValueError(f"rf_host_dp_plan: bad arguments ({rc})")
+    return (*(a[:nt.value] for a in out), dp_launch_records(rec, nl.value))
 
 
 def ptr(a: np.ndarray | None):

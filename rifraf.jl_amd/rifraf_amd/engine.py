@@ -739,6 +739,14 @@ class Engine:
         self._check(self.lib.rf_last_codon_dense_ms(self.ctx, byref(v)))
         return v.value
 
+    def last_dp_launches(self):
+        """The launches of the last successful realign, in issue order
+        (_lib.DpLaunch records: which kernel family ran which tasks)."""
+        rec = np.zeros((_lib.DP_LAUNCH_CAP, len(_lib.DpLaunch._fields)), np.int32)
+        n = c_int32()
+        self._check(self.lib.rf_last_dp_launches(self.ctx, _lib.DP_LAUNCH_CAP, ptr(rec), byref(n)))
+        return _lib.dp_launch_records(rec, n.value)
+
     def last_timing(self):
         a, b, c = c_double(), c_double(), c_double()
         self._check(self.lib.rf_last_timing(self.ctx, byref(a), byref(b), byref(c)))

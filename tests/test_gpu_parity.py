@@ -98,6 +98,14 @@ def test_dp_bands_bitexact(engine, opts, L, err, bw, jit, codon, nl64, pad, lat)
         assert nerr[0] == oracle.count_errors(ref_moves, t, s.seq)
 
 
+def launched_tasks(engine):
+    """{(kernel family, npi): tasks} of the last rf_realign (Engine.last_dp_launches)."""
+    got = {}
+    for L in engine.last_dp_launches():
+        got[(L.kernel, L.npi)] = got.get((L.kernel, L.npi), 0) + L.count
+    return got
+
+
 def _check_bands(engine, t, seqs, bws):
     n = len(seqs)
     engine.set_sequences(0, seqs)
@@ -176,11 +184,30 @@ def test_dp_wide_task_classes_long_reads(engine, opts, dp_wide, lat):
             lp = np.concatenate([lp, np.full(len(extra), -1.2)])
         seqs.append(RifrafSequence(s, lp, bw, SEQ_SCORES))
         bws.append(bw)
+    # the class of each (lean) task by its H; the two reads of H <= 31 are too
+    # few for the NP = 1 stride split, the NP >= 2 classes refit to a stride class
+    def family(h):
+        if lat and h <= 127:
+            return ("dpx_lean", 0)
+        if 64 <= h <= 127 and dp_wide & 2:
+            return ("dpr_wide32", 0)
+        if 128 <= h <= 255 and dp_wide & 1:
+            return ("dpr_wide64", 0)
+        if h <= 31:
+            return ("dpr_lean", 0)
+        return ("dpr_lean_pm", 1 + (h > 63) + (h > 127)) if h <= 255 else ("dp64", 0)
+    per_direction = {}
+    for s, bw in zip(seqs, bws):
+        f = family(2 * bw + abs(len(s) - len(t)) + 1)
+        per_direction[f] = per_direction.get(f, 0) + 1
     _check_bands(engine, t, seqs, bws)
+    assert launched_tasks(engine) == {f: 2 * c for f, c in per_direction.items()}
     # the same jobs split over two calls (forward alone, then backward alone)
     n = len(seqs)
     engine.realign(np.arange(n), np.arange(n), 0, bws, RF_FWD)
+    assert launched_tasks(engine) == per_direction
     engine.realign(np.arange(n), np.arange(n), 0, bws, RF_BWD)
+    assert launched_tasks(engine) == per_direction
     for k in (0, 7, 12, n - 1):
         A_exp, _ = oracle.forward(t, seqs[k], bandwidth=bws[k])
         assert_band_equal(engine.download_band(k, RF_BAND_A), A_exp, len(seqs[k]) + 1, len(t) + 1, bws[k])

@@ -36,7 +36,7 @@ from rifraf_amd.engine import RF_BAND_A, RF_BAND_B, RF_BWD, RF_FWD, RF_SKEW, RF_
 from rifraf_amd.errormodel import phred_to_log_p
 from rifraf_amd.model import _add_base_distributions
 from rifraf_amd.sample import sample_from_template
-from test_gpu_parity import assert_band_equal
+from test_gpu_parity import assert_band_equal, launched_tasks
 from test_pair_scores import bits_equal, final_cell
 from test_score_dense_ref import dense_mask, same, table
 from test_sharded import QV_RTOL, assert_same_run, summary
@@ -69,6 +69,12 @@ H_RANGE = {"dpx31": (1, 31), "dpx63": (32, 63), "dpx127": (64, 127), "dpr1": (1,
            "dpr4": (64, 127), "dpr8": (128, 255), "dp64": (128, 255), "dpring": (256, 300), "dpm": (2041, 2047),
            "dpwide": (2041, 2047)}
 WIDE = ("dpm", "dpwide")
+# tier -> the general kernel family (Engine.last_dp_launches: kernel, npi) that
+# its non-lean fills run in: the non-finite reads', and every skew / trim fill
+GENERAL_KERNELS = {"dpr", "dpx_codon", "dp64", "dpw_lds", "dpw_global", "dpm"}
+TIER_KERNEL = {"dpx31": ("dpx_codon", 0), "dpx63": ("dpx_codon", 0), "dpx127": ("dpx_codon", 0),
+               "dpr1": ("dpr", 0), "dpr2": ("dpr", 1), "dpr4": ("dpr", 2), "dpr8": ("dpr", 3),
+               "dp64": ("dp64", 0), "dpring": ("dp64", 0), "dpm": ("dpm", 0), "dpwide": ("dpw_lds", 0)}
 KINDS = ("phred0", "phred0-codes", "holes", "holes-codon")
 FLAG_SETS = (RF_FWD | RF_BWD, RF_FWD | RF_SKEW, RF_FWD | RF_TRIM, RF_FWD | RF_SKEW | RF_TRIM)
 
@@ -294,6 +300,17 @@ def set_tier(opts, tier, pad=None):
         opts("band_pad", pad)
 
 
+def assert_tier_ran(engine, tier, general, lean):
+    """The last rf_realign ran its `general` non-lean tasks in the tier's
+    kernel and nowhere else, and its `lean` tasks (finite reads, no skew /
+    trim) in lean kernels; above H 255 the tier's kernel takes those too."""
+    got = launched_tasks(engine)
+    wide = H_RANGE[tier][1] > 255
+    non_lean = {k: c for k, c in got.items() if k[0] in GENERAL_KERNELS}
+    assert non_lean == {TIER_KERNEL[tier]: general + (lean if wide else 0)}, (tier, got)
+    assert sum(got.values()) - sum(non_lean.values()) == (0 if wide else lean), (tier, got)
+
+
 def proposals_mask(t, walks, seqs):
     exp = np.zeros((len(t) + 1, 9), np.uint8)
     for w, s in zip(walks, seqs):
@@ -336,6 +353,9 @@ def test_general_tier_parity(engine, opts, tier, kind, pad):
     sl = np.arange(n)
     for flags in FLAG_SETS:
         scores = engine.realign(sl, sl, 0, [c.bw] * n, flags)
+        # three non-finite and three finite reads: lean only without skew / trim
+        nf = len(c.nonfinite)
+        assert_tier_ran(engine, tier, *((2 * nf, 2 * (n - nf)) if flags == RF_FWD | RF_BWD else (n, 0)))
         walks = []
         for k, r in enumerate(c.reads):
             A, w, ne = c.fwd(k, flags)
@@ -548,11 +568,14 @@ def test_raise_and_state_after(engine, opts, tier, direction):
     # every slot current first: the good jobs, the replacement in the wall's slot, the slot left alone
     slots = np.array([0, 1, 2, 3], np.int32)
     engine.realign(slots, [0, w.repl, 2, w.other], 0, [bw] * 4, RF_FWD | RF_BWD)
+    assert_tier_ran(engine, tier, 2, 6)       # the holes read's two fills in the tier's kernel
+    ran = engine.last_dp_launches()
     fails = raises(lambda: (oracle.forward if direction == "fwd" else oracle.backward)(t, w.reads[w.wall]))
     assert fails
     # 1. the raise
     with pytest.raises(RifrafError, match=INVALID):
         engine.realign([0, 1, 2], [0, w.wall, 2], 0, [bw] * 3, flag)
+    assert engine.last_dp_launches() == ran   # the launches of the last successful fill
     # 2. a failed fill leaves nothing readable
     props = all_proposals_arrays(t)
     good = np.array(w.good, np.int32)

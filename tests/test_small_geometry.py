@@ -40,6 +40,7 @@ from _util import REF_SCORES, SEQ_SCORES, all_proposals_arrays, dense_slot, inba
 from rifraf_amd import RifrafSequence
 from rifraf_amd.align import moves_to_proposals_np
 from rifraf_amd.engine import RF_BAND_A, RF_BAND_B, RF_BWD, RF_FWD, RF_SKEW, RF_TRIM
+from test_gpu_parity import launched_tasks
 from test_sharded import QV_ATOL, QV_RTOL
 
 pytestmark = pytest.mark.gpu
@@ -344,6 +345,24 @@ LEAN = ("seq", "tie_seq")
 DP_OPTS = {"tp": ("dp_lat", 0), "lat": ("dp_lat", 2048), "nl16": ("dp_nl64", 0), "nl64": ("dp_nl64", 1024)}
 
 
+# the kernel families (Engine.last_dp_launches) a leg's tasks run in
+LEG_KERNELS = {"tp": {"dpr_lean", "dpr_lean_pm"}, "lat": {"dpx_lean"}, "nl16": {"dpr"}, "nl64": {"dpx_codon"}}
+LEAN_KERNELS = {"dpr_lean", "dpr_lean_pm", "dpr_wide64", "dpr_wide32", "dpx_lean"}
+
+
+def check_leg(engine, dp, ntasks):
+    """The last rf_realign ran its lean ("tp", "lat") or its non-lean ("nl16",
+    "nl64") tasks in the leg's kernel family and in no other, with NP = 1
+    (every H here is <= 22); ntasks: the call held only such tasks, this many
+    (None: a call of lean and non-lean tasks, `seq0`)."""
+    ran = launched_tasks(engine)
+    assert {npi for _, npi in ran} == {0}, ran
+    side = {k for k, _ in ran if (k in LEAN_KERNELS) == (dp in ("tp", "lat"))}
+    assert side and side <= LEG_KERNELS[dp], (dp, ran)
+    if ntasks is not None:
+        assert {k for k, _ in ran} == side and sum(ran.values()) == ntasks, (dp, ran)
+
+
 def dp_modes(names):
     """(class, launch class, band_pad) for the plain forward + backward fill."""
     legs = {name: ("tp", "lat") if name in LEAN else ("nl16", "nl64") for name in names}
@@ -374,6 +393,7 @@ def test_sweep_bands(engine, opts, name, dp, pad):
     opts(*DP_OPTS[dp])
     opts("band_pad", pad)
     scores = upload(engine, c, RF_FWD | RF_BWD, per_direction=dp == "nl64")
+    check_leg(engine, dp, None if name == "seq0" else NA if dp == "nl64" else 2 * NA)
     check_A(engine, c, scores, c.fills())
     for k, ((m, n, bw), B) in enumerate(zip(SHAPES, c.backward())):
         got = engine.download_band(k, RF_BAND_B).data
@@ -392,6 +412,7 @@ def test_sweep_skew_trim(engine, opts, name, dp, flags):
     opts(*DP_OPTS[dp])
     skew, trim = bool(flags & RF_SKEW), bool(flags & RF_TRIM)
     scores = upload(engine, c, RF_FWD | flags)
+    check_leg(engine, dp, NA)
     check_A(engine, c, scores, c.fills(skew, trim))
     check_walks(engine, c, c.walks(skew, trim))
 
