@@ -685,6 +685,39 @@ int rf_host_dp_plan(int32_t njobs, const int32_t *n, const int32_t *m, const int
  * rf_realign_jobs, in issue order; RF_ERR_ARG when there are more than cap. */
 int rf_last_dp_launches(const rf_ctx *ctx, int32_t cap, int32_t *launches, int32_t *nlaunches);
 
+/* The scoring planner made observable (DESIGN.md §4 "Scoring planner"), for
+ * the same reason: the three scorers, fused and split mode and both item
+ * widths compute the same bits.  No reference counterpart. */
+#define RF_SCK_GENERAL      1   /* k_score: any tables, 64 columns per item             */
+#define RF_SCK_SEG          2   /* k_score_segl: finite tables, wide bands, 64 columns  */
+#define RF_SCK_WS           3   /* k_score_ws: finite tables, 256 columns per item      */
+#define RF_SCL_FIELDS       4
+/* The scorer launch of the context's last successful rf_score, rf_score_dense,
+ * rf_score_dense_dev, rf_score_dense_ref or rf_qv_probs, as RF_SCL_FIELDS
+ * int32: kernel family (RF_SCK_*), split mode (0 / 1), work items, grid.y (0
+ * items: nothing was launched, grid.y 0). */
+int rf_last_score_launch(const rf_ctx *ctx, int32_t *launch);
+/* The scoring planner on the host alone: no context, no GPU.  Read r has
+ * n[r] bases against a template of m[r] at bandwidth bw[r] with band row
+ * stride stride[r] (stride NULL: the unpadded stride of the band's H) and
+ * finite[r] tables; group g holds reads [read_off[g], read_off[g + 1]), all
+ * of one m.  Options: nopt pairs of RF_OPT_SCORE_MODE, RF_OPT_SCORE_KERNEL or
+ * RF_OPT_LEAN_LDS_KB, the rest at their defaults.  per_seq: rf_score with
+ * per-read output.  empty_ok: a group without reads is legal and gets no
+ * items and no span (rf_score), else RF_ERR_ARG (the dense calls).  Outputs:
+ * pick[3] = kernel family (RF_SCK_*), LDS doubles, columns per item;
+ * split[2] = split mode as rf_score decides it (from the count of 64-column
+ * items, with per_seq) and as the dense calls do (from the count of items);
+ * the items as (group, first column) pairs, room for item_cap; per group
+ * dense_off (ngroups + 1 values, the last the total) and split_off (doubles).
+ * RF_ERR_ARG also for bad arguments as rf_host_dp_plan's, reads of several m
+ * in a group, an unknown key and more items than item_cap. */
+int rf_host_score_plan(int32_t nreads, const int32_t *n, const int32_t *m, const int32_t *bw, const int32_t *stride,
+                       const uint8_t *finite, int32_t ngroups, const int32_t *read_off, int32_t nopt,
+                       const int32_t *opt_key, const int32_t *opt_val, int32_t per_seq, int32_t empty_ok,
+                       int32_t *pick, int32_t *split, int32_t item_cap, int32_t *items, int32_t *nitems,
+                       int64_t *dense_off, int64_t *split_off);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,7 @@
 
 #include "../../include/rifraf_hip.h"
 #include "rifraf_dp_plan.h"
+#include "rifraf_score_plan.h"
 
 #define RF_INF (__builtin_inf())
 
@@ -103,28 +104,7 @@ constexpr int RF_CODES = 1 << 16;   // entries of the row codes' dictionary (DPT
 // doubles from a read's table start to its row-code records
 __host__ __device__ inline int64_t row_code_off(int64_t n, int64_t nci, int64_t ncd) { return 4 * n + 1 + nci + ncd; }
 
-// One batch read of a scoring group.
-struct alignas(16) ScoreRead {
-    int64_t A, B;     // band offsets (doubles)
-    int64_t sb, tab;  // sequence bases / tables
-    int32_t n, bw, H, c;
-    int32_t vb;       // v_off + bw
-    int32_t P, K;
-    int32_t flags;    // SR_CODED: row-code records follow the tables (no codon tables)
-};
-constexpr int SR_CODED = 1;
-
-struct alignas(16) ScoreGroup {
-    int64_t tb;         // template bases
-    int64_t dense_off;  // totals [m+1][9]
-    int64_t split_off;  // per-read partials base (split mode)
-    int32_t r0, r1;     // reads [r0, r1) in the ScoreRead list
-    int32_t m, pad;
-};
-
-struct alignas(8) WorkItem {
-    int32_t group, p0;
-};
+// ScoreRead, ScoreGroup, WorkItem: rifraf_score_plan.h
 
 struct alignas(16) CodonTask {
     int64_t A, B, sb, tab, tb;
@@ -2791,8 +2771,6 @@ k_dpx(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ 
 // fits (the common narrow band), otherwise read in place.
 // ---------------------------------------------------------------------
 
-constexpr int SCORE_C = 64;    // positions per work item
-
 // Accessor of a band window: rows [k0, ...) of a kappa-major band.
 struct BandWin {
     const double *base;
@@ -3065,14 +3043,6 @@ __global__ void k_reduce(const ScoreGroup *__restrict__ groups, int ngroups,
 // that consecutive chunks of one group run on the same XCD (shared L2 for the
 // H overlapping kappa rows of neighbouring chunks).
 // ---------------------------------------------------------------------
-
-// doubles of LDS a sub-pass over L lanes needs for a read of band height H
-
-__host__ __device__ inline int lean_need(int L, int H, int P)
-{
-    const int win = ((2 * L + H + 1) * P + 3) & ~1;   // kappa rows + alignment shift, even
-    return 2 * win + (L + H + 1) * 6;
-}
 
 // v_max_f64 without the NaN-quieting self-max hipcc adds in front of every
 // fmax whose operand is a loop-carried value; the operands here are never NaN
@@ -5487,16 +5457,6 @@ struct Slot {
     Band a, b;
 };
 
-// Choice of dense scorer for one launch.
-struct ScorePick {
-    bool lean = false;
-    bool seg = false;   // k_score_segl: wide bands (window too large for LDS), finite tables
-    int lds = 0;    // lean: doubles of dynamic LDS; general: doubles per staged band
-    int q() const { return 256; }   // k_score_ws chain columns per work item
-    // columns per work item of the chosen scorer (k_score: 64)
-    int cols() const { return lean ? q() : 64; }
-};
-
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
@@ -5633,11 +5593,9 @@ struct CodeDict {
 // Tuning options (rf_set_option keys, include/rifraf_hip.h).  Every option
 // selects between bit-identical code paths; defaults come from the RIFRAF_*
 // environment once, at rf_create, and never from a hot path.
-// The DP launch planner's options are DpOpts (rifraf_dp_plan.h).
-struct Opts : DpOpts {
-    int score_mode = 0;     // RF_OPT_SCORE_MODE: 0 auto, 1 fused, 2 split
-    int score_kernel = 0;   // RF_OPT_SCORE_KERNEL: 0 auto, 1 general, 2 seg, 3 ws (k_score_ws when it fits)
-    int lean_lds_kb = 0;    // RF_OPT_LEAN_LDS_KB: k_score_ws LDS budget (0 = default 160 KB)
+// The launch planners' options are DpOpts (rifraf_dp_plan.h) and ScoreOpts
+// (rifraf_score_plan.h).
+struct Opts : DpOpts, ScoreOpts {
     int band_pad_h = 64;    // RF_OPT_BAND_PAD: a realign call whose widest band has H >= this gets
                             // 128-B-line rows for all its bands (0: never, 1: always)
     int bt_win_kb = 16;     // RF_OPT_BT_WIN_KB: k_bt_win A window (16 or 32 KB of LDS)
@@ -5730,18 +5688,13 @@ struct rf_ctx {
         uint64_t gen = 0;
         uint64_t val_epoch = 0;   // state_epoch at which the slot list was last validated
         std::vector<int32_t> slot_off, slots;
-        size_t nitems = 0;
-        int max_reads = 0, ngroups = 0;
-        int64_t dense_total = 0, split_total = 0;
-        ScorePick pick;
+        int ngroups = 0;
         uint64_t opt_gen = 0;
-        // host copies of the uploaded descriptors: alive until the uploads
-        // they source have completed (hipMemcpyAsync from pageable memory)
-        std::vector<WorkItem> items;
-        std::vector<ScoreGroup> groups;
-        std::vector<ScoreRead> reads;
-        std::vector<int64_t> gstart;
+        // host copy of the uploaded descriptors: alive until the uploads it
+        // sources have completed (hipMemcpyAsync from pageable memory)
+        ScorePlan plan;
     } dplan;
+    int32_t last_score[RF_SCL_FIELDS] = {};   // the last successful scoring call's launch (rf_last_score_launch)
 };
 
 namespace {
@@ -6063,23 +6016,6 @@ int check_err(rf_ctx *ctx)
     return check_err_hdn(ctx);
 }
 
-// k_score stages the kappa rows of a work item through LDS; size the
-// per-band buffer for the 90th-percentile window (at most 24 KB per band,
-// two bands per single-wave block), larger windows read in place.
-int score_lds_elems(const std::vector<ScoreRead> &reads)
-{
-    if (reads.empty())
-        return 0;
-    std::vector<int> w;
-    w.reserve(reads.size());
-    for (const auto &R : reads)
-        w.push_back((2 * SCORE_C + R.H) * R.P);
-    const size_t q = (w.size() * 9) / 10;
-    std::nth_element(w.begin(), w.begin() + q, w.end());
-    return std::min(w[q], 24 * 1024 / 8);
-}
-
-
 int env_int(const char *name, int dflt)
 {
     const char *v = std::getenv(name);
@@ -6114,59 +6050,9 @@ void load_env_opts(Opts &o)
     o.pair_walk = env_int("RIFRAF_PAIR_WALK", o.pair_walk);
 }
 
-ScorePick pick_scorer(const Opts &o, const std::vector<ScoreRead> &reads, bool all_finite)
-{
-    ScorePick p;
-    const bool force_general = o.score_kernel == 1;
-    const bool force_seg = o.score_kernel == 2;
-    if (all_finite && !force_general && !force_seg && !reads.empty()) {
-        int need1 = 0;
-        for (const auto &R : reads)
-            need1 = std::max(need1, lean_need(1, R.H, R.P));
-        // k_score_ws: 256 chain lanes + 256 loader lanes, one workgroup per CU
-        // (measured at c4: 128 chain lanes (two workgroups per CU) +14 %,
-        // 320 / 384 chain lanes +50 % scoring time)
-        const int lds = std::max((o.lean_lds_kb > 0 ? o.lean_lds_kb : 160) * 1024 / 8, need1);
-        // Round 5: a read whose 256-column window exceeds LDS runs in sub-
-        // windows over a half (or less) of the chain lanes, the others idle;
-        // when such reads hold most of the launch's cells, the segment scorer
-        // (LDS independent of H) is faster -- configs[2]'s doubled bands
-        // (bw 18, H ~ 37-51): 1.50 -> 0.65 ms per dense pass,
-        // profiles/r05q_c3_score_kernel.jsonl
-        double wide = 0.0, all = 0.0;
-        for (const auto &R : reads) {
-            const double w = (double)R.n * R.H;
-            all += w;
-            if (lean_need(256, R.H, R.P) > lds)
-                wide += w;
-        }
-        if (lds <= 160 * 1024 / 8 && (o.score_kernel == 3 || !(2.0 * wide > all))) {
-            p.lean = true;
-            p.lds = lds;
-            return p;
-        }
-    }
-    // wide bands: the row-segment scorer (same chains, H-independent LDS)
-    if (all_finite && !force_general && !reads.empty()) {
-        p.seg = true;
-        return p;
-    }
-    p.lds = score_lds_elems(reads);
-    return p;
-}
-
-// work items: chunks of q consecutive positions of every group
-std::vector<WorkItem> make_items(const std::vector<ScoreGroup> &groups, int q)
-{
-    std::vector<WorkItem> items;
-    for (int g = 0; g < (int)groups.size(); ++g)
-        if (groups[g].r1 > groups[g].r0)
-            for (int p0 = 0; p0 <= groups[g].m; p0 += q)
-                items.push_back({g, p0});
-    return items;
-}
-
-void launch_scorer(rf_ctx *ctx, const ScorePick &pk, unsigned nitems, unsigned gy, const WorkItem *items,
+// Launches the picked scorer over nitems items (split: partials of gy reads,
+// rchunk of them per workgroup); returns the launch's grid.y
+unsigned launch_scorer(rf_ctx *ctx, const ScorePick &pk, unsigned nitems, unsigned gy, const WorkItem *items,
                    const ScoreGroup *groups, const ScoreRead *reads, double *dense, double *split)
 {
     const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
@@ -6198,6 +6084,104 @@ void launch_scorer(rf_ctx *ctx, const ScorePick &pk, unsigned nitems, unsigned g
                            groups, reads, d_bases, d_tabs, d_bands, dense, split, sm, pk.lds,
                            WS_CODES ? (const double *)ctx->codes.lut.p : nullptr, rchunk);
     }
+    return grid.y;
+}
+
+void note_score_launch(rf_ctx *ctx, const ScorePick &pk, bool split, size_t nitems, unsigned gy)
+{
+    const int32_t rec[RF_SCL_FIELDS] = {pk.family(), split ? 1 : 0, (int32_t)nitems, (int32_t)gy};
+    std::copy(rec, rec + RF_SCL_FIELDS, ctx->last_score);
+}
+
+// Why slot s cannot be scored (NULL: it can): A and B both filled, neither
+// fill failed, both for one alignment at one row stride, and neither the
+// template nor the sequence replaced since
+const char *score_band_fault(const rf_ctx *ctx, int32_t s)
+{
+    if (s < 0 || s >= (int32_t)ctx->slots.size())
+        return "unknown slot";
+    const Slot &S = ctx->slots[s];
+    if (!S.a.valid || !S.b.valid)
+        return "slot has no A/B bands";
+    if (S.a.failed || S.b.failed)
+        return FILL_FAILED;
+    if (S.a.seq != S.b.seq || S.a.tpl != S.b.tpl || S.a.bw != S.b.bw || S.a.tplver != S.b.tplver ||
+        S.a.m != S.b.m || S.a.seqver != S.b.seqver || S.a.n != S.b.n)
+        return "A and B bands were computed for different alignments";
+    if (S.a.P != S.b.P)
+        return "A and B bands have different row strides";
+    if (ctx->tpls[S.a.tpl].version != S.a.tplver)
+        return "template changed since the bands were computed";
+    if (seq_stale(ctx, S.a))
+        return "sequence changed since the bands were computed";
+    return nullptr;
+}
+
+// Why the A band of slot s cannot be walked (NULL: it can): the calls that
+// read A alone (backtraces, alignment sums)
+const char *a_band_fault(const rf_ctx *ctx, int32_t s)
+{
+    if (s < 0 || s >= (int32_t)ctx->slots.size() || !ctx->slots[s].a.valid)
+        return "slot has no A band";
+    const Band &b = ctx->slots[s].a;
+    if (b.failed)
+        return FILL_FAILED;
+    if (seq_stale(ctx, b))
+        return "sequence changed since the bands were computed";
+    if (ctx->tpls[b.tpl].version != b.tplver)
+        return "template changed since the A band was computed";
+    return nullptr;
+}
+
+// The fields that CodonTask, CodonDenseGroup and BTTask share, from a checked
+// slot's bands and the sequence and template they were filled for
+template <class D>
+D slot_desc(const rf_ctx *ctx, int32_t s)
+{
+    const Band &A = ctx->slots[s].a;
+    const SeqObj &S = ctx->seqs[A.seq];
+    D t{};
+    t.A = A.r.off / 8;
+    if constexpr (!std::is_same_v<D, BTTask>)
+        t.B = ctx->slots[s].b.r.off / 8;
+    t.sb = S.bases.off;
+    t.tab = S.tabs.off / 8;
+    t.tb = ctx->tpls[A.tpl].bases.off;
+    t.n = A.n;
+    t.m = A.m;
+    t.bw = A.bw;
+    t.H = A.H;
+    t.ncins = S.ncins;
+    t.ncdel = S.ncdel;
+    t.P = A.P;
+    return t;
+}
+
+// The batch slots [k0, k1) of one scoring group, checked in slot order (an
+// unknown slot is `unknown`, RF_ERR_STATE in rf_score and RF_ERR_ARG in the
+// dense calls); tpl: the group's template, -1 before its first slot.  Appends
+// the planner's records of the slots to `in` unless that is NULL.
+int score_group_slots(rf_ctx *ctx, const char *fn, int unknown, const int32_t *slots, int32_t k0, int32_t k1,
+                      int32_t &tpl, std::vector<ScoreReadIn> *in)
+{
+    for (int32_t k = k0; k < k1; ++k) {
+        const int32_t s = slots[k];
+        if (s < 0 || s >= (int32_t)ctx->slots.size())
+            return fail(ctx, unknown, std::string(fn) + ": unknown slot");
+        if (const char *why = score_band_fault(ctx, s))
+            return fail(ctx, RF_ERR_STATE, std::string(fn) + ": " + why);
+        const Band &A = ctx->slots[s].a;
+        const SeqObj &S = ctx->seqs[A.seq];
+        if (S.ncins > 0 || S.ncdel > 0)
+            return fail(ctx, RF_ERR_ARG, "error model cannot allow codon indels");
+        if (tpl >= 0 && A.tpl != tpl)
+            return fail(ctx, RF_ERR_ARG, std::string(fn) + ": batch slots use different templates");
+        tpl = A.tpl;
+        if (in)
+            in->push_back({A.r.off, ctx->slots[s].b.r.off, S.bases.off, S.tabs.off, A.n, A.m, A.bw, A.H, A.P,
+                           S.finite, S.coded});
+    }
+    return 0;
 }
 
 }  // namespace
@@ -8006,41 +7990,21 @@ static void note_bt_ms(rf_ctx *ctx)
 }
 
 // Backtrace descriptors of `nslots` slots (moves slot k at offs[k], n+m bytes)
-// and the scratch buffers for moves and counts.
-static int build_bt_tasks(rf_ctx *ctx, int32_t nslots, const int32_t *slot, std::vector<BTTask> &tasks,
-                          std::vector<int64_t> &offs)
+// and the scratch buffers for moves and counts, for the call `fn`.
+static int build_bt_tasks(rf_ctx *ctx, const char *fn, int32_t nslots, const int32_t *slot,
+                          std::vector<BTTask> &tasks, std::vector<int64_t> &offs)
 {
     tasks.assign(nslots, BTTask{});
     offs.assign(nslots, 0);
     int64_t total = 0;
     for (int32_t k = 0; k < nslots; ++k) {
-        if (slot[k] < 0 || slot[k] >= (int32_t)ctx->slots.size() || !ctx->slots[slot[k]].a.valid)
-            return fail(ctx, RF_ERR_STATE, "rf_backtrace: slot has no A band");
+        if (const char *why = a_band_fault(ctx, slot[k]))
+            return fail(ctx, RF_ERR_STATE, std::string(fn) + ": " + why);
         const Band &b = ctx->slots[slot[k]].a;
-        if (b.failed)
-            return fail(ctx, RF_ERR_STATE, std::string("rf_backtrace: ") + FILL_FAILED);
-        if (seq_stale(ctx, b))
-            return fail(ctx, RF_ERR_STATE, "rf_backtrace: sequence changed since the bands were computed");
-        const SeqObj &S = ctx->seqs[b.seq];
-        const TplObj &T = ctx->tpls[b.tpl];
-        if (T.version != b.tplver)
-            return fail(ctx, RF_ERR_STATE, "rf_backtrace: template changed since the A band was computed");
-        BTTask &t = tasks[k];
-        t.A = b.r.off / 8;
-        t.sb = S.bases.off;
-        t.tab = S.tabs.off / 8;
-        t.tb = T.bases.off;
+        BTTask &t = tasks[k] = slot_desc<BTTask>(ctx, slot[k]);
         t.out = total;
-        t.n = b.n;
-        t.m = b.m;
-        t.bw = b.bw;
-        t.H = b.H;
-        t.ncins = S.ncins;
-        t.ncdel = S.ncdel;
         t.flags = (b.flags & RF_SKEW ? 2 : 0) | (b.flags & RF_TRIM ? 4 : 0);
         t.idx = k;
-        t.P = b.P;
-        t.mask = 0;
         offs[k] = total;
         total += b.n + b.m;
     }
@@ -8059,7 +8023,7 @@ int rf_backtrace(rf_ctx *ctx, int32_t nslots, const int32_t *slot, int8_t *moves
     (void)hipSetDevice(ctx->device);
     std::vector<BTTask> tasks;
     std::vector<int64_t> offs;
-    if (int e = build_bt_tasks(ctx, nslots, slot, tasks, offs))
+    if (int e = build_bt_tasks(ctx, "rf_backtrace", nslots, slot, tasks, offs))
         return e;
     const int64_t total = nslots > 0 ? offs[nslots - 1] + tasks[nslots - 1].n + tasks[nslots - 1].m : 0;
     int32_t *d_cnt = (int32_t *)ctx->scratch[4].p;
@@ -8105,7 +8069,7 @@ int rf_alignment_proposals(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off
     // 1. descriptors: backtrace tasks of every batch slot + each cluster's mask
     std::vector<BTTask> tasks;
     std::vector<int64_t> offs;
-    if (int e = build_bt_tasks(ctx, nslots, slots, tasks, offs))
+    if (int e = build_bt_tasks(ctx, "rf_alignment_proposals", nslots, slots, tasks, offs))
         return e;
     int64_t mask_total = 0;
     for (int32_t g = 0; g < ngroups; ++g) {
@@ -8144,43 +8108,6 @@ int rf_alignment_proposals(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off
     return 0;
 }
 
-// rf_score's check of a slot it scores: both bands filled, for one alignment,
-// and neither the template nor the sequence replaced since
-static bool score_band_ok(const rf_ctx *ctx, int32_t s, std::string &why)
-{
-    if (s < 0 || s >= (int32_t)ctx->slots.size()) {
-        why = "unknown slot";
-        return false;
-    }
-    const Slot &S = ctx->slots[s];
-    if (!S.a.valid || !S.b.valid) {
-        why = "slot has no A/B bands";
-        return false;
-    }
-    if (S.a.failed || S.b.failed) {
-        why = FILL_FAILED;
-        return false;
-    }
-    if (S.a.seq != S.b.seq || S.a.tpl != S.b.tpl || S.a.bw != S.b.bw || S.a.tplver != S.b.tplver ||
-        S.a.m != S.b.m || S.a.seqver != S.b.seqver || S.a.n != S.b.n) {
-        why = "A and B bands were computed for different alignments";
-        return false;
-    }
-    if (S.a.P != S.b.P) {
-        why = "A and B bands have different row strides";
-        return false;
-    }
-    if (ctx->tpls[S.a.tpl].version != S.a.tplver) {
-        why = "template changed since the bands were computed";
-        return false;
-    }
-    if (seq_stale(ctx, S.a)) {
-        why = "sequence changed since the bands were computed";
-        return false;
-    }
-    return true;
-}
-
 int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
              const int32_t *ref_slot, const int64_t *prop_off, const uint8_t *kind,
              const int32_t *pos, const uint8_t *base, double *out_total, double *out_per_seq)
@@ -8192,106 +8119,52 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
     if (nprops > 0 && (!kind || !pos || !base || !out_total))
         return fail(ctx, RF_ERR_ARG, "rf_score: bad proposal arrays");
 
-    auto band_ok = [&](int32_t s, std::string &why) -> bool { return score_band_ok(ctx, s, why); };
-
-    std::vector<ScoreGroup> groups(ngroups);
-    std::vector<ScoreRead> reads;
+    // 1. the slots, group by group in slot order: batch slots, then the reference
+    std::vector<ScoreReadIn> in;
+    std::vector<ScoreGroupIn> gin(ngroups);
     std::vector<int32_t> has_reads(ngroups, 0), has_ref(ngroups, 0);
-    std::vector<WorkItem> items;
-    std::vector<CodonTask> ctasks;
-    std::vector<int64_t> gstart(ngroups + 1, 0);
-    int64_t dense_total = 0, split_total = 0, scratch_total = 0;
-    int max_reads = 0;
-    bool all_finite = true;
+    in.reserve(ngroups > 0 ? std::max(slot_off[ngroups], 0) : 0);
     for (int32_t g = 0; g < ngroups; ++g) {
         int32_t tpl = -1;
-        std::string why;
-        const int32_t r0 = (int32_t)reads.size();
-        for (int32_t k = slot_off[g]; k < slot_off[g + 1]; ++k) {
-            if (!band_ok(slots[k], why))
-                return fail(ctx, RF_ERR_STATE, "rf_score: " + why);
-            const Band &A = ctx->slots[slots[k]].a;
-            const Band &B = ctx->slots[slots[k]].b;
-            const SeqObj &S = ctx->seqs[A.seq];
-            if (S.ncins > 0 || S.ncdel > 0)
-                return fail(ctx, RF_ERR_ARG, "error model cannot allow codon indels");
-            all_finite = all_finite && S.finite;
-            if (tpl >= 0 && A.tpl != tpl)
-                return fail(ctx, RF_ERR_ARG, "rf_score: batch slots use different templates");
-            tpl = A.tpl;
-            ScoreRead R{};
-            R.A = A.r.off / 8;
-            R.B = B.r.off / 8;
-            R.sb = S.bases.off;
-            R.tab = S.tabs.off / 8;
-            R.n = A.n;
-            R.bw = A.bw;
-            R.H = A.H;
-            R.c = std::max(A.m - A.n, 0) + A.bw;
-            R.vb = std::max(A.n - A.m, 0) + A.bw;
-            R.P = A.P;
-            R.K = (int32_t)band_K(A.H, A.m);
-            R.flags = (S.coded && S.ncins == 0 && S.ncdel == 0) ? SR_CODED : 0;
-            reads.push_back(R);
-        }
-        const int32_t r1 = (int32_t)reads.size();
+        const int32_t r0 = (int32_t)in.size();
+        if (int e = score_group_slots(ctx, "rf_score", RF_ERR_STATE, slots, slot_off[g], slot_off[g + 1], tpl, &in))
+            return e;
         if (ref_slot && ref_slot[g] >= 0) {
-            if (!band_ok(ref_slot[g], why))
-                return fail(ctx, RF_ERR_STATE, "rf_score (reference): " + why);
+            if (const char *why = score_band_fault(ctx, ref_slot[g]))
+                return fail(ctx, RF_ERR_STATE, std::string("rf_score (reference): ") + why);
             const int32_t rt = ctx->slots[ref_slot[g]].a.tpl;
             if (tpl >= 0 && rt != tpl)
                 return fail(ctx, RF_ERR_ARG, "rf_score: reference uses a different template");
             tpl = rt;
             has_ref[g] = 1;
         }
-        ScoreGroup &G = groups[g];
-        G.r0 = r0;
-        G.r1 = r1;
-        has_reads[g] = r1 > r0;
-        max_reads = std::max(max_reads, r1 - r0);
-        if (tpl < 0) {
-            G.m = 0;
-            G.tb = 0;
-        } else {
-            G.m = ctx->tpls[tpl].m;
-            G.tb = ctx->tpls[tpl].bases.off;
-        }
-        G.dense_off = dense_total;
-        gstart[g] = dense_total;
-        if (has_reads[g]) {
-            dense_total += (int64_t)(G.m + 1) * 9;
-            G.split_off = split_total;
-            split_total += (int64_t)(G.m + 1) * 9 * (r1 - r0);
-            for (int p0 = 0; p0 <= G.m; p0 += 64)
-                items.push_back({g, p0});
-        }
-        gstart[g + 1] = dense_total;
-        // proposals: validate, build codon tasks for the reference
+        has_reads[g] = (int32_t)in.size() > r0;
+        gin[g] = {r0, (int32_t)in.size(), tpl < 0 ? 0 : ctx->tpls[tpl].m, tpl < 0 ? 0 : ctx->tpls[tpl].bases.off};
+    }
+    // 2. the layout and the scorer; its vectors source the uploads below
+    ScorePlan P;
+    score_plan(in, gin, ctx->opt, true, P);
+    const std::vector<ScoreGroup> &groups = P.groups;
+    const std::vector<WorkItem> &items = P.items;
+    const int64_t dense_total = P.dense_total, split_total = P.split_total;
+    // rf_score counts 64-column items whichever scorer runs
+    const bool split = score_split(P.items64, P.max_reads, ctx->opt.score_mode, out_per_seq != nullptr);
+    // 3. the proposals; codon tasks for those of a group with a reference
+    std::vector<CodonTask> ctasks;
+    std::vector<int32_t> pgroup(nprops);
+    int64_t scratch_total = 0;
+    for (int32_t g = 0; g < ngroups; ++g)
         for (int64_t k = prop_off[g]; k < prop_off[g + 1]; ++k) {
-            const int kd = kind[k], ps = pos[k], b = base[k];
-            if (kd > 2 || b > 3 || (kd == 1 ? (ps < 0 || ps > G.m) : (ps < 1 || ps > G.m)))
+            const int kd = kind[k], ps = pos[k], b = base[k], m = groups[g].m;
+            if (kd > 2 || b > 3 || (kd == 1 ? (ps < 0 || ps > m) : (ps < 1 || ps > m)))
                 return fail(ctx, RF_ERR_ARG, "rf_score: proposal out of range");
             if (!has_reads[g] && !has_ref[g])
                 return fail(ctx, RF_ERR_ARG, "rf_score: group has neither reads nor reference");
+            pgroup[k - prop_off[0]] = g;
             if (has_ref[g]) {
-                const Band &A = ctx->slots[ref_slot[g]].a;
-                const Band &B = ctx->slots[ref_slot[g]].b;
-                const SeqObj &S = ctx->seqs[A.seq];
-                CodonTask t{};
-                t.A = A.r.off / 8;
-                t.B = B.r.off / 8;
-                t.sb = S.bases.off;
-                t.tab = S.tabs.off / 8;
-                t.tb = ctx->tpls[A.tpl].bases.off;
+                CodonTask t = slot_desc<CodonTask>(ctx, ref_slot[g]);
                 t.scratch = scratch_total;
-                scratch_total += 4 * (int64_t)(A.n + 1);
-                t.n = A.n;
-                t.m = A.m;
-                t.bw = A.bw;
-                t.H = A.H;
-                t.ncins = S.ncins;
-                t.ncdel = S.ncdel;
-                t.P = A.P;
+                scratch_total += 4 * (int64_t)(t.n + 1);
                 t.kind = kd;
                 t.pos = ps;
                 t.base = b;
@@ -8299,29 +8172,11 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
                 ctasks.push_back(t);
             }
         }
-    }
-    // split mode: not enough (group, chunk) items to fill the chip, or the
-    // caller wants per-read scores
-    // RF_OPT_SCORE_MODE = fused | split overrides the choice (tests cover both)
-    bool split = out_per_seq != nullptr || ((int64_t)items.size() < 2048 && max_reads > 1);
-    if (ctx->opt.score_mode == 1 && !out_per_seq)
-        split = false;
-    else if (ctx->opt.score_mode == 2)
-        split = true;
-
-    const ScorePick pick = pick_scorer(ctx->opt, reads, all_finite);
-    if (pick.cols() != 64)
-        items = make_items(groups, pick.cols());
-
-    std::vector<int32_t> pgroup(nprops);
-    for (int32_t g = 0; g < ngroups; ++g)
-        for (int64_t k = prop_off[g]; k < prop_off[g + 1]; ++k)
-            pgroup[k - prop_off[0]] = g;
 
     // uploads
     if (int e = upload(ctx, ctx->scratch[0], items)) return e;
     if (int e = upload(ctx, ctx->scratch[1], groups)) return e;
-    if (int e = upload(ctx, ctx->scratch[2], reads)) return e;
+    if (int e = upload(ctx, ctx->scratch[2], P.reads)) return e;
     if (int e = upload(ctx, ctx->scratch[3], ctasks)) return e;
     // proposal arrays + per-group flags + gstart
     const size_t pbytes = align_up(nprops * 4, 256) * 2 + align_up(nprops, 256) * 2 +
@@ -8358,7 +8213,7 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
     if (ngroups > 0) {
         HIPCHK(ctx, put(d_hr, has_reads.data(), ngroups * 4));
         HIPCHK(ctx, put(d_href, has_ref.data(), ngroups * 4));
-        HIPCHK(ctx, put(d_gstart, gstart.data(), (ngroups + 1) * 8));
+        HIPCHK(ctx, put(d_gstart, P.gstart.data(), (ngroups + 1) * 8));
     }
     if (h && (nprops > 0 || ngroups > 0))
         HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[4].p, h, pused, hipMemcpyHostToDevice, ctx->stream));
@@ -8381,10 +8236,11 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
     const double *d_bands = (const double *)ctx->band_arena.d;
 
     HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    unsigned gy = 0;
     if (!items.empty()) {
-        launch_scorer(ctx, pick, (unsigned)items.size(), split ? (unsigned)max_reads : 1u,
-                      (const WorkItem *)ctx->scratch[0].p, (const ScoreGroup *)ctx->scratch[1].p,
-                      (const ScoreRead *)ctx->scratch[2].p, d_dense, d_split);
+        gy = launch_scorer(ctx, P.pick, (unsigned)items.size(), split ? (unsigned)P.max_reads : 1u,
+                           (const WorkItem *)ctx->scratch[0].p, (const ScoreGroup *)ctx->scratch[1].p,
+                           (const ScoreRead *)ctx->scratch[2].p, d_dense, d_split);
         if (split && dense_total > 0)
             hipLaunchKernelGGL(k_reduce, dim3((unsigned)((dense_total + 255) / 256)), dim3(256), 0,
                                ctx->stream, (const ScoreGroup *)ctx->scratch[1].p, ngroups, d_gstart,
@@ -8453,6 +8309,7 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
         return e;
     if (nprops > 0)
         std::memcpy(out_total, (char *)ctx->hdn + HDN_RES, nprops * 8);
+    note_score_launch(ctx, P.pick, split, items.size(), gy);
     return 0;
 }
 
@@ -8463,119 +8320,49 @@ static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_of
         return fail(ctx, RF_ERR_ARG, "rf_score_dense: bad arguments");
     (void)hipSetDevice(ctx->device);
     const int32_t nslots = ngroups > 0 ? slot_off[ngroups] : 0;
-    auto &P = ctx->dplan;
-    const bool same = P.valid && P.gen == ctx->layout_gen && P.ngroups == ngroups && P.opt_gen == ctx->opt_gen &&
-                      P.slots.size() == (size_t)nslots &&
-                      !std::memcmp(P.slot_off.data(), slot_off, sizeof(int32_t) * (ngroups + 1)) &&
-                      (nslots == 0 || !std::memcmp(P.slots.data(), slots, sizeof(int32_t) * nslots));
+    auto &C = ctx->dplan;
+    ScorePlan &P = C.plan;
+    const bool same = C.valid && C.gen == ctx->layout_gen && C.ngroups == ngroups && C.opt_gen == ctx->opt_gen &&
+                      C.slots.size() == (size_t)nslots &&
+                      !std::memcmp(C.slot_off.data(), slot_off, sizeof(int32_t) * (ngroups + 1)) &&
+                      (nslots == 0 || !std::memcmp(C.slots.data(), slots, sizeof(int32_t) * nslots));
     // per-call validation of the bands, unless this very slot list was
-    // validated and nothing (sequences, templates, bands) changed since
-    if (!(same && P.val_epoch == ctx->state_epoch))
-    for (int32_t g = 0; g < ngroups; ++g) {
-        if (slot_off[g + 1] <= slot_off[g])
-            return fail(ctx, RF_ERR_ARG, "rf_score_dense: empty group");
-        int32_t tpl = -1;
-        for (int32_t k = slot_off[g]; k < slot_off[g + 1]; ++k) {
-            const int32_t sl = slots[k];
-            if (sl < 0 || sl >= (int32_t)ctx->slots.size())
-                return fail(ctx, RF_ERR_ARG, "rf_score_dense: unknown slot");
-            const Slot &S = ctx->slots[sl];
-            if (S.a.valid && S.b.valid && (S.a.failed || S.b.failed))
-                return fail(ctx, RF_ERR_STATE, std::string("rf_score_dense: ") + FILL_FAILED);
-            if (!S.a.valid || !S.b.valid || S.a.seq != S.b.seq || S.a.tpl != S.b.tpl ||
-                S.a.bw != S.b.bw || S.a.tplver != S.b.tplver || S.a.m != S.b.m || S.a.seqver != S.b.seqver ||
-                S.a.n != S.b.n)
-                return fail(ctx, RF_ERR_STATE, "rf_score_dense: A and B bands were computed for different alignments");
-            if (S.a.P != S.b.P)
-                return fail(ctx, RF_ERR_STATE, "rf_score_dense: A and B bands have different row strides");
-            if (ctx->tpls[S.a.tpl].version != S.a.tplver)
-                return fail(ctx, RF_ERR_STATE, "rf_score_dense: template changed since the bands were computed");
-            if (seq_stale(ctx, S.a))
-                return fail(ctx, RF_ERR_STATE, "rf_score_dense: sequence changed since the bands were computed");
-            const SeqObj &Q = ctx->seqs[S.a.seq];
-            if (Q.ncins > 0 || Q.ncdel > 0)
-                return fail(ctx, RF_ERR_ARG, "error model cannot allow codon indels");
-            if (tpl >= 0 && S.a.tpl != tpl)
-                return fail(ctx, RF_ERR_ARG, "rf_score_dense: batch slots use different templates");
-            tpl = S.a.tpl;
-        }
-    }
-    P.val_epoch = ctx->state_epoch;
-    if (!same) {
-        P.valid = false;
-        std::vector<ScoreGroup> &groups = P.groups;
-        std::vector<ScoreRead> &reads = P.reads;
-        std::vector<WorkItem> &items = P.items;
-        groups.assign(ngroups, ScoreGroup{});
-        reads.clear();
-        items.clear();
-        reads.reserve(nslots);
-        int64_t dense_total = 0, split_total = 0;
-        int max_reads = 0;
-        bool all_finite = true;
+    // validated and nothing (sequences, templates, bands) changed since; a
+    // new slot list is planned from the records of the same pass
+    if (!(same && C.val_epoch == ctx->state_epoch)) {
+        std::vector<ScoreReadIn> in;
+        std::vector<ScoreGroupIn> gin;
+        in.reserve(same ? 0 : std::max(nslots, 0));
+        gin.reserve(ngroups);
         for (int32_t g = 0; g < ngroups; ++g) {
-            ScoreGroup &G = groups[g];
-            G.r0 = (int32_t)reads.size();
-            for (int32_t k = slot_off[g]; k < slot_off[g + 1]; ++k) {
-                const Band &B = ctx->slots[slots[k]].b;
-                const Band &A = ctx->slots[slots[k]].a;
-                const SeqObj &S = ctx->seqs[A.seq];
-                all_finite = all_finite && S.finite;
-                ScoreRead R{};
-                R.A = A.r.off / 8;
-                R.B = B.r.off / 8;
-                R.sb = S.bases.off;
-                R.tab = S.tabs.off / 8;
-                R.n = A.n;
-                R.bw = A.bw;
-                R.H = A.H;
-                R.c = std::max(A.m - A.n, 0) + A.bw;
-                R.vb = std::max(A.n - A.m, 0) + A.bw;
-                R.P = A.P;
-                R.K = (int32_t)band_K(A.H, A.m);
-                R.flags = (S.coded && S.ncins == 0 && S.ncdel == 0) ? SR_CODED : 0;
-                reads.push_back(R);
-            }
-            G.r1 = (int32_t)reads.size();
-            const TplObj &T = ctx->tpls[ctx->slots[slots[slot_off[g]]].b.tpl];
-            G.m = T.m;
-            G.tb = T.bases.off;
-            G.dense_off = dense_total;
-            dense_total += (int64_t)(G.m + 1) * 9;
-            G.split_off = split_total;
-            split_total += (int64_t)(G.m + 1) * 9 * (G.r1 - G.r0);
-            max_reads = std::max(max_reads, G.r1 - G.r0);
-            for (int p0 = 0; p0 <= G.m; p0 += 64)
-                items.push_back({g, p0});
+            int32_t tpl = -1;
+            const int32_t r0 = (int32_t)in.size();
+            if (int e = score_group_slots(ctx, "rf_score_dense", RF_ERR_ARG, slots, slot_off[g], slot_off[g + 1], tpl,
+                                          same ? nullptr : &in))
+                return e;
+            gin.push_back({r0, (int32_t)in.size(), tpl < 0 ? 0 : ctx->tpls[tpl].m, tpl < 0 ? 0 : ctx->tpls[tpl].bases.off});
+            if (tpl < 0)   // no slots: score_plan refuses the group, the later ones stay unread
+                break;
         }
-        std::vector<int64_t> &gstart = P.gstart;
-        gstart.assign(ngroups + 1, 0);
-        for (int32_t g = 0; g < ngroups; ++g)
-            gstart[g] = groups[g].dense_off;
-        gstart[ngroups] = dense_total;
-        P.pick = pick_scorer(ctx->opt, reads, all_finite);
-        if (P.pick.cols() != 64)
-            items = make_items(groups, P.pick.cols());
-        if (int e = upload(ctx, ctx->scratch[11], items)) return e;
-        if (int e = upload(ctx, ctx->scratch[12], groups)) return e;
-        if (int e = upload(ctx, ctx->scratch[13], reads)) return e;
-        if (int e = upload(ctx, ctx->scratch[14], gstart)) return e;
-        P.valid = true;
-        P.gen = ctx->layout_gen;
-        P.ngroups = ngroups;
-        P.slot_off.assign(slot_off, slot_off + ngroups + 1);
-        P.slots.assign(slots, slots + nslots);
-        P.nitems = items.size();
-        P.max_reads = max_reads;
-        P.dense_total = dense_total;
-        P.split_total = split_total;
-        P.opt_gen = ctx->opt_gen;
+        if (!same) {
+            C.valid = false;
+            if (score_plan(in, gin, ctx->opt, false, P))
+                return fail(ctx, RF_ERR_ARG, "rf_score_dense: empty group");
+            if (int e = upload(ctx, ctx->scratch[11], P.items)) return e;
+            if (int e = upload(ctx, ctx->scratch[12], P.groups)) return e;
+            if (int e = upload(ctx, ctx->scratch[13], P.reads)) return e;
+            if (int e = upload(ctx, ctx->scratch[14], P.gstart)) return e;
+            C.valid = true;
+            C.gen = ctx->layout_gen;
+            C.ngroups = ngroups;
+            C.slot_off.assign(slot_off, slot_off + ngroups + 1);
+            C.slots.assign(slots, slots + nslots);
+            C.opt_gen = ctx->opt_gen;
+        }
+        C.val_epoch = ctx->state_epoch;
     }
-    bool split = (int64_t)P.nitems < 2048 && P.max_reads > 1;
-    if (ctx->opt.score_mode == 1)
-        split = false;
-    else if (ctx->opt.score_mode == 2)
-        split = true;
+    const size_t nitems = P.items.size();
+    const bool split = score_split((int64_t)nitems, P.max_reads, ctx->opt.score_mode, false);
     if (int e = ensure_buf(ctx, ctx->scratch[15], sizeof(double) * std::max<int64_t>(P.dense_total, 1)))
         return e;
     if (split)
@@ -8583,11 +8370,12 @@ static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_of
             return e;
     double *d_dense = (double *)ctx->scratch[15].p;
     HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    if (P.nitems) {
-        dim3 grid((unsigned)P.nitems, split ? (unsigned)P.max_reads : 1u);
-        launch_scorer(ctx, P.pick, grid.x, grid.y, (const WorkItem *)ctx->scratch[11].p,
-                      (const ScoreGroup *)ctx->scratch[12].p, (const ScoreRead *)ctx->scratch[13].p,
-                      d_dense, split ? (double *)ctx->scratch[10].p : nullptr);
+    unsigned gy = 0;
+    if (nitems) {
+        gy = launch_scorer(ctx, P.pick, (unsigned)nitems, split ? (unsigned)P.max_reads : 1u,
+                           (const WorkItem *)ctx->scratch[11].p, (const ScoreGroup *)ctx->scratch[12].p,
+                           (const ScoreRead *)ctx->scratch[13].p, d_dense,
+                           split ? (double *)ctx->scratch[10].p : nullptr);
         if (split)
             hipLaunchKernelGGL(k_reduce, dim3((unsigned)((P.dense_total + 255) / 256)), dim3(256), 0,
                                ctx->stream, (const ScoreGroup *)ctx->scratch[12].p, ngroups,
@@ -8605,6 +8393,7 @@ static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_of
     (void)hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]);
     ctx->score_ms = ms;
     ctx->gather_ms = 0;
+    note_score_launch(ctx, P.pick, split, nitems, gy);
     return 0;
 }
 
@@ -8636,11 +8425,10 @@ int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
         if (rs < 0)
             continue;
         any_ref = true;
-        std::string why;
         if (rs >= (int32_t)ctx->slots.size())
             return fail(ctx, RF_ERR_ARG, "rf_score_dense_ref: unknown reference slot");
-        if (!score_band_ok(ctx, rs, why))
-            return fail(ctx, RF_ERR_STATE, "rf_score_dense_ref (reference): " + why);
+        if (const char *why = score_band_fault(ctx, rs))
+            return fail(ctx, RF_ERR_STATE, std::string("rf_score_dense_ref (reference): ") + why);
         // the group's template is its first batch slot's (a bad batch slot is
         // refused by the reads' fold below)
         if (slot_off[g + 1] > slot_off[g]) {
@@ -8653,7 +8441,7 @@ int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
     // the reads' fold: totals in scratch[15]
     if (int e = score_dense_impl(ctx, ngroups, slot_off, slots, nullptr, hipMemcpyDeviceToHost))
         return e;
-    const auto &P = ctx->dplan;
+    const ScorePlan &P = ctx->dplan.plan;
     ctx->codon_dense_ms = 0;
     double *d_dense = (double *)ctx->scratch[15].p;
     if (any_ref) {
@@ -8662,25 +8450,10 @@ int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
         for (int32_t g = 0; g < ngroups; ++g) {
             if (ref_slot[g] < 0)
                 continue;
-            const Band &A = ctx->slots[ref_slot[g]].a;
-            const Band &B = ctx->slots[ref_slot[g]].b;
-            const SeqObj &S = ctx->seqs[A.seq];
-            CodonDenseGroup G{};
-            G.A = A.r.off / 8;
-            G.B = B.r.off / 8;
-            G.sb = S.bases.off;
-            G.tab = S.tabs.off / 8;
-            G.tb = ctx->tpls[A.tpl].bases.off;
+            CodonDenseGroup G = slot_desc<CodonDenseGroup>(ctx, ref_slot[g]);
             G.dense_off = P.groups[g].dense_off;
-            G.n = A.n;
-            G.m = A.m;
-            G.bw = A.bw;
-            G.H = A.H;
-            G.ncins = S.ncins;
-            G.ncdel = S.ncdel;
-            G.P = A.P;
             G.blk0 = (int32_t)nblk;
-            nblk += (9 * ((int64_t)A.m + 1) + 63) / 64;
+            nblk += (9 * ((int64_t)G.m + 1) + 63) / 64;
             cg.push_back(G);
         }
         if (nblk > INT32_MAX)
@@ -8705,6 +8478,69 @@ int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
                                    ctx->stream));
         HIPCHK(ctx, stream_wait(ctx));
     }
+    return 0;
+}
+
+int rf_last_score_launch(const rf_ctx *ctx, int32_t *launch)
+{
+    if (!ctx || !launch)
+        return RF_ERR_ARG;
+    std::copy(ctx->last_score, ctx->last_score + RF_SCL_FIELDS, launch);
+    return 0;
+}
+
+int rf_host_score_plan(int32_t nreads, const int32_t *n, const int32_t *m, const int32_t *bw, const int32_t *stride,
+                       const uint8_t *finite, int32_t ngroups, const int32_t *read_off, int32_t nopt,
+                       const int32_t *opt_key, const int32_t *opt_val, int32_t per_seq, int32_t empty_ok,
+                       int32_t *pick, int32_t *split, int32_t item_cap, int32_t *items, int32_t *nitems,
+                       int64_t *dense_off, int64_t *split_off)
+{
+    if (nreads < 0 || ngroups < 0 || nopt < 0 || item_cap < 0 || !pick || !split || !nitems || !dense_off ||
+        (nopt > 0 && (!opt_key || !opt_val)) || (nreads > 0 && (!n || !m || !bw || !finite)) ||
+        (ngroups > 0 && (!read_off || !split_off || read_off[0] != 0 || read_off[ngroups] != nreads)) ||
+        (ngroups == 0 && nreads > 0) || (item_cap > 0 && !items))
+        return RF_ERR_ARG;
+    ScoreOpts o;
+    for (int32_t i = 0; i < nopt; ++i) {
+        int *v = opt_key[i] == RF_OPT_SCORE_MODE ? &o.score_mode : opt_key[i] == RF_OPT_SCORE_KERNEL ? &o.score_kernel
+                 : opt_key[i] == RF_OPT_LEAN_LDS_KB ? &o.lean_lds_kb : nullptr;
+        if (!v)
+            return RF_ERR_ARG;
+        *v = opt_val[i];
+    }
+    std::vector<ScoreReadIn> in(nreads);
+    std::vector<ScoreGroupIn> gin(ngroups);
+    for (int32_t g = 0; g < ngroups; ++g) {
+        if (read_off[g + 1] < read_off[g])
+            return RF_ERR_ARG;
+        gin[g] = {read_off[g], read_off[g + 1], read_off[g + 1] > read_off[g] ? m[read_off[g]] : 0, 0};
+        for (int32_t r = read_off[g]; r < read_off[g + 1]; ++r) {
+            // as rf_host_dp_plan: H and K = H + 2 m in range, a stride that holds the band's row pairs
+            const int64_t H = 2 * (int64_t)bw[r] + std::abs((int64_t)n[r] - m[r]) + 1;
+            if (n[r] < 0 || m[r] < 0 || bw[r] < 1 || m[r] != gin[g].m || H + 2 * (int64_t)m[r] > INT32_MAX / 2 ||
+                (stride && (stride[r] < (H + 1) / 2 || stride[r] > (H + 1) / 2 + 16)))
+                return RF_ERR_ARG;
+            in[r] = {0, 0, 0, 0, n[r], m[r], bw[r], (int32_t)H, stride ? stride[r] : band_P((int)H), finite[r] != 0, false};
+        }
+    }
+    ScorePlan P;
+    if (int e = score_plan(in, gin, o, empty_ok != 0, P))
+        return e;
+    if (P.items.size() > (size_t)item_cap)
+        return RF_ERR_ARG;
+    pick[0] = P.pick.family();
+    pick[1] = P.pick.lds;
+    pick[2] = P.pick.cols();
+    split[0] = score_split(P.items64, P.max_reads, o.score_mode, per_seq != 0);          // rf_score
+    split[1] = score_split((int64_t)P.items.size(), P.max_reads, o.score_mode, false);   // the dense calls
+    *nitems = (int32_t)P.items.size();
+    for (size_t i = 0; i < P.items.size(); ++i) {
+        items[2 * i] = P.items[i].group;
+        items[2 * i + 1] = P.items[i].p0;
+    }
+    std::copy(P.gstart.begin(), P.gstart.end(), dense_off);
+    for (int32_t g = 0; g < ngroups; ++g)
+        split_off[g] = P.groups[g].split_off;
     return 0;
 }
 
@@ -8793,21 +8629,13 @@ int rf_internal_aln_sums_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_o
         return 1;
     (void)hipSetDevice(ctx->device);
     const int32_t ns = ngroups > 0 ? slot_off[ngroups] : 0;
-    for (int32_t k = 0; k < ns; ++k) {
-        if (slots[k] < 0 || slots[k] >= (int32_t)ctx->slots.size() || !ctx->slots[slots[k]].a.valid)
-            return fail(ctx, RF_ERR_STATE, "rf_aln_error_sums: slot has no A band");
-        if (ctx->slots[slots[k]].a.failed)
-            return fail(ctx, RF_ERR_STATE, std::string("rf_aln_error_sums: ") + FILL_FAILED);
-        if (seq_stale(ctx, ctx->slots[slots[k]].a))
-            return fail(ctx, RF_ERR_STATE, "rf_aln_error_sums: sequence changed since the bands were computed");
-        const SeqObj &S = ctx->seqs[ctx->slots[slots[k]].a.seq];
-        if (!S.coded)
-            return 1;
-    }
     std::vector<BTTask> tasks;
     std::vector<int64_t> offs;
-    if (int e = build_bt_tasks(ctx, ns, slots, tasks, offs))
+    if (int e = build_bt_tasks(ctx, "rf_aln_error_sums", ns, slots, tasks, offs))
         return e;
+    for (int32_t k = 0; k < ns; ++k)
+        if (!ctx->seqs[ctx->slots[slots[k]].a.seq].coded)
+            return 1;
     // errlut for the dictionary entries added since the last call
     CodeDict &D = ctx->codes;
     const size_t n3 = D.t3v.size() / 4;
@@ -9044,7 +8872,7 @@ extern "C" int rf_qv_probs(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off
     //    without row codes: the caller takes the host path
     if (int e = rf_internal_aln_sums_dev(ctx, ngroups, slot_off, slots, tlen, nullptr))
         return e;
-    const auto &P = ctx->dplan;
+    const ScorePlan &P = ctx->dplan.plan;
     std::vector<QvGroup> gq(ngroups);
     int64_t rows = 0;
     for (int32_t g = 0; g < ngroups; ++g) {

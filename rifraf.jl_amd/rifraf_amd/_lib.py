@@ -83,6 +83,10 @@ _SIGNATURES = {
     "rf_host_dp_plan": (c_int, [c_int32] + [c_void_p] * 9 + [c_int32] + [c_void_p] * 6 + [POINTER(c_int32), c_int32,
                                 c_void_p, POINTER(c_int32)]),
     "rf_last_dp_launches": (c_int, [c_void_p, c_int32, c_void_p, POINTER(c_int32)]),
+    "rf_host_score_plan": (c_int, [c_int32] + [c_void_p] * 5 + [c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                   c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, POINTER(c_int32),
+                                   c_void_p, c_void_p]),
+    "rf_last_score_launch": (c_int, [c_void_p, c_void_p]),
     "rf_set_option": (c_int, [c_void_p, c_int32, c_int32]),
     "rf_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int32)]),
 }
@@ -109,6 +113,15 @@ DP_LAUNCH_CAP = 64   # more than the planner's classes
 
 def dp_launch_records(buf, n):
     return [DpLaunch(DP_KERNELS[int(r[0])], *(int(x) for x in r[1:])) for r in buf[:n]]
+
+
+# kernel families of the scorers (include/rifraf_hip.h RF_SCK_*, by value: the score_kernel option's names)
+SCORE_KERNELS = (None, "general", "seg", "ws")
+# the scorer launch of a scoring call (RF_SCL_FIELDS int32)
+ScoreLaunch = namedtuple("ScoreLaunch", "kernel split items grid_y")
+# rf_host_score_plan's outputs: split_score is rf_score's split mode, split_dense the dense calls';
+# items are (group, first column) pairs; dense_off has one more entry than groups, the total
+ScorePlan = namedtuple("ScorePlan", "kernel lds cols split_score split_dense items dense_off split_off")
 
 
 class BatchParams(ctypes.Structure):
@@ -192,6 +205,29 @@ def host_dp_plan(n, m, bw, flags, ncins=None, ncdel=None, finite=None, stride_a=
     if rc != 0:
         raise ValueError(f"rf_host_dp_plan: bad arguments ({rc})")
     return (*(a[:nt.value] for a in out), dp_launch_records(rec, nl.value))
+
+
+def host_score_plan(n, m, bw, read_off, stride=None, finite=None, per_seq=False, empty_ok=True, **opts):
+    """rf_host_score_plan: the scoring planner for reads (n[r], m[r], bw[r])
+    in groups [read_off[g], read_off[g + 1]) on the host alone (no context, no
+    GPU).  finite defaults to True, stride to the unpadded stride; opts are
+    score_mode, score_kernel and lean_lds_kb by value.  Returns a ScorePlan."""
+    nr, ng = len(n), len(read_off) - 1
+    i32 = lambda a: np.ascontiguousarray(a, np.int32)
+    fin = np.ascontiguousarray(np.ones(nr) if finite is None else finite, np.uint8)
+    keys = np.array([OPTIONS[k] for k in opts], np.int32)
+    vals = np.array([opts[k] for k in opts], np.int32)
+    cap = int(sum(int(x) // 64 + 1 for x in m)) + 1   # no group has more items than its reads' 64-column chunks
+    pick, split, items = np.zeros(3, np.int32), np.zeros(2, np.int32), np.zeros((cap, 2), np.int32)
+    dense_off, split_off, ni = np.zeros(ng + 1, np.int64), np.zeros(max(ng, 1), np.int64), c_int32()
+    rc = load().rf_host_score_plan(nr, ptr(i32(n)), ptr(i32(m)), ptr(i32(bw)), None if stride is None else ptr(i32(stride)),
+                                   ptr(fin), ng, ptr(i32(read_off)), len(keys), ptr(keys), ptr(vals), int(per_seq),
+                                   int(empty_ok), ptr(pick), ptr(split), cap, ptr(items), ctypes.byref(ni),
+                                   ptr(dense_off), ptr(split_off))
+    if rc != 0:
+        raise ValueError(f"rf_host_score_plan: bad arguments ({rc})")
+    return ScorePlan(SCORE_KERNELS[pick[0]], int(pick[1]), int(pick[2]), bool(split[0]), bool(split[1]),
+                     [tuple(int(x) for x in it) for it in items[:ni.value]], dense_off.tolist(), split_off[:ng].tolist())
 
 
 def ptr(a: np.ndarray | None):

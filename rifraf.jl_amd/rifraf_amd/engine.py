@@ -747,6 +747,13 @@ class Engine:
         self._check(self.lib.rf_last_dp_launches(self.ctx, _lib.DP_LAUNCH_CAP, ptr(rec), byref(n)))
         return _lib.dp_launch_records(rec, n.value)
 
+    def last_score_launch(self):
+        """The scorer launch of the last successful scoring call (a
+        _lib.ScoreLaunch: kernel family, split mode, work items, grid.y)."""
+        rec = np.zeros(len(_lib.ScoreLaunch._fields), np.int32)
+        self._check(self.lib.rf_last_score_launch(self.ctx, ptr(rec)))
+        return _lib.ScoreLaunch(_lib.SCORE_KERNELS[rec[0]], bool(rec[1]), int(rec[2]), int(rec[3]))
+
     def last_timing(self):
         a, b, c = c_double(), c_double(), c_double()
         self._check(self.lib.rf_last_timing(self.ctx, byref(a), byref(b), byref(c)))

@@ -49,5 +49,17 @@ def dense_slot(kind, base):
     return np.where(kind == SUB, base, np.where(kind == DEL, 4, 5 + base))
 
 
+def assert_score_launch(engine, kernel=None, mode=None):
+    """The engine's last scoring call ran the scorer `kernel` ("general",
+    "seg", "ws") in `mode` ("fused", "split"); None: not checked.  The
+    scorers and modes compute the same bits, so only this shows the routing."""
+    launch = engine.last_score_launch()
+    assert launch.items > 0 and launch.grid_y > 0, launch
+    if kernel is not None:
+        assert launch.kernel == kernel, launch
+    if mode is not None:
+        assert launch.split == (mode == "split"), launch
+
+
 __all__ = ["make_read", "inband_mask", "all_proposals_arrays", "dense_slot", "random_seq",
-           "SEQ_SCORES", "REF_SCORES"]
+           "SEQ_SCORES", "REF_SCORES", "assert_score_launch"]

@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 
 import oracle
-from _util import (REF_SCORES, SEQ_SCORES, all_proposals_arrays, dense_slot, inband_mask, make_read,
-                   random_seq)
+from _util import (REF_SCORES, SEQ_SCORES, all_proposals_arrays, assert_score_launch, dense_slot, inband_mask,
+                   make_read, random_seq)
 from rifraf_amd import ErrorModel, RifrafSequence, Scores
 from rifraf_amd.engine import RF_BAND_A, RF_BAND_B, RF_BWD, RF_FWD, RF_SKEW, RF_TRIM, RifrafError
 
@@ -498,6 +498,7 @@ def test_score_all_proposals_bitexact(engine, opts, mode, L, nreads, bw):
     engine.realign(np.arange(nreads), np.arange(nreads), 0, [bw] * nreads, RF_FWD | RF_BWD)
     props = all_proposals_arrays(t)
     got = engine.score([(np.arange(nreads), -1, props)])[0]
+    assert_score_launch(engine, mode=mode)
     ref_tot, _ = oracle.cpu_pass(t, seqs, nthreads=4)
     exp = ref_tot[props[1], dense_slot(props[0], props[2])]
     np.testing.assert_array_equal(got, exp)
@@ -545,6 +546,7 @@ def test_score_many_clusters(engine, opts):
     engine.realign(np.arange(at), np.arange(at), np.array(tpl), [9] * at, RF_FWD | RF_BWD)
     groups = [(ids[c], -1, all_proposals_arrays(templates[c])) for c in range(6)]
     got = engine.score(groups)
+    assert_score_launch(engine, mode="fused")
     for c in range(6):
         ref_tot, _ = oracle.cpu_pass(templates[c], seqs[c], nthreads=4)
         k, p, b = groups[c][2]
@@ -633,6 +635,7 @@ def test_score_dense_clusters(engine, opts, mode):
         groups.append(np.arange(at, at + len(rs)))
         at += len(rs)
     got = engine.score_dense(groups)
+    assert_score_launch(engine, mode=mode)
     for c in range(5):
         ref_tot, _ = oracle.cpu_pass(templates[c], seqs[c], nthreads=4)
         t = templates[c]
@@ -685,6 +688,7 @@ def test_score_dense_fixed_stride_chains(engine, opts, mode):
         groups.append(np.arange(at, at + len(rs)))
         at += len(rs)
     got = engine.score_dense(groups)
+    assert_score_launch(engine, "ws", mode)
     for c in range(len(templates)):
         ref_tot, _ = oracle.cpu_pass(templates[c], seqs[c], nthreads=4)
         t = templates[c]
@@ -764,6 +768,7 @@ def test_score_ws_split_read_chunks(engine, opts, wgs):
     n = len(seqs)
     engine.realign(np.arange(n), np.arange(n), np.array(tpl_of), bws, RF_FWD | RF_BWD)
     dense = engine.score_dense(groups)
+    assert_score_launch(engine, "ws", "split")
     for c, t in enumerate(tpls):
         exp, _ = oracle.cpu_pass(t, [seqs[i] for i in groups[c]], nthreads=2)
         mask = np.ones_like(exp, bool)
@@ -817,6 +822,9 @@ def test_score_dense_kernels(engine, opts, kern, lds, mode):
         groups.append(np.arange(at, at + len(rs)))
         at += len(rs)
     got = engine.score_dense(groups)
+    # a named scorer runs ("ws" fits every budget here); auto under a 24-KB budget is k_score_segl
+    want = kern or ("seg" if lds else None)
+    assert_score_launch(engine, want, mode)
     for c in range(len(templates)):
         ref_tot, _ = oracle.cpu_pass(templates[c], seqs[c], nthreads=4)
         t = templates[c]
@@ -828,6 +836,7 @@ def test_score_dense_kernels(engine, opts, kern, lds, mode):
     # the proposal-list path (rf_score) through the same scorer
     props = [all_proposals_arrays(t) for t in templates]
     tots = engine.score([(groups[c], -1, props[c]) for c in range(len(templates))])
+    assert_score_launch(engine, want, mode)
     for c in range(len(templates)):
         ref_tot, _ = oracle.cpu_pass(templates[c], seqs[c], nthreads=4)
         k, p, b = props[c]
@@ -848,6 +857,7 @@ def test_score_lean_ineligible_tables(engine):
     engine.realign(np.arange(3), np.arange(3), 0, [9] * 3, RF_FWD | RF_BWD)
     props = all_proposals_arrays(t)
     got = engine.score([(np.arange(3), -1, props)])[0]
+    assert_score_launch(engine, "general")
     ref_tot, _ = oracle.cpu_pass(t, rs, nthreads=4)
     exp = ref_tot[props[1], dense_slot(props[0], props[2])]
     np.testing.assert_array_equal(got, exp)
@@ -908,6 +918,7 @@ def test_score_wide_bands(engine, opts, mode, kern):
         groups.append(np.arange(at, at + len(rs)))
         at += len(rs)
     got = engine.score_dense(groups)
+    assert_score_launch(engine, "general" if kern == "general" else "seg", mode)
     for c in range(len(templates)):
         ref_tot, _ = oracle.cpu_pass(templates[c], seqs[c], nthreads=4)
         t = templates[c]

@@ -29,7 +29,7 @@ import numpy as np
 import pytest
 
 import oracle
-from _util import REF_SCORES, SEQ_SCORES, all_proposals_arrays, random_seq
+from _util import REF_SCORES, SEQ_SCORES, all_proposals_arrays, assert_score_launch, random_seq
 from rifraf_amd import ErrorModel, RifrafSequence, Scores
 from rifraf_amd.align import moves_to_aligned_seqs, moves_to_indices, moves_to_proposals_np
 from rifraf_amd.engine import RF_BAND_A, RF_BAND_B, RF_BWD, RF_FWD, RF_SKEW, RF_TRIM, RifrafError
@@ -471,6 +471,7 @@ def test_scoring_nonfinite_groups(engine, opts, tier, mode):
         print(f"{tier} {mode} group {group}: {nfin} of {int(mask.sum())} compared slots finite")
         assert 2 * nfin >= mask.sum()
         got = engine.score_dense([g])[0]
+        assert_score_launch(engine, None if group == [0, 2] else "general", mode)
         assert same(got[mask], exp[mask]).all(), (tier, mode, group)
         check_list_scores(engine, g, -1, props, tot, per)
         if group == [0, 2]:

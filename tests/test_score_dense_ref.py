@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 import oracle
-from _util import REF_SCORES, all_proposals_arrays, dense_slot, make_read, random_seq
+from _util import REF_SCORES, all_proposals_arrays, assert_score_launch, dense_slot, make_read, random_seq
 from rifraf_amd import ErrorModel, RifrafSequence, Scores
 from rifraf_amd._lib import ptr
 from rifraf_amd.engine import RF_BWD, RF_FWD, Engine, RifrafError
@@ -418,6 +418,7 @@ def test_scorer_crossing(engine, opts, mode, kern):
     opts("score_kernel", kern)
     for cs in crossing_cases():
         check_cases(engine, [cs], f"crossing {mode} {kern}")
+        assert_score_launch(engine, kern, mode)
 
 
 def test_reference_follows_the_call(engine):
