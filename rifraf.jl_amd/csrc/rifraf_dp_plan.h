@@ -347,4 +347,118 @@ struct PairPlan {
     }
 };
 
+// The move trace of a pair (the layout is described in rifraf_hip.hip):
+// pa_blocks(klen) blocks of 16 periods, pa_hp(H) 64-bit words each
+RF_HD inline int pa_hp(int H) { return (H + 1) & ~1; }
+RF_HD inline int pa_blocks(int klen) { return (((klen + 1) >> 1) + 15) >> 4; }
+
+// What one launch set of a pair call produces besides its scores
+struct PairWants {
+    bool trace;    // the fills write the move trace (rf_pair_scores: none, and nothing below)
+    bool walk;     // the walk runs: nmoves and nerrors
+    bool get_mv;   // the moves go to the caller
+    bool emit;     // k_pa_emit runs: aln_len, t2s_len and tolerance, and with
+    bool want_txt, want_ix;   // ... these the two texts / the index maps
+    bool want_mv() const { return get_mv || emit; }   // the walk writes the moves
+};
+
+struct PairDims {
+    int32_t n, m, bw;
+};
+
+// The end of the launch set that starts at list position p0 of npairs: at
+// least one pair (a pair above the budget runs alone), then while there are
+// fewer than `chunk` pairs and, with a trace, its 64-bit words stay within
+// `budget` bytes.  dims(i): the PairDims of list position i.
+template <class F>
+int64_t pair_set_end(int64_t p0, int64_t npairs, int64_t chunk, bool trace, int64_t budget, F dims)
+{
+    if (!trace)
+        return p0 + std::min(chunk, npairs - p0);
+    int64_t cn = 0, words = 0;
+    while (p0 + cn < npairs && cn < chunk) {
+        const PairDims d = dims(p0 + cn);
+        const int H = band_rows(d.n + 1, d.m + 1, d.bw);
+        const int64_t w = (int64_t)pa_blocks(H + 2 * d.m) * pa_hp(H);
+        if (cn > 0 && (words + w) * 8 > budget)
+            break;
+        words += w;
+        ++cn;
+    }
+    return p0 + cn;
+}
+
+// One launch set: its tasks in launch order and, with a trace, where each
+// pair's trace, moves (n + m bytes) and index map (m int32) start.
+struct PairSet {
+    int64_t cn = 0;
+    PairPlan pl;
+    std::vector<int64_t> mvoff, ixoff;   // per pair, in set order
+    int64_t tr_at = 0, mv_total = 0, ix_total = 0;   // the totals: trace words, move bytes, map entries
+};
+
+// Fills `s` with the cn pairs of a set.  task(i, &finite): the DPTask of the
+// set's pair i (out_idx i; no band, P or pad yet) and whether its tables are
+// finite.
+template <class F>
+void pair_set_fill(PairSet &s, int64_t cn, bool trace, F task)
+{
+    s.cn = cn;
+    s.pl.clear();
+    s.mvoff.assign(trace ? (size_t)cn : 0, 0);
+    s.ixoff.assign(trace ? (size_t)cn : 0, 0);
+    s.tr_at = s.mv_total = s.ix_total = 0;
+    for (int64_t i = 0; i < cn; ++i) {
+        bool finite = false;
+        DPTask t = task(i, &finite);
+        if (trace) {
+            t.band = s.tr_at;             // the pair's trace: 64-bit words from the set's first
+            t.P = pa_hp(t.H);             // words per 16-period block
+            t.pad = pa_blocks(t.klen);    // blocks
+            s.tr_at += (int64_t)t.pad * t.P;
+            s.mvoff[(size_t)i] = s.mv_total;
+            s.mv_total += t.n + t.m;
+            s.ixoff[(size_t)i] = s.ix_total;
+            s.ix_total += t.m;
+        }
+        s.pl.add(t, finite);
+    }
+    s.pl.finish();
+}
+
+// Where a set's downloads land in the pinned zone (bytes from its start,
+// each part 16-byte aligned), and the device sizes that go with them.
+// Scores, then nmoves and nerrors, then the moves; with k_pa_emit its
+// lengths, the two texts (t, then s, mv_total bytes each) and the index maps.
+struct PairLanding {
+    size_t scores, counts;   // bytes: cn doubles at 0; 2 cn int32 behind them
+    size_t mv_at, len_at, txt_at, ix_at;
+    size_t lens;             // bytes: 3 cn int32 (aln_len, t2s_len, tolerance)
+    size_t total;            // bytes of the zone
+    size_t mv_dev, ix_dev;   // device bytes of the moves (and of each text) and of the index maps
+};
+
+inline PairLanding pair_landing(int64_t cn, int64_t mv_total, int64_t ix_total, const PairWants &w)
+{
+    const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    PairLanding L{};
+    L.scores = sizeof(double) * (size_t)cn;
+    L.total = L.scores;
+    if (!w.trace)
+        return L;
+    L.counts = sizeof(int32_t) * 2 * (size_t)cn;
+    L.lens = sizeof(int32_t) * 3 * (size_t)cn;
+    L.mv_at = up16(L.scores + L.counts);
+    L.len_at = up16(L.mv_at + (w.get_mv ? (size_t)mv_total : 0));
+    L.txt_at = up16(L.len_at + (w.emit ? L.lens : 0));
+    L.ix_at = up16(L.txt_at + (w.want_txt ? 2 * (size_t)mv_total : 0));
+    L.total = L.ix_at + (w.want_ix ? sizeof(int32_t) * (size_t)ix_total : 0);
+    L.mv_dev = (size_t)std::max<int64_t>(mv_total, 16);
+    L.ix_dev = sizeof(int32_t) * (size_t)std::max<int64_t>(ix_total, 4);
+    return L;
+}
+
+// DPTask.flags' skew and trim bits of a call's RF_SKEW / RF_TRIM
+inline int fill_flags(int flags) { return ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0); }
+
 #endif

@@ -1266,8 +1266,6 @@ constexpr int PS_GEN64_H = 2040;   // widest band of the one-wave general tier (
 static_assert(DPW_LDS_H == DP_LDS_H && PS_FAST_H == DP_FAST_H && PS_GEN64_H == DP_GEN64_H, "rifraf_dp_plan.h's limits");
 constexpr int PS_CHUNK = 65536;    // pairs per launch set of rf_pair_scores (RF_OPT_PAIR_CHUNK's default)
 constexpr int PA_TRACE_MB = 1024;  // RF_OPT_PAIR_TRACE_MB's default
-__host__ __device__ inline int pa_hp(int H) { return (H + 1) & ~1; }
-__host__ __device__ inline int pa_blocks(int klen) { return (((klen + 1) >> 1) + 15) >> 4; }
 // diagonal pairs per thread of the general tier: 2 NT NPP >= pa_hp(widest band of the tier)
 constexpr int PA_NPP64 = (PS_GEN64_H + 1 + 127) / 128;
 constexpr int PA_NPPW = (DPW_LDS_H + 1 + 2 * DPW_NT - 1) / (2 * DPW_NT);
@@ -5462,6 +5460,98 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// The context's device buffers (rf_ctx::scratch), each named for what it
+// holds.  Every buffer grows on demand (ensure_buf, upload) and is freed by
+// rf_destroy.  All work on them is issued to the context's stream (launch_dp's
+// side streams fork from it and join it again before launch_dp returns), and
+// every exported call waits for that stream before it returns, so two calls
+// never have work in flight at once: a buffer with two users (X_OR_Y) holds
+// one content at a time, in stream order.  A new user takes a new enumerator.
+// The wait is each call's own stream_wait after its last launch or copy that
+// touches a buffer: upload_sequence_chunk, rf_set_sequences_codes (after every
+// chunk) and rf_set_templates*; realign_run; pair_download, for every set;
+// rf_backtrace, rf_alignment_proposals, rf_score, score_dense_impl,
+// rf_score_dense_ref, rf_internal_aln_sums_dev and rf_qv_probs.  Nothing else
+// enforces it: an entry point that returned with work in flight would have to
+// take buffers of its own, and a context serves one call at a time.
+enum Buf : int {
+    BUF_SCORE_ITEMS,    // rf_score: WorkItem
+    BUF_SCORE_GROUPS,   // rf_score: ScoreGroup
+    // rf_score: ScoreRead | rf_alignment_proposals: the proposal mask its walks mark
+    BUF_READS_OR_MASK,
+    // The backtrace's moves (n + m bytes per slot, at BTTask::out) and its
+    // counts (nmoves, then nerrors, per slot): sized by build_bt_tasks,
+    // written by launch_backtraces' k_bt_win, read by rf_backtrace's downloads
+    // and by rf_internal_aln_sums_dev's k_aln_marks / k_aln_sums.  Writer and
+    // reader run inside the same exported call (rf_backtrace,
+    // rf_alignment_proposals, rf_aln_error_sums, rf_qv_probs), on the stream.
+    // | rf_score: CodonTask (moves) and its proposal block -- pgroup, pos,
+    // kind, base, the per-group flags and gstart (counts).
+    BUF_MOVES_OR_CTASKS,
+    BUF_COUNTS_OR_PROPS,
+    // Segment of the sequence and template uploads (upload_sequence_chunk,
+    // rf_set_sequences_codes, rf_set_templates*); upload_sequence_chunk uses it
+    // twice and waits for the stream in between | rf_score: its work block
+    // (dense totals, split partials, k_codon's columns and outputs, totals)
+    BUF_SEGS_OR_WORK,
+    // upload_sequence_chunk: the staged tables | rf_set_sequences_codes:
+    // CodeSeq; it waits for the stream after every chunk
+    BUF_TABS_OR_CSEQS,
+    // the staged bases of the sequence and template uploads (with
+    // rf_set_sequences_codes, the codes behind them) | launch_dp: the sink the
+    // lean kernels' padding tasks store to (written, never read)
+    BUF_BYTES_OR_SINK,
+    BUF_DP_TASKS,    // rf_realign: DPTask in device order; kept while rf_ctx::rplan is valid
+    BUF_DP_SCORES,   // rf_realign: two scores per job
+    // launch_dp: k_dp's global anti-diagonal ring (DpwLds / DpwGlobal launches)
+    // | score_dense_impl: the split partials k_reduce folds
+    BUF_RING_OR_SPLIT,
+    // score_dense_impl: WorkItem, ScoreGroup, ScoreRead and gstart; kept while rf_ctx::dplan is valid
+    BUF_DENSE_ITEMS,
+    BUF_DENSE_GROUPS,
+    BUF_DENSE_READS,
+    BUF_DENSE_GSTART,
+    // The dense totals, (m + 1) x 9 per group at dplan's dense_off: written by
+    // score_dense_impl, then folded into by rf_score_dense_ref's k_codon_dense
+    // or read by rf_qv_probs' k_qv -- inside the exported call that ran
+    // score_dense_impl, on the stream.
+    BUF_DENSE_TOTALS,
+    BUF_BT_TASKS,     // launch_backtraces: BTTask
+    BUF_ALN_READS,    // rf_internal_aln_sums_dev: AlnSumRead
+    BUF_ALN_GROUPS,   // rf_internal_aln_sums_dev: AlnSumGroup
+    // The alignment sums, m x 4 per group: written by rf_internal_aln_sums_dev
+    // (k_aln_fold / k_aln_sums), downloaded by it or read by rf_qv_probs' k_qv
+    // -- inside the rf_qv_probs call that ran it, on the stream.
+    BUF_ALN_SUMS,
+    BUF_CODE_LUTS,   // rf_set_sequences_codes: CodeLut
+    // rf_internal_aln_sums_dev's two-launch path: the reads' mark offsets, the
+    // groups' column and mark offsets, the marks
+    BUF_ALN_READ_BASE,
+    BUF_ALN_GROUP_COL,
+    BUF_ALN_GROUP_BASE,
+    BUF_ALN_MARKS,
+    BUF_QV_GROUPS,   // rf_qv_probs: QvGroup
+    BUF_QV_OUT,      // rf_qv_probs: pos, ins and aln probabilities, the groups' error codes
+    BUF_CODE_PREP,   // rf_set_sequences_codes_prep: p10 | match tables, the grid, est / tsum / ucode
+    // one launch set of the pair calls (pair_run): DPTask and scores; the move
+    // trace, the moves, their offsets, and the counts (nmoves, then nerrors)
+    BUF_PAIR_TASKS,
+    BUF_PAIR_SCORES,
+    BUF_PAIR_TRACE,
+    BUF_PAIR_MOVES,
+    BUF_PAIR_MOVE_OFF,
+    BUF_PAIR_COUNTS,
+    BUF_CODON_GROUPS,   // rf_score_dense_ref: CodonDenseGroup
+    // k_pa_emit's products for one launch set: the two texts, the index maps,
+    // their offsets, and aln_len / t2s_len / tolerance
+    BUF_PAIR_TEXT_T,
+    BUF_PAIR_TEXT_S,
+    BUF_PAIR_INDEX,
+    BUF_PAIR_INDEX_OFF,
+    BUF_PAIR_LENGTHS,
+    BUF_COUNT
+};
+
 }  // namespace
 
 // Host worker threads: OMP_NUM_THREADS when set (the GPU box's CPU share),
@@ -5639,10 +5729,7 @@ struct rf_ctx {
     // a plan validated at the current epoch with the same job / slot list
     // needs no per-slot validation again
     uint64_t state_epoch = 1;
-    DevBuf scratch[40];   // 28, 29: rf_pair_scores' / rf_pair_align's descriptors and scores;
-                          // 30-33: rf_pair_align's trace, moves, move offsets and counts;
-                          // 34: rf_score_dense_ref's group descriptors;
-                          // 35-39: rf_pair_align_text's two texts, index maps, map offsets and lengths
+    DevBuf scratch[BUF_COUNT];   // by Buf: what each holds, and who shares it
     // pinned host staging for sequence uploads (pageable H2D copies of a few
     // MB took ~14 ms per cluster upload on the box: page locking per call)
     void *pinned = nullptr;
@@ -5779,6 +5866,13 @@ hipError_t stream_wait(rf_ctx *ctx)
 hipError_t pre_d2h(rf_ctx *ctx)
 {
     return host_blocks(ctx) ? stream_wait(ctx) : hipSuccess;
+}
+
+// a context buffer as an array of T
+template <class T>
+T *dev(const rf_ctx *ctx, Buf b)
+{
+    return (T *)ctx->scratch[b].p;
 }
 
 int ensure_buf(rf_ctx *ctx, DevBuf &b, size_t bytes)
@@ -6530,19 +6624,21 @@ int upload_sequence_chunk(rf_ctx *ctx, int32_t first, int32_t k0, int32_t k1, co
         D.up3 = n3;
         D.up1 = n1;
     }
-    if (int e = ensure_buf(ctx, ctx->scratch[6], (size_t)std::max<int64_t>(nt * 8, 16))) return e;
-    if (int e = ensure_buf(ctx, ctx->scratch[7], (size_t)std::max<int64_t>(nb, 16))) return e;
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_TABS_OR_CSEQS], (size_t)std::max<int64_t>(nt * 8, 16))) return e;
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_BYTES_OR_SINK], (size_t)std::max<int64_t>(nb, 16))) return e;
     if (nseq > 0) {
         std::memcpy(host_bases, bases + off[k0], nb);
-        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[6].p, host_tabs, nt * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[7].p, host_bases, nb, hipMemcpyHostToDevice, ctx->stream));
-        if (int e = upload(ctx, ctx->scratch[5], st)) return e;
-        hipLaunchKernelGGL(k_scatter, dim3(nseq), dim3(256), 0, ctx->stream, (const Segment *)ctx->scratch[5].p,
-                           (const uint8_t *)ctx->scratch[6].p, (uint8_t *)ctx->tab_arena.d);
-        HIPCHK(ctx, stream_wait(ctx));   // scratch[5] is reused below
-        if (int e = upload(ctx, ctx->scratch[5], sb)) return e;
-        hipLaunchKernelGGL(k_scatter, dim3(nseq), dim3(256), 0, ctx->stream, (const Segment *)ctx->scratch[5].p,
-                           (const uint8_t *)ctx->scratch[7].p, (uint8_t *)ctx->bytes_arena.d);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_TABS_OR_CSEQS].p, host_tabs, nt * 8, hipMemcpyHostToDevice,
+                                   ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_BYTES_OR_SINK].p, host_bases, nb, hipMemcpyHostToDevice,
+                                   ctx->stream));
+        if (int e = upload(ctx, ctx->scratch[BUF_SEGS_OR_WORK], st)) return e;
+        hipLaunchKernelGGL(k_scatter, dim3(nseq), dim3(256), 0, ctx->stream, dev<const Segment>(ctx, BUF_SEGS_OR_WORK),
+                           dev<const uint8_t>(ctx, BUF_TABS_OR_CSEQS), (uint8_t *)ctx->tab_arena.d);
+        HIPCHK(ctx, stream_wait(ctx));   // BUF_SEGS_OR_WORK is reused below
+        if (int e = upload(ctx, ctx->scratch[BUF_SEGS_OR_WORK], sb)) return e;
+        hipLaunchKernelGGL(k_scatter, dim3(nseq), dim3(256), 0, ctx->stream, dev<const Segment>(ctx, BUF_SEGS_OR_WORK),
+                           dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK), (uint8_t *)ctx->bytes_arena.d);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, stream_wait(ctx));
     }
@@ -6771,12 +6867,12 @@ static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, co
         D.up3 = n3;
         D.up1 = n1;
     }
-    if (int e = upload(ctx, ctx->scratch[20], lut)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_CODE_LUTS], lut)) return e;
     // prep (rf_set_sequences_codes_prep): p10 | match tables, the 256 x 256
     // grid, then est / tsum (nseq doubles each) and ucode (nseq ints)
     const size_t prep_tab = 512 * 8, prep_grid = 65536 * 8, prep_out = (size_t)std::max(nseq, 1) * 20;
     if (prep) {
-        if (int e = ensure_buf(ctx, ctx->scratch[27], prep_tab + prep_grid + prep_out)) return e;
+        if (int e = ensure_buf(ctx, ctx->scratch[BUF_CODE_PREP], prep_tab + prep_grid + prep_out)) return e;
         // the two tables and the grid as one copy out of the pinned ring
         char *h;
         if (int e = ring_take(ctx, prep_tab + prep_grid, &h)) return e;
@@ -6784,17 +6880,18 @@ static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, co
             std::memcpy(h, p10_t, 256 * 8);
             std::memcpy(h + 256 * 8, match_t, 256 * 8);
             std::memcpy(h + prep_tab, grid, prep_grid);
-            HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[27].p, h, prep_tab + prep_grid, hipMemcpyHostToDevice,
+            HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_CODE_PREP].p, h, prep_tab + prep_grid, hipMemcpyHostToDevice,
                                        ctx->stream));
         } else {
-            HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[27].p, p10_t, 256 * 8, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync((char *)ctx->scratch[27].p + 256 * 8, match_t, 256 * 8,
+            HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_CODE_PREP].p, p10_t, 256 * 8, hipMemcpyHostToDevice,
+                                       ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(dev<char>(ctx, BUF_CODE_PREP) + 256 * 8, match_t, 256 * 8,
                                        hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync((char *)ctx->scratch[27].p + prep_tab, grid, prep_grid,
+            HIPCHK(ctx, hipMemcpyAsync(dev<char>(ctx, BUF_CODE_PREP) + prep_tab, grid, prep_grid,
                                        hipMemcpyHostToDevice, ctx->stream));
         }
     }
-    double *d_est = (double *)((char *)ctx->scratch[27].p + prep_tab + prep_grid);
+    double *d_est = (double *)(dev<char>(ctx, BUF_CODE_PREP) + prep_tab + prep_grid);
     double *d_tsum = d_est + std::max(nseq, 1);
     int32_t *d_ucode = (int32_t *)(d_tsum + std::max(nseq, 1));
     // chunks of sequences: codes + bases staged in pinned memory, one H2D,
@@ -6827,20 +6924,24 @@ static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, co
             cs[k - k0] = {S.tabs.off / 8, off[k] - off[k0], S.n, 0, 0};
             sg[k - k0] = {off[k] - off[k0], S.bases.off, S.n, 0};
         }
-        if (int e = ensure_buf(ctx, ctx->scratch[7], (size_t)std::max<int64_t>(2 * nb, 16))) return e;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[7].p, hb, 2 * nb, hipMemcpyHostToDevice, ctx->stream));
-        if (int e = upload(ctx, ctx->scratch[5], sg)) return e;
-        if (int e = upload(ctx, ctx->scratch[6], cs)) return e;
-        hipLaunchKernelGGL(k_scatter, dim3(k1 - k0), dim3(256), 0, ctx->stream, (const Segment *)ctx->scratch[5].p,
-                           (const uint8_t *)ctx->scratch[7].p, (uint8_t *)ctx->bytes_arena.d);
-        hipLaunchKernelGGL(k_tables, dim3(k1 - k0), dim3(256), 0, ctx->stream, (const CodeSeq *)ctx->scratch[6].p,
-                           (const uint8_t *)ctx->scratch[7].p + nb, (const uint8_t *)ctx->scratch[7].p,
-                           (const CodeLut *)ctx->scratch[20].p, s_mis, s_ins, s_del, (double *)ctx->tab_arena.d);
+        if (int e = ensure_buf(ctx, ctx->scratch[BUF_BYTES_OR_SINK], (size_t)std::max<int64_t>(2 * nb, 16))) return e;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_BYTES_OR_SINK].p, hb, 2 * nb, hipMemcpyHostToDevice, ctx->stream));
+        if (int e = upload(ctx, ctx->scratch[BUF_SEGS_OR_WORK], sg)) return e;
+        if (int e = upload(ctx, ctx->scratch[BUF_TABS_OR_CSEQS], cs)) return e;
+        hipLaunchKernelGGL(k_scatter, dim3(k1 - k0), dim3(256), 0, ctx->stream,
+                           dev<const Segment>(ctx, BUF_SEGS_OR_WORK),
+                           dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK), (uint8_t *)ctx->bytes_arena.d);
+        hipLaunchKernelGGL(k_tables, dim3(k1 - k0), dim3(256), 0, ctx->stream,
+                           dev<const CodeSeq>(ctx, BUF_TABS_OR_CSEQS),
+                           dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK) + nb, dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK),
+                           dev<const CodeLut>(ctx, BUF_CODE_LUTS), s_mis, s_ins, s_del, (double *)ctx->tab_arena.d);
         if (prep)
             hipLaunchKernelGGL(k_code_prep, dim3(k1 - k0), dim3(64), 0, ctx->stream,
-                               (const CodeSeq *)ctx->scratch[6].p, k1 - k0, (const uint8_t *)ctx->scratch[7].p + nb,
-                               (const double *)ctx->scratch[27].p, (const double *)((char *)ctx->scratch[27].p + prep_tab),
-                               d_est + k0, d_ucode + k0, d_tsum + k0);
+                               dev<const CodeSeq>(ctx, BUF_TABS_OR_CSEQS), k1 - k0,
+                               dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK) + nb,
+                               dev<const double>(ctx, BUF_CODE_PREP),
+                               (const double *)(dev<char>(ctx, BUF_CODE_PREP) + prep_tab), d_est + k0, d_ucode + k0,
+                               d_tsum + k0);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, stream_wait(ctx));   // staging and descriptors are reused
         k0 = k1;
@@ -6950,11 +7051,12 @@ int rf_set_templates_ids(rf_ctx *ctx, int32_t ntpl, const int32_t *ids, const ui
         for (int32_t k = 0; k < ntpl; ++k)
             sg[k] = {off[k] - off[0], ctx->tpls[ids[k]].bases.off, off[k + 1] - off[k], 0};
         const int64_t nb = off[ntpl] - off[0];
-        if (int e = ensure_buf(ctx, ctx->scratch[7], (size_t)std::max<int64_t>(nb, 16))) return e;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[7].p, bases + off[0], nb, hipMemcpyHostToDevice, ctx->stream));
-        if (int e = upload(ctx, ctx->scratch[5], sg)) return e;
-        hipLaunchKernelGGL(k_scatter, dim3(ntpl), dim3(256), 0, ctx->stream, (const Segment *)ctx->scratch[5].p,
-                           (const uint8_t *)ctx->scratch[7].p, (uint8_t *)ctx->bytes_arena.d);
+        if (int e = ensure_buf(ctx, ctx->scratch[BUF_BYTES_OR_SINK], (size_t)std::max<int64_t>(nb, 16))) return e;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_BYTES_OR_SINK].p, bases + off[0], nb, hipMemcpyHostToDevice,
+                                   ctx->stream));
+        if (int e = upload(ctx, ctx->scratch[BUF_SEGS_OR_WORK], sg)) return e;
+        hipLaunchKernelGGL(k_scatter, dim3(ntpl), dim3(256), 0, ctx->stream, dev<const Segment>(ctx, BUF_SEGS_OR_WORK),
+                           dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK), (uint8_t *)ctx->bytes_arena.d);
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, stream_wait(ctx));
@@ -7018,7 +7120,7 @@ static DPTask pair_task(const SeqObj &S, const TplObj &T, int bw, int fl, int32_
 static DPTask realign_task(const SeqObj &S, const TplObj &T, int bw, int jf, int dir, int32_t k, int32_t njobs,
                            int64_t band, int P)
 {
-    const int fl = dir == 1 ? 1 : ((jf & RF_SKEW) ? 2 : 0) | ((jf & RF_TRIM) ? 4 : 0);
+    const int fl = dir == 1 ? 1 : fill_flags(jf);
     DPTask t = pair_task(S, T, bw, fl, (dir == 0 || !(jf & RF_FWD)) ? k : njobs + k);
     t.band = band;
     t.P = P;
@@ -7182,22 +7284,23 @@ static DprFn dpr_kernel(const DpLaunch &L)
     return L.k == DpKernel::DprLeanPm ? pm[L.npi][L.pmi] : whole[L.npi][L.k == DpKernel::DprLean];
 }
 
-// The launches of a plan whose tasks are in scratch[8], scores into d_out.
+// The launches of a plan whose tasks are in BUF_DP_TASKS, scores into d_out.
 // The side streams fork from the context's stream and join it again.
 static int launch_dp(rf_ctx *ctx, const DpPlan &plan, double *d_out)
 {
-    const DPTask *d_tasks = (const DPTask *)ctx->scratch[8].p;
+    const DPTask *d_tasks = dev<const DPTask>(ctx, BUF_DP_TASKS);
     const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
     const double *d_tabs = (const double *)ctx->tab_arena.d;
     double *d_bands = (double *)ctx->band_arena.d;
     const double *d_lut = (const double *)ctx->codes.lut.p;
-    if (int e = ensure_buf(ctx, ctx->scratch[7], 4 * (size_t)dpl_task_bytes(4)))  // lean padding-task sink
+    // the lean kernels' padding-task sink
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_BYTES_OR_SINK], 4 * (size_t)dpl_task_bytes(4)))
         return e;
     bool fork = false;
     for (const DpLaunch &L : plan.launches) {
         fork = fork || L.stream >= 0;
         if (L.k == DpKernel::DpwLds || L.k == DpKernel::DpwGlobal)   // the global ring (sized for either)
-            if (int e = ensure_buf(ctx, ctx->scratch[10], L.n * 4 * (size_t)(L.hmax + 6) * 8))
+            if (int e = ensure_buf(ctx, ctx->scratch[BUF_RING_OR_SPLIT], L.n * 4 * (size_t)(L.hmax + 6) * 8))
                 return e;
     }
     if (fork)
@@ -7221,7 +7324,7 @@ static int launch_dp(rf_ctx *ctx, const DpPlan &plan, double *d_out)
         case DpKernel::DprLean:
         case DpKernel::DprLeanPm:
             hipLaunchKernelGGL(dpr_kernel(L), dim3(g.grid), dim3(g.block), g.lds, st, tk, n, d_bases, d_tabs, d_bands,
-                               d_out, ctx->d_err, (double *)ctx->scratch[7].p, d_lut);
+                               d_out, ctx->d_err, dev<double>(ctx, BUF_BYTES_OR_SINK), d_lut);
             break;
         case DpKernel::DpxCodon:
         case DpKernel::DpxLean:
@@ -7232,7 +7335,7 @@ static int launch_dp(rf_ctx *ctx, const DpPlan &plan, double *d_out)
         case DpKernel::DprWide32: {
             const DprFn fn = L.k == DpKernel::DprWide64 ? k_dpr<2, true, dpl_pmax(2, 64), 64> : k_dpr<2, true, dpl_pmax(2, 32), 32>;
             hipLaunchKernelGGL(fn, dim3(g.grid), dim3(g.block), g.lds, st, tk, n, d_bases, d_tabs, d_bands, d_out,
-                               ctx->d_err, (double *)ctx->scratch[7].p, d_lut);
+                               ctx->d_err, dev<double>(ctx, BUF_BYTES_OR_SINK), d_lut);
             break;
         }
         case DpKernel::Dp64:
@@ -7262,7 +7365,7 @@ static int launch_dp(rf_ctx *ctx, const DpPlan &plan, double *d_out)
             const bool gring = L.k == DpKernel::DpwGlobal;
             hipLaunchKernelGGL((gring ? k_dp<DPW_NT, true, DPW_NT> : k_dp<DPW_NT, false, DPW_NT>), dim3(g.grid),
                                dim3(g.block), g.lds, st, tk, n, d_bases, d_tabs, d_bands, d_out, ctx->d_err, ld,
-                               gring ? (double *)ctx->scratch[10].p : nullptr);
+                               gring ? dev<double>(ctx, BUF_RING_OR_SPLIT) : nullptr);
             break;
         }
         }
@@ -7307,7 +7410,7 @@ static int realign_run(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const in
         if (int e = realign_bands(ctx, njobs, slot, seq, tpl, bw, jf))
             return e;
         P.dp = realign_plan(ctx, njobs, slot, seq, tpl, bw, jf);
-        if (int e = upload(ctx, ctx->scratch[8], P.dp.tasks))
+        if (int e = upload(ctx, ctx->scratch[BUF_DP_TASKS], P.dp.tasks))
             return e;
         P.valid = true;
         P.gen = ctx->layout_gen;
@@ -7318,9 +7421,9 @@ static int realign_run(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const in
         P.tpl.assign(tpl, tpl + njobs);
         P.bw.assign(bw, bw + njobs);
     }
-    if (int e = ensure_buf(ctx, ctx->scratch[9], sizeof(double) * 2 * std::max(njobs, 1)))
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_DP_SCORES], sizeof(double) * 2 * std::max(njobs, 1)))
         return e;
-    double *d_out = (double *)ctx->scratch[9].p;
+    double *d_out = dev<double>(ctx, BUF_DP_SCORES);
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     if (int e = launch_dp(ctx, P.dp, d_out))
         return e;
@@ -7442,13 +7545,25 @@ int rf_realign_jobs(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32
 
 // ---- rf_pair_scores / rf_pair_align: the checks, the launch plan and the fill launches they share ----
 
+// The refusal of a band that no pair kernel holds.  k: the pair (-1:
+// rf_pair_scores, which names none); mb: the bandwidth after the last
+// doubling (-1: the call's own).  Both are indices / bandwidths the checks
+// have found non-negative, so a negative value can only mean "not named".
+static std::string band_too_wide(const std::string &fn, int64_t H, int64_t k, int64_t mb = -1)
+{
+    return fn + ": band of " + std::to_string(H) + " rows" +
+           (mb >= 0 ? " at the largest bandwidth " + std::to_string(mb) : std::string()) +
+           (k >= 0 ? " (pair " + std::to_string(k) + ")" : std::string()) + " is wider than the " +
+           std::to_string(DPW_LDS_H) + (k >= 0 ? " a bandless" : " a score-only") + " pass holds in LDS";
+}
+
 // Argument, flag and per-pair checks.  `fn` names the entry point in the
-// messages; `args_ok` is its own pointer check; `align` is rf_pair_align
-// (its wording, and its timers are the ones reset).
-static int pair_check(rf_ctx *ctx, const std::string &fn, bool align, bool args_ok, int64_t npairs,
+// messages; `outs_ok` is its check of its own output pointers; `align` is
+// rf_pair_align (its wording, and its timers are the ones reset).
+static int pair_check(rf_ctx *ctx, const std::string &fn, bool align, bool outs_ok, int64_t npairs,
                       const int32_t *seq, const int32_t *tpl, const int32_t *bw, int32_t flags)
 {
-    if (!args_ok)
+    if (!(ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && outs_ok))
         return fail(ctx, RF_ERR_ARG, fn + ": bad arguments");
     if (flags & RF_BWD)
         return fail(ctx, RF_ERR_ARG,
@@ -7468,20 +7583,16 @@ static int pair_check(rf_ctx *ctx, const std::string &fn, bool align, bool args_
             return fail(ctx, RF_ERR_ARG, "bandwidth must be positive");
         const int64_t H = 2 * (int64_t)bw[k] + std::abs((int64_t)ctx->seqs[seq[k]].n - ctx->tpls[tpl[k]].m) + 1;
         if (H > DPW_LDS_H)
-            return fail(ctx, RF_ERR_ARG,
-                        fn + ": band of " + std::to_string(H) + " rows" +
-                            (align ? " (pair " + std::to_string(k) + ")" : std::string()) + " is wider than the " +
-                            std::to_string(DPW_LDS_H) + (align ? " a bandless" : " a score-only") +
-                            " pass holds in LDS");
+            return fail(ctx, RF_ERR_ARG, band_too_wide(fn, H, align ? k : -1));
     }
     return 0;
 }
 
-// The fill launches of a plan whose tasks are in scratch[28]: k_pa* into the
-// trace d_tr, k_ps* without one.
+// The fill launches of a plan whose tasks are in BUF_PAIR_TASKS: k_pa* into
+// the trace d_tr, k_ps* without one.
 static int pair_fill(rf_ctx *ctx, const PairPlan &pl, double *d_out, uint64_t *d_tr)
 {
-    const DPTask *d_tasks = (const DPTask *)ctx->scratch[28].p;
+    const DPTask *d_tasks = dev<const DPTask>(ctx, BUF_PAIR_TASKS);
     const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
     const double *d_tabs = (const double *)ctx->tab_arena.d;
     const double *d_lut = (const double *)ctx->codes.lut.p;
@@ -7521,50 +7632,6 @@ static int pair_fill(rf_ctx *ctx, const PairPlan &pl, double *d_out, uint64_t *d
     return 0;
 }
 
-// Score-only forward pass of independent pairs (k_ps / k_ps_gen).  Reads the
-// sequence and template arenas only: no slot, no band, no band bookkeeping.
-// Pairs go to the device RF_OPT_PAIR_CHUNK at a time (descriptors in
-// scratch[28], scores in scratch[29]), so device memory does not grow with
-// npairs; within a chunk they are sorted into width classes, longest first.
-int rf_pair_scores(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
-                   int32_t flags, double *out)
-{
-    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw && out));
-    if (int e = pair_check(ctx, "rf_pair_scores", false, args_ok, npairs, seq, tpl, bw, flags))
-        return e;
-    const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
-    const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
-    PairPlan pl;
-    for (int64_t p0 = 0; p0 < npairs; p0 += chunk) {
-        const int64_t cn = std::min(chunk, npairs - p0);
-        pl.clear();
-        for (int64_t k = p0; k < p0 + cn; ++k) {
-            const SeqObj &S = ctx->seqs[seq[k]];
-            pl.add(pair_task(S, ctx->tpls[tpl[k]], bw[k], fl, (int32_t)(k - p0)), S.finite);
-        }
-        pl.finish();
-        if (int e = upload(ctx, ctx->scratch[28], pl.all))
-            return e;
-        if (int e = ensure_buf(ctx, ctx->scratch[29], sizeof(double) * (size_t)cn))
-            return e;
-        if (int e = ensure_hdn(ctx, sizeof(double) * (size_t)cn))
-            return e;
-        double *d_out = (double *)ctx->scratch[29].p;
-        HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-        if (int e = pair_fill(ctx, pl, d_out, nullptr))
-            return e;
-        HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync((char *)ctx->hdn + HDN_RES, d_out, sizeof(double) * (size_t)cn,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, stream_wait(ctx));
-        std::memcpy(out + p0, (const char *)ctx->hdn + HDN_RES, sizeof(double) * (size_t)cn);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
-        ctx->pair_ms += ms;
-    }
-    return 0;
-}
-
 int rf_last_pair_ms(const rf_ctx *ctx, double *ms)
 {
     if (!ctx || !ms)
@@ -7589,18 +7656,6 @@ static bool pair_walk_wave(const rf_ctx *ctx, int64_t cn, int64_t mv_total)
     return mv_total >= (int64_t)PAW_MIN_NM * cn;
 }
 
-// The body of rf_pair_align and of one round of rf_pair_align_smart: the
-// pairs idx[0 .. nidx) (idx NULL: 0 .. nidx - 1) at the bandwidths bw[k], in
-// launch sets of at most RF_OPT_PAIR_CHUNK pairs and RF_OPT_PAIR_TRACE_MB of
-// trace (a pair above the budget alone), so the trace (scratch[30]), the
-// moves (31), their offsets (32) and the counts (33) of one set are all the
-// device memory a call needs.  seq, tpl, bw and every output are indexed by
-// the pair's own k.  `walk`: run the walk (counts, and moves with `moves`).
-// `ended` (may be empty) sees a pair's score and counts and says whether its
-// moves go to the caller; without it every pair's do.  `tx` (may be NULL):
-// k_pa_emit runs after the walk of each set, over the moves in scratch[31],
-// and its products (scratch[35-39]) go to the caller under the same `ended`
-// rule; the moves themselves are downloaded only if `moves` asks for them.
 struct PairText {   // rf_pair_align_text's outputs, each NULL or indexed by the pair's own k
     uint8_t *aln_t, *aln_s;
     const int64_t *aln_off;
@@ -7609,200 +7664,243 @@ struct PairText {   // rf_pair_align_text's outputs, each NULL or indexed by the
     int32_t *t2s_len, *tolerance;
     bool any() const { return aln_t || aln_len || t2s || t2s_len || tolerance; }
 };
-static int pair_align_run(rf_ctx *ctx, int64_t nidx, const int64_t *idx, const int32_t *seq, const int32_t *tpl,
-                          const int32_t *bw, int fl, bool walk, double *out_score, int8_t *moves,
-                          const int64_t *moves_off, int32_t *nmoves, int32_t *nerrors,
-                          const std::function<bool(int64_t, double, int32_t, int32_t)> &ended,
-                          const PairText *tx = nullptr)
+
+// The pairs of one pair_run and where their results go.  List position i is
+// pair at(i); seq, tpl, bw and every output are indexed by the pair's own k.
+struct PairIo {
+    int64_t nidx;
+    const int64_t *idx;   // NULL: the pairs 0 .. nidx - 1
+    const int32_t *seq, *tpl, *bw;
+    int fl;               // fill_flags of the call
+    double *out_score;
+    int8_t *moves;
+    const int64_t *moves_off;
+    int32_t *nmoves, *nerrors;
+    const PairText *tx;   // may be NULL
+    int64_t at(int64_t i) const { return idx ? idx[i] : i; }
+};
+// sees a pair's k, score, nmoves and nerrors; says whether its moves and texts go to the caller
+using PairEnded = std::function<bool(int64_t, double, int32_t, int32_t)>;
+
+// rf_ctx::ev of a launch set (rf_realign and the scoring calls use the same events)
+enum { EV_PAIR_FILL_START = 0, EV_PAIR_FILL_END = 1, EV_PAIR_WALK_END = 2, EV_PAIR_EMIT_END = 3 };
+
+// Step 1 of a launch set: its descriptors on the device, room for its products
+static int pair_stage(rf_ctx *ctx, const PairSet &s, const PairLanding &L, const PairWants &w)
+{
+    DevBuf *b = ctx->scratch;
+    if (int e = upload(ctx, b[BUF_PAIR_TASKS], s.pl.all))
+        return e;
+    if (int e = ensure_buf(ctx, b[BUF_PAIR_SCORES], L.scores))
+        return e;
+    if (w.trace)
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_TRACE], (size_t)std::max<int64_t>(s.tr_at, 2) * 8))
+            return e;
+    if (w.walk) {
+        if (w.want_mv()) {
+            if (int e = ensure_buf(ctx, b[BUF_PAIR_MOVES], L.mv_dev))
+                return e;
+            if (int e = upload(ctx, b[BUF_PAIR_MOVE_OFF], s.mvoff))
+                return e;
+        }
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_COUNTS], L.counts))
+            return e;
+    }
+    if (w.want_txt) {
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_TEXT_T], L.mv_dev))
+            return e;
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_TEXT_S], L.mv_dev))
+            return e;
+    }
+    if (w.want_ix) {
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_INDEX], L.ix_dev))
+            return e;
+        if (int e = upload(ctx, b[BUF_PAIR_INDEX_OFF], s.ixoff))
+            return e;
+    }
+    if (w.emit)
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_LENGTHS], L.lens))
+            return e;
+    return ensure_hdn(ctx, L.total);
+}
+
+// Step 2: the fills, then with a trace the walk (k_pa_walk_w or k_pa_walk by
+// pair_walk_wave) and k_pa_emit over the moves the walk left
+static int pair_launch(rf_ctx *ctx, const PairSet &s, const PairWants &w)
+{
+    const int64_t cn = s.cn;
+    const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
+    const DPTask *d_tasks = dev<const DPTask>(ctx, BUF_PAIR_TASKS);
+    double *d_out = dev<double>(ctx, BUF_PAIR_SCORES);
+    uint64_t *d_tr = w.trace ? dev<uint64_t>(ctx, BUF_PAIR_TRACE) : nullptr;
+    int8_t *d_mv = w.want_mv() ? dev<int8_t>(ctx, BUF_PAIR_MOVES) : nullptr;
+    const int64_t *d_mvoff = dev<const int64_t>(ctx, BUF_PAIR_MOVE_OFF);
+    int32_t *d_cnt = dev<int32_t>(ctx, BUF_PAIR_COUNTS);
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_FILL_START], ctx->stream));
+    if (int e = pair_fill(ctx, s.pl, d_out, d_tr))
+        return e;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_FILL_END], ctx->stream));
+    if (!w.trace)
+        return 0;
+    if (w.walk) {
+        if (pair_walk_wave(ctx, cn, s.mv_total))
+            hipLaunchKernelGGL(k_pa_walk_w, dim3((unsigned)((cn + PAW_NW - 1) / PAW_NW)), dim3(64 * PAW_NW), 0,
+                               ctx->stream, d_tasks, (int)cn, d_bases, (const double *)d_out,
+                               (const uint64_t *)d_tr, d_mv, d_mvoff, d_cnt, d_cnt + cn);
+        else
+            hipLaunchKernelGGL(k_pa_walk, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, ctx->stream, d_tasks,
+                               (int)cn, d_bases, (const double *)d_out, (const uint64_t *)d_tr, d_mv, d_mvoff,
+                               d_cnt, d_cnt + cn);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_WALK_END], ctx->stream));
+    if (w.emit) {
+        hipLaunchKernelGGL(k_pa_emit, dim3((unsigned)((cn + PAW_NW - 1) / PAW_NW)), dim3(64 * PAW_NW), 0,
+                           ctx->stream, d_tasks, (int)cn, d_bases, (const int8_t *)d_mv, d_mvoff,
+                           (const int32_t *)d_cnt, w.want_txt ? dev<uint8_t>(ctx, BUF_PAIR_TEXT_T) : nullptr,
+                           w.want_txt ? dev<uint8_t>(ctx, BUF_PAIR_TEXT_S) : nullptr,
+                           w.want_ix ? dev<int32_t>(ctx, BUF_PAIR_INDEX) : nullptr,
+                           dev<const int64_t>(ctx, BUF_PAIR_INDEX_OFF), dev<int32_t>(ctx, BUF_PAIR_LENGTHS));
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_EMIT_END], ctx->stream));
+    }
+    return 0;
+}
+
+// Step 3: the set's products into the pinned landing zone, and the wait
+static int pair_download(rf_ctx *ctx, const PairSet &s, const PairLanding &L, const PairWants &w)
+{
+    const size_t mv = (size_t)s.mv_total;
+    auto get = [&](size_t at, Buf b, size_t bytes) {
+        return hipMemcpyAsync((char *)ctx->hdn + HDN_RES + at, ctx->scratch[b].p, bytes, hipMemcpyDeviceToHost,
+                              ctx->stream);
+    };
+    HIPCHK(ctx, get(0, BUF_PAIR_SCORES, L.scores));
+    if (w.walk)
+        HIPCHK(ctx, get(L.scores, BUF_PAIR_COUNTS, L.counts));
+    if (w.walk && w.get_mv && mv > 0)
+        HIPCHK(ctx, get(L.mv_at, BUF_PAIR_MOVES, mv));
+    if (w.emit)
+        HIPCHK(ctx, get(L.len_at, BUF_PAIR_LENGTHS, L.lens));
+    if (w.want_txt && mv > 0) {
+        HIPCHK(ctx, get(L.txt_at, BUF_PAIR_TEXT_T, mv));
+        HIPCHK(ctx, get(L.txt_at + mv, BUF_PAIR_TEXT_S, mv));
+    }
+    if (w.want_ix && s.ix_total > 0)
+        HIPCHK(ctx, get(L.ix_at, BUF_PAIR_INDEX, sizeof(int32_t) * (size_t)s.ix_total));
+    HIPCHK(ctx, stream_wait(ctx));
+    return 0;
+}
+
+// Step 4: the landed products to the caller's arrays, for the set's pairs
+// io.at(p0 ..), and the kernel times
+static void pair_collect(rf_ctx *ctx, const PairIo &io, int64_t p0, const PairSet &s, const PairLanding &L,
+                         const PairWants &w, const PairEnded &ended)
+{
+    const int64_t cn = s.cn;
+    const char *h = (const char *)ctx->hdn + HDN_RES;
+    const double *sc = (const double *)h;
+    const int32_t *cnt = (const int32_t *)(h + L.scores);
+    const int32_t *len = (const int32_t *)(h + L.len_at);   // aln_len, t2s_len, tolerance: cn of each
+    const PairText *tx = io.tx;
+    for (int64_t i = 0; i < cn; ++i) {
+        const int64_t k = io.at(p0 + i);
+        if (io.out_score)
+            io.out_score[k] = sc[i];
+        if (!w.walk)
+            continue;
+        if (io.nmoves)
+            io.nmoves[k] = cnt[i];
+        if (io.nerrors)
+            io.nerrors[k] = cnt[cn + i];
+        if (ended && !ended(k, sc[i], cnt[i], cnt[cn + i]))
+            continue;
+        if (w.get_mv && cnt[i] > 0) {   // the walk leaves the moves at the end of the pair's n + m slot
+            const int64_t slot = (i + 1 < cn ? s.mvoff[(size_t)i + 1] : s.mv_total) - s.mvoff[(size_t)i];
+            std::memcpy(io.moves + io.moves_off[k], h + L.mv_at + s.mvoff[(size_t)i] + slot - cnt[i], (size_t)cnt[i]);
+        }
+        if (!w.emit)
+            continue;
+        const int32_t al = len[i], il = len[cn + i];
+        if (tx->aln_len)
+            tx->aln_len[k] = al;
+        if (tx->t2s_len)
+            tx->t2s_len[k] = il;
+        if (tx->tolerance)
+            tx->tolerance[k] = len[2 * cn + i];
+        if (w.want_txt && al > 0) {   // k_pa_emit writes the texts from the start of the slot
+            std::memcpy(tx->aln_t + tx->aln_off[k], h + L.txt_at + s.mvoff[(size_t)i], (size_t)al);
+            std::memcpy(tx->aln_s + tx->aln_off[k], h + L.txt_at + s.mv_total + s.mvoff[(size_t)i], (size_t)al);
+        }
+        if (w.want_ix && il > 0)
+            std::memcpy(tx->t2s + tx->t2s_off[k], h + L.ix_at + sizeof(int32_t) * (size_t)s.ixoff[(size_t)i],
+                        sizeof(int32_t) * (size_t)il);
+    }
+    auto ms = [&](int a, int b) {
+        float t = 0;
+        (void)hipEventElapsedTime(&t, ctx->ev[a], ctx->ev[b]);
+        return t;
+    };
+    if (!w.trace) {
+        ctx->pair_ms += ms(EV_PAIR_FILL_START, EV_PAIR_FILL_END);
+        return;
+    }
+    ctx->pa_fill_ms += ms(EV_PAIR_FILL_START, EV_PAIR_FILL_END);
+    ctx->pa_walk_ms += ms(EV_PAIR_FILL_END, EV_PAIR_WALK_END);
+    if (w.emit)
+        ctx->pa_emit_ms += ms(EV_PAIR_WALK_END, EV_PAIR_EMIT_END);
+}
+
+// The body of every pair call (one round of rf_pair_align_smart): the pairs of
+// `io` in launch sets of at most RF_OPT_PAIR_CHUNK pairs and, with `trace`,
+// RF_OPT_PAIR_TRACE_MB of trace (pair_set_end), so one set's buffers
+// (BUF_PAIR_*) are all the device memory a call needs, whatever its size.
+// Within a set the pairs are sorted into width classes, longest first.
+// Without `trace` (rf_pair_scores) the fills are k_ps*, score-only, and
+// nothing follows them.  `walk`: run the walk (counts, and moves where asked
+// for); with io.tx, k_pa_emit then runs over the moves, which are downloaded
+// only if io.moves asks for them.  `ended` (may be empty) sees a pair's score
+// and counts and says whether its moves and k_pa_emit's products go to the
+// caller; without it every pair's do.
+static int pair_run(rf_ctx *ctx, const PairIo &io, bool trace, bool walk, const PairEnded &ended)
 {
     const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
     const int64_t budget = (int64_t)std::max(ctx->opt.pair_trace_mb, 1) << 20;   // bytes of trace per set
-    const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
-    auto at = [&](int64_t i) { return idx ? idx[i] : i; };
-    auto trace_words = [&](int64_t k) {
-        const SeqObj &S = ctx->seqs[seq[k]];
-        const TplObj &T = ctx->tpls[tpl[k]];
-        const int H = band_rows(S.n + 1, T.m + 1, bw[k]);
-        return (int64_t)pa_blocks(H + 2 * T.m) * pa_hp(H);
-    };
-    PairPlan pl;
-    std::vector<int64_t> mvoff, ixoff;
-    const bool emit = walk && tx && tx->any();
-    const bool want_txt = emit && tx->aln_t, want_ix = emit && tx->t2s;
-    for (int64_t p0 = 0; p0 < nidx;) {
-        // the set [p0, p0 + cn): at least one pair, then while both bounds hold
-        int64_t cn = 0, words = 0;
-        while (p0 + cn < nidx && cn < chunk) {
-            const int64_t w = trace_words(at(p0 + cn));
-            if (cn > 0 && (words + w) * 8 > budget)
-                break;
-            words += w;
-            ++cn;
-        }
-        pl.clear();
-        mvoff.assign((size_t)cn, 0);
-        ixoff.assign((size_t)cn, 0);
-        int64_t tr_at = 0, mv_total = 0, ix_total = 0;
-        for (int64_t i = p0; i < p0 + cn; ++i) {
-            const int64_t k = at(i);
-            const SeqObj &S = ctx->seqs[seq[k]];
-            const TplObj &T = ctx->tpls[tpl[k]];
-            DPTask t = pair_task(S, T, bw[k], fl, (int32_t)(i - p0));
-            t.band = tr_at;               // the pair's trace: 64-bit words from scratch[30]
-            t.P = pa_hp(t.H);             // words per 16-period block
-            t.pad = pa_blocks(t.klen);    // blocks
-            tr_at += (int64_t)t.pad * t.P;
-            mvoff[(size_t)(i - p0)] = mv_total;
-            mv_total += S.n + T.m;
-            ixoff[(size_t)(i - p0)] = ix_total;
-            ix_total += T.m;
-            pl.add(t, S.finite);
-        }
-        pl.finish();
-        const bool get_mv = moves != nullptr;    // the moves go to the caller
-        const bool want_mv = get_mv || emit;     // the walk writes them
-        // downloads: scores, then nmoves and nerrors, then the moves; with k_pa_emit
-        // its lengths, the two texts and the index maps follow
-        const size_t cb = sizeof(double) * (size_t)cn, nbytes = sizeof(int32_t) * 2 * (size_t)cn;
-        const size_t mv_at = (cb + nbytes + 15) & ~(size_t)15;
-        const size_t mv_len = (size_t)std::max<int64_t>(mv_total, 16), lb = sizeof(int32_t) * 3 * (size_t)cn;
-        const size_t len_at = (mv_at + (get_mv ? (size_t)mv_total : 0) + 15) & ~(size_t)15;
-        const size_t txt_at = (len_at + (emit ? lb : 0) + 15) & ~(size_t)15;
-        const size_t ix_at = (txt_at + (want_txt ? 2 * (size_t)mv_total : 0) + 15) & ~(size_t)15;
-        const size_t h_end = ix_at + (want_ix ? sizeof(int32_t) * (size_t)ix_total : 0);
-        if (int e = upload(ctx, ctx->scratch[28], pl.all))
+    const bool emit = walk && io.tx && io.tx->any();
+    const PairWants w{trace, walk, io.moves != nullptr, emit, emit && io.tx->aln_t, emit && io.tx->t2s};
+    PairSet s;
+    for (int64_t p0 = 0; p0 < io.nidx; p0 += s.cn) {
+        const int64_t p1 = pair_set_end(p0, io.nidx, chunk, trace, budget, [&](int64_t i) {
+            const int64_t k = io.at(i);
+            return PairDims{ctx->seqs[io.seq[k]].n, ctx->tpls[io.tpl[k]].m, io.bw[k]};
+        });
+        pair_set_fill(s, p1 - p0, trace, [&](int64_t i, bool *finite) {
+            const int64_t k = io.at(p0 + i);
+            const SeqObj &S = ctx->seqs[io.seq[k]];
+            *finite = S.finite;
+            return pair_task(S, ctx->tpls[io.tpl[k]], io.bw[k], io.fl, (int32_t)i);
+        });
+        const PairLanding L = pair_landing(s.cn, s.mv_total, s.ix_total, w);
+        if (int e = pair_stage(ctx, s, L, w))
             return e;
-        if (int e = ensure_buf(ctx, ctx->scratch[29], cb))
+        if (int e = pair_launch(ctx, s, w))
             return e;
-        if (int e = ensure_buf(ctx, ctx->scratch[30], (size_t)std::max<int64_t>(tr_at, 2) * 8))
+        if (int e = pair_download(ctx, s, L, w))
             return e;
-        if (walk) {
-            if (want_mv) {
-                if (int e = ensure_buf(ctx, ctx->scratch[31], mv_len))
-                    return e;
-                if (int e = upload(ctx, ctx->scratch[32], mvoff))
-                    return e;
-            }
-            if (int e = ensure_buf(ctx, ctx->scratch[33], nbytes))
-                return e;
-        }
-        if (want_txt) {
-            if (int e = ensure_buf(ctx, ctx->scratch[35], mv_len))
-                return e;
-            if (int e = ensure_buf(ctx, ctx->scratch[36], mv_len))
-                return e;
-        }
-        if (want_ix) {
-            if (int e = ensure_buf(ctx, ctx->scratch[37], sizeof(int32_t) * (size_t)std::max<int64_t>(ix_total, 4)))
-                return e;
-            if (int e = upload(ctx, ctx->scratch[38], ixoff))
-                return e;
-        }
-        if (emit)
-            if (int e = ensure_buf(ctx, ctx->scratch[39], lb))
-                return e;
-        if (int e = ensure_hdn(ctx, h_end))
-            return e;
-        const DPTask *d_tasks = (const DPTask *)ctx->scratch[28].p;
-        double *d_out = (double *)ctx->scratch[29].p;
-        uint64_t *d_tr = (uint64_t *)ctx->scratch[30].p;
-        int32_t *d_cnt = (int32_t *)ctx->scratch[33].p;
-        HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-        if (int e = pair_fill(ctx, pl, d_out, d_tr))
-            return e;
-        HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-        if (walk) {
-            if (pair_walk_wave(ctx, cn, mv_total))
-                hipLaunchKernelGGL(k_pa_walk_w, dim3((unsigned)((cn + PAW_NW - 1) / PAW_NW)), dim3(64 * PAW_NW), 0,
-                                   ctx->stream, d_tasks, (int)cn, d_bases, (const double *)d_out,
-                                   (const uint64_t *)d_tr, want_mv ? (int8_t *)ctx->scratch[31].p : nullptr,
-                                   (const int64_t *)ctx->scratch[32].p, d_cnt, d_cnt + cn);
-            else
-                hipLaunchKernelGGL(k_pa_walk, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, ctx->stream, d_tasks,
-                                   (int)cn, d_bases, (const double *)d_out, (const uint64_t *)d_tr,
-                                   want_mv ? (int8_t *)ctx->scratch[31].p : nullptr,
-                                   (const int64_t *)ctx->scratch[32].p, d_cnt, d_cnt + cn);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-        if (emit) {
-            hipLaunchKernelGGL(k_pa_emit, dim3((unsigned)((cn + PAW_NW - 1) / PAW_NW)), dim3(64 * PAW_NW), 0,
-                               ctx->stream, d_tasks, (int)cn, d_bases, (const int8_t *)ctx->scratch[31].p,
-                               (const int64_t *)ctx->scratch[32].p, (const int32_t *)d_cnt,
-                               want_txt ? (uint8_t *)ctx->scratch[35].p : nullptr,
-                               want_txt ? (uint8_t *)ctx->scratch[36].p : nullptr,
-                               want_ix ? (int32_t *)ctx->scratch[37].p : nullptr,
-                               (const int64_t *)ctx->scratch[38].p, (int32_t *)ctx->scratch[39].p);
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-        }
-        char *h = (char *)ctx->hdn + HDN_RES;
-        HIPCHK(ctx, hipMemcpyAsync(h, d_out, cb, hipMemcpyDeviceToHost, ctx->stream));
-        if (walk)
-            HIPCHK(ctx, hipMemcpyAsync(h + cb, d_cnt, nbytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (walk && get_mv && mv_total > 0)
-            HIPCHK(ctx, hipMemcpyAsync(h + mv_at, ctx->scratch[31].p, (size_t)mv_total, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        if (emit)
-            HIPCHK(ctx, hipMemcpyAsync(h + len_at, ctx->scratch[39].p, lb, hipMemcpyDeviceToHost, ctx->stream));
-        if (want_txt && mv_total > 0) {
-            HIPCHK(ctx, hipMemcpyAsync(h + txt_at, ctx->scratch[35].p, (size_t)mv_total, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(h + txt_at + mv_total, ctx->scratch[36].p, (size_t)mv_total,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (want_ix && ix_total > 0)
-            HIPCHK(ctx, hipMemcpyAsync(h + ix_at, ctx->scratch[37].p, sizeof(int32_t) * (size_t)ix_total,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, stream_wait(ctx));
-        const double *sc = (const double *)h;
-        const int32_t *cnt = (const int32_t *)(h + cb);
-        const int32_t *len = (const int32_t *)(h + len_at);   // aln_len, t2s_len, tolerance: cn of each
-        for (int64_t i = 0; i < cn; ++i) {
-            const int64_t k = at(p0 + i);
-            if (out_score)
-                out_score[k] = sc[i];
-            if (!walk)
-                continue;
-            if (nmoves)
-                nmoves[k] = cnt[i];
-            if (nerrors)
-                nerrors[k] = cnt[cn + i];
-            if (ended && !ended(k, sc[i], cnt[i], cnt[cn + i]))
-                continue;
-            if (get_mv && cnt[i] > 0) {   // the walk leaves the moves at the end of the pair's n + m slot
-                const int64_t slot = (i + 1 < cn ? mvoff[(size_t)i + 1] : mv_total) - mvoff[(size_t)i];
-                std::memcpy(moves + moves_off[k], h + mv_at + mvoff[(size_t)i] + slot - cnt[i], (size_t)cnt[i]);
-            }
-            if (!emit)
-                continue;
-            const int32_t al = len[i], il = len[cn + i];
-            if (tx->aln_len)
-                tx->aln_len[k] = al;
-            if (tx->t2s_len)
-                tx->t2s_len[k] = il;
-            if (tx->tolerance)
-                tx->tolerance[k] = len[2 * cn + i];
-            if (want_txt && al > 0) {   // k_pa_emit writes the texts from the start of the slot
-                std::memcpy(tx->aln_t + tx->aln_off[k], h + txt_at + mvoff[(size_t)i], (size_t)al);
-                std::memcpy(tx->aln_s + tx->aln_off[k], h + txt_at + mv_total + mvoff[(size_t)i], (size_t)al);
-            }
-            if (want_ix && il > 0)
-                std::memcpy(tx->t2s + tx->t2s_off[k], h + ix_at + sizeof(int32_t) * (size_t)ixoff[(size_t)i],
-                            sizeof(int32_t) * (size_t)il);
-        }
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
-        ctx->pa_fill_ms += ms;
-        (void)hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]);
-        ctx->pa_walk_ms += ms;
-        if (emit) {
-            (void)hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]);
-            ctx->pa_emit_ms += ms;
-        }
-        p0 += cn;
+        pair_collect(ctx, io, p0, s, L, w, ended);
     }
     return 0;
+}
+
+// Score-only forward pass of independent pairs (k_ps / k_ps_gen).  Reads the
+// sequence and template arenas only: no slot, no band, no band bookkeeping.
+int rf_pair_scores(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
+                   int32_t flags, double *out)
+{
+    if (int e = pair_check(ctx, "rf_pair_scores", false, npairs == 0 || out, npairs, seq, tpl, bw, flags))
+        return e;
+    const PairIo io{npairs, nullptr, seq, tpl, bw, fill_flags(flags), out, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return pair_run(ctx, io, false, false, nullptr);
 }
 
 // Alignments of independent pairs from a 4-bit move trace (k_pa / k_pa_gen,
@@ -7812,27 +7910,26 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
                   int32_t flags, double *out_score, int8_t *moves, const int64_t *moves_off, int32_t *nmoves,
                   int32_t *nerrors)
 {
-    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && (!moves == !moves_off);
-    if (int e = pair_check(ctx, "rf_pair_align", true, args_ok, npairs, seq, tpl, bw, flags))
+    if (int e = pair_check(ctx, "rf_pair_align", true, !moves == !moves_off, npairs, seq, tpl, bw, flags))
         return e;
-    const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
-    return pair_align_run(ctx, npairs, nullptr, seq, tpl, bw, fl, moves || nmoves || nerrors, out_score, moves,
-                          moves_off, nmoves, nerrors, nullptr);
+    const PairIo io{npairs, nullptr, seq, tpl, bw, fill_flags(flags),
+                    out_score, moves, moves_off, nmoves, nerrors, nullptr};
+    return pair_run(ctx, io, true, moves || nmoves || nerrors, nullptr);
 }
 
 // smart_forward_moves! (model.jl:643-672) of independent pairs: rounds of
-// pair_align_run over the pairs still pending, each at its current bandwidth;
+// pair_run over the pairs still pending, each at its current bandwidth;
 // the loop's decisions are taken here from the downloaded counts.
 // `fn` names the entry point (rf_pair_align_smart, rf_pair_align_text); `tx`
 // (may be NULL) is rf_pair_align_text's outputs, which also lets threshold be
 // NULL when max_doublings is 0: no pair then gets past its first fill.
-static int pair_smart_run(rf_ctx *ctx, const std::string &fn, bool args_ok, int64_t npairs, const int32_t *seq,
+static int pair_smart_run(rf_ctx *ctx, const std::string &fn, bool outs_ok, int64_t npairs, const int32_t *seq,
                           const int32_t *tpl, const int32_t *bw, const double *threshold, const uint8_t *fixed,
                           int32_t max_doublings, int32_t flags, double *out_score, int8_t *moves,
                           const int64_t *moves_off, int32_t *nmoves, int32_t *nerrors, int32_t *out_bw,
                           int32_t *out_rounds, const PairText *tx)
 {
-    if (int e = pair_check(ctx, fn, true, args_ok, npairs, seq, tpl, bw, flags))
+    if (int e = pair_check(ctx, fn, true, outs_ok, npairs, seq, tpl, bw, flags))
         return e;
     if (npairs > 0 && !threshold && !(tx && max_doublings == 0))
         return fail(ctx, RF_ERR_ARG, fn + ": threshold is NULL");
@@ -7845,14 +7942,10 @@ static int pair_smart_run(rf_ctx *ctx, const std::string &fn, bool args_ok, int6
         const int64_t mb = (fixed && fixed[k]) ? bw[k] : std::min({(int64_t)bw[k] << max_doublings, m, n});
         const int64_t H = 2 * mb + std::abs(n - m) + 1;
         if (H > DPW_LDS_H)
-            return fail(ctx, RF_ERR_ARG,
-                        fn + ": band of " + std::to_string(H) + " rows at the largest bandwidth " +
-                            std::to_string(mb) + " (pair " + std::to_string(k) + ") is wider than the " +
-                            std::to_string(DPW_LDS_H) + " a bandless pass holds in LDS");
+            return fail(ctx, RF_ERR_ARG, band_too_wide(fn, H, k, mb));
         cur[(size_t)k] = bw[k];
         maxbw[(size_t)k] = (int32_t)mb;
     }
-    const int fl = ((flags & RF_SKEW) ? 2 : 0) | ((flags & RF_TRIM) ? 4 : 0);
     const bool want = moves || nmoves || nerrors || (tx && tx->any());
     // the loop reads every pair's score and error count, whatever the caller asked for
     std::vector<double> sc_own;
@@ -7887,8 +7980,9 @@ static int pair_smart_run(rf_ctx *ctx, const std::string &fn, bool args_ok, int6
         bool walk = want;
         for (int64_t k : pending)
             walk = walk || !stops_at_fill(k);
-        if (int e = pair_align_run(ctx, (int64_t)pending.size(), pending.data(), seq, tpl, cur.data(), fl, walk,
-                                   out_score, moves, moves_off, nmoves, nerrors, ended, tx))
+        const PairIo io{(int64_t)pending.size(), pending.data(), seq, tpl, cur.data(), fill_flags(flags), out_score,
+                        moves, moves_off, nmoves, nerrors, tx};
+        if (int e = pair_run(ctx, io, true, walk, ended))
             return e;
         next.clear();
         for (int64_t k : pending) {
@@ -7913,9 +8007,9 @@ int rf_pair_align_smart(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const i
                         double *out_score, int8_t *moves, const int64_t *moves_off, int32_t *nmoves,
                         int32_t *nerrors, int32_t *out_bw, int32_t *out_rounds)
 {
-    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && (!moves == !moves_off);
-    return pair_smart_run(ctx, "rf_pair_align_smart", args_ok, npairs, seq, tpl, bw, threshold, fixed, max_doublings,
-                          flags, out_score, moves, moves_off, nmoves, nerrors, out_bw, out_rounds, nullptr);
+    return pair_smart_run(ctx, "rf_pair_align_smart", !moves == !moves_off, npairs, seq, tpl, bw, threshold, fixed,
+                          max_doublings, flags, out_score, moves, moves_off, nmoves, nerrors, out_bw, out_rounds,
+                          nullptr);
 }
 
 // rf_pair_align_smart whose products are k_pa_emit's: align (align.jl:346-353,
@@ -7928,10 +8022,9 @@ int rf_pair_align_text(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const in
                        int32_t *t2s, const int64_t *t2s_off, int32_t *t2s_len, int32_t *tolerance,
                        int32_t *nerrors, int32_t *out_bw, int32_t *out_rounds)
 {
-    const bool args_ok = ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && (!aln_t == !aln_s) &&
-                         (!aln_t || aln_off) && (!t2s || t2s_off);
+    const bool outs_ok = (!aln_t == !aln_s) && (!aln_t || aln_off) && (!t2s || t2s_off);
     const PairText tx{aln_t, aln_s, aln_off, aln_len, t2s, t2s_off, t2s_len, tolerance};
-    return pair_smart_run(ctx, "rf_pair_align_text", args_ok, npairs, seq, tpl, bw, threshold, fixed, max_doublings,
+    return pair_smart_run(ctx, "rf_pair_align_text", outs_ok, npairs, seq, tpl, bw, threshold, fixed, max_doublings,
                           flags, out_score, nullptr, nullptr, nullptr, nerrors, out_bw, out_rounds, &tx);
 }
 
@@ -7954,27 +8047,27 @@ int rf_last_pair_align_ms(const rf_ctx *ctx, double *fill_ms, double *walk_ms)
     return 0;
 }
 
-// Launch the backtraces of `tasks` (moves into scratch[3] at t.out, counts in
-// scratch[4]) in k_bt_win (round 4: codon alignments and bands of any height
+// Launch the backtraces of `tasks` (moves into BUF_MOVES_OR_CTASKS at t.out,
+// counts in BUF_COUNTS_OR_PROPS) in k_bt_win (round 4: codon alignments and bands of any height
 // too); with d_mask, the walks also mark alignment proposals.
 static int launch_backtraces(rf_ctx *ctx, std::vector<BTTask> &tasks, uint8_t *d_mask, int do_indels)
 {
     const int32_t nslots = (int32_t)tasks.size();
     std::vector<BTTask> &win = ctx->bt_win;   // alive until the caller's sync
     win = tasks;
-    int32_t *d_cnt = (int32_t *)ctx->scratch[4].p;
+    int32_t *d_cnt = dev<int32_t>(ctx, BUF_COUNTS_OR_PROPS);
     HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
     if (!win.empty()) {
-        if (int e = upload(ctx, ctx->scratch[16], win))
+        if (int e = upload(ctx, ctx->scratch[BUF_BT_TASKS], win))
             return e;
         // a launch of few walks (the reference's, edit_distance's: one
         // latency-bound walk each) runs each walk on 4 waves (NW = 4)
         const bool few = win.size() <= (size_t)BTW_FEW && ctx->opt.bt_nw != 1;
         auto kern = few ? k_bt_win<4096, 4> : ctx->opt.bt_win_kb == 16 ? k_bt_win<2048> : k_bt_win<4096>;
         hipLaunchKernelGGL(kern, dim3((unsigned)win.size()), dim3(few ? 256 : 64), 0, ctx->stream,
-                           (const BTTask *)ctx->scratch[16].p, (const uint8_t *)ctx->bytes_arena.d,
+                           dev<const BTTask>(ctx, BUF_BT_TASKS), (const uint8_t *)ctx->bytes_arena.d,
                            (const double *)ctx->tab_arena.d, (const double *)ctx->band_arena.d,
-                           (int8_t *)ctx->scratch[3].p, d_cnt, d_cnt + nslots, ctx->d_err, d_mask, do_indels);
+                           dev<int8_t>(ctx, BUF_MOVES_OR_CTASKS), d_cnt, d_cnt + nslots, ctx->d_err, d_mask, do_indels);
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
@@ -8003,14 +8096,14 @@ static int build_bt_tasks(rf_ctx *ctx, const char *fn, int32_t nslots, const int
         const Band &b = ctx->slots[slot[k]].a;
         BTTask &t = tasks[k] = slot_desc<BTTask>(ctx, slot[k]);
         t.out = total;
-        t.flags = (b.flags & RF_SKEW ? 2 : 0) | (b.flags & RF_TRIM ? 4 : 0);
+        t.flags = fill_flags(b.flags);
         t.idx = k;
         offs[k] = total;
         total += b.n + b.m;
     }
-    if (int e = ensure_buf(ctx, ctx->scratch[3], std::max<int64_t>(total, 16)))
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_MOVES_OR_CTASKS], std::max<int64_t>(total, 16)))
         return e;
-    if (int e = ensure_buf(ctx, ctx->scratch[4], sizeof(int32_t) * 2 * std::max(nslots, 1)))
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_COUNTS_OR_PROPS], sizeof(int32_t) * 2 * std::max(nslots, 1)))
         return e;
     return 0;
 }
@@ -8026,7 +8119,7 @@ int rf_backtrace(rf_ctx *ctx, int32_t nslots, const int32_t *slot, int8_t *moves
     if (int e = build_bt_tasks(ctx, "rf_backtrace", nslots, slot, tasks, offs))
         return e;
     const int64_t total = nslots > 0 ? offs[nslots - 1] + tasks[nslots - 1].n + tasks[nslots - 1].m : 0;
-    int32_t *d_cnt = (int32_t *)ctx->scratch[4].p;
+    int32_t *d_cnt = dev<int32_t>(ctx, BUF_COUNTS_OR_PROPS);
     if (nslots > 0)
         if (int e = launch_backtraces(ctx, tasks, nullptr, 0))
             return e;
@@ -8041,7 +8134,8 @@ int rf_backtrace(rf_ctx *ctx, int32_t nslots, const int32_t *slot, int8_t *moves
         HIPCHK(ctx, hipMemcpyAsync((void *)cnt, d_cnt, sizeof(int32_t) * 2 * nslots, hipMemcpyDeviceToHost,
                                    ctx->stream));
     if (moves && total > 0)
-        HIPCHK(ctx, hipMemcpyAsync((void *)all, ctx->scratch[3].p, total, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync((void *)all, ctx->scratch[BUF_MOVES_OR_CTASKS].p, total, hipMemcpyDeviceToHost,
+                                   ctx->stream));
     HIPCHK(ctx, land_err(ctx));
     HIPCHK(ctx, stream_wait(ctx));
     if (nslots > 0)
@@ -8087,18 +8181,18 @@ int rf_alignment_proposals(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off
     }
     if (nslots == 0)
         return 0;
-    if (int e = ensure_buf(ctx, ctx->scratch[2], std::max<int64_t>(mask_total, 16)))
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_READS_OR_MASK], std::max<int64_t>(mask_total, 16)))
         return e;
-    HIPCHK(ctx, hipMemsetAsync(ctx->scratch[2].p, 0, mask_total, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->scratch[BUF_READS_OR_MASK].p, 0, mask_total, ctx->stream));
     // 2. the walks mark the mask as they go
-    if (int e = launch_backtraces(ctx, tasks, (uint8_t *)ctx->scratch[2].p, do_indels ? 1 : 0))
+    if (int e = launch_backtraces(ctx, tasks, dev<uint8_t>(ctx, BUF_READS_OR_MASK), do_indels ? 1 : 0))
         return e;
     HIPCHK(ctx, hipGetLastError());
     if (int e = ensure_hdn(ctx, mask_total))
         return e;
     HIPCHK(ctx, pre_d2h(ctx));
-    HIPCHK(ctx, hipMemcpyAsync((char *)ctx->hdn + HDN_RES, ctx->scratch[2].p, mask_total, hipMemcpyDeviceToHost,
-                               ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync((char *)ctx->hdn + HDN_RES, ctx->scratch[BUF_READS_OR_MASK].p, mask_total,
+                               hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, land_err(ctx));
     HIPCHK(ctx, stream_wait(ctx));
     note_bt_ms(ctx);
@@ -8174,15 +8268,15 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
         }
 
     // uploads
-    if (int e = upload(ctx, ctx->scratch[0], items)) return e;
-    if (int e = upload(ctx, ctx->scratch[1], groups)) return e;
-    if (int e = upload(ctx, ctx->scratch[2], P.reads)) return e;
-    if (int e = upload(ctx, ctx->scratch[3], ctasks)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_SCORE_ITEMS], items)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_SCORE_GROUPS], groups)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_READS_OR_MASK], P.reads)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_MOVES_OR_CTASKS], ctasks)) return e;
     // proposal arrays + per-group flags + gstart
     const size_t pbytes = align_up(nprops * 4, 256) * 2 + align_up(nprops, 256) * 2 +
                           align_up(ngroups * 4, 256) * 2 + align_up((ngroups + 1) * 8, 256);
-    if (int e = ensure_buf(ctx, ctx->scratch[4], pbytes + 256)) return e;
-    char *pb = (char *)ctx->scratch[4].p;
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_COUNTS_OR_PROPS], pbytes + 256)) return e;
+    char *pb = dev<char>(ctx, BUF_COUNTS_OR_PROPS);
     int32_t *d_pgroup = (int32_t *)pb;  pb += align_up(nprops * 4, 256);
     int32_t *d_pos = (int32_t *)pb;     pb += align_up(nprops * 4, 256);
     uint8_t *d_kind = (uint8_t *)pb;    pb += align_up(nprops, 256);
@@ -8191,7 +8285,7 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
     int32_t *d_href = (int32_t *)pb;    pb += align_up(ngroups * 4, 256);
     int64_t *d_gstart = (int64_t *)pb;
     // the seven arrays in their device layout: one copy out of the ring
-    const size_t pused = (size_t)((char *)(d_gstart + ngroups + 1) - (char *)ctx->scratch[4].p);
+    const size_t pused = (size_t)((char *)(d_gstart + ngroups + 1) - dev<char>(ctx, BUF_COUNTS_OR_PROPS));
     char *h;
     if (int e = ring_take(ctx, pused, &h))
         return e;
@@ -8199,7 +8293,7 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
         if (!n)
             return hipSuccess;
         if (h) {
-            std::memcpy(h + ((char *)d - (char *)ctx->scratch[4].p), src, n);
+            std::memcpy(h + ((char *)d - dev<char>(ctx, BUF_COUNTS_OR_PROPS)), src, n);
             return hipSuccess;
         }
         return hipMemcpyAsync(d, src, n, hipMemcpyHostToDevice, ctx->stream);
@@ -8216,14 +8310,14 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
         HIPCHK(ctx, put(d_gstart, P.gstart.data(), (ngroups + 1) * 8));
     }
     if (h && (nprops > 0 || ngroups > 0))
-        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[4].p, h, pused, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_COUNTS_OR_PROPS].p, h, pused, hipMemcpyHostToDevice, ctx->stream));
     // work buffers: dense totals, split partials, codon scratch + outputs, final totals
     const size_t wbytes = align_up(std::max<int64_t>(dense_total, 1) * 8, 256) +
                           (split ? align_up(std::max<int64_t>(split_total, 1) * 8, 256) : 0) +
                           align_up(std::max<int64_t>(scratch_total, 1) * 8, 256) +
                           2 * align_up(std::max<int64_t>(nprops, 1) * 8, 256);
-    if (int e = ensure_buf(ctx, ctx->scratch[5], wbytes)) return e;
-    char *wb = (char *)ctx->scratch[5].p;
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_SEGS_OR_WORK], wbytes)) return e;
+    char *wb = dev<char>(ctx, BUF_SEGS_OR_WORK);
     double *d_dense = (double *)wb;   wb += align_up(std::max<int64_t>(dense_total, 1) * 8, 256);
     double *d_split = nullptr;
     if (split) { d_split = (double *)wb; wb += align_up(std::max<int64_t>(split_total, 1) * 8, 256); }
@@ -8239,22 +8333,22 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
     unsigned gy = 0;
     if (!items.empty()) {
         gy = launch_scorer(ctx, P.pick, (unsigned)items.size(), split ? (unsigned)P.max_reads : 1u,
-                           (const WorkItem *)ctx->scratch[0].p, (const ScoreGroup *)ctx->scratch[1].p,
-                           (const ScoreRead *)ctx->scratch[2].p, d_dense, d_split);
+                           dev<const WorkItem>(ctx, BUF_SCORE_ITEMS), dev<const ScoreGroup>(ctx, BUF_SCORE_GROUPS),
+                           dev<const ScoreRead>(ctx, BUF_READS_OR_MASK), d_dense, d_split);
         if (split && dense_total > 0)
             hipLaunchKernelGGL(k_reduce, dim3((unsigned)((dense_total + 255) / 256)), dim3(256), 0,
-                               ctx->stream, (const ScoreGroup *)ctx->scratch[1].p, ngroups, d_gstart,
+                               ctx->stream, dev<const ScoreGroup>(ctx, BUF_SCORE_GROUPS), ngroups, d_gstart,
                                dense_total, d_split, d_dense);
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev_codon, ctx->stream));
     if (!ctasks.empty())
         hipLaunchKernelGGL(k_codon, dim3((unsigned)((ctasks.size() + 63) / 64)), dim3(64), 0,
-                           ctx->stream, (const CodonTask *)ctx->scratch[3].p, (int)ctasks.size(),
+                           ctx->stream, dev<const CodonTask>(ctx, BUF_MOVES_OR_CTASKS), (int)ctasks.size(),
                            d_bases, d_tabs, d_bands, d_cscr, d_ref);
     HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     if (nprops > 0)
         hipLaunchKernelGGL(k_gather, dim3((unsigned)((nprops + 255) / 256)), dim3(256), 0, ctx->stream,
-                           nprops, d_pgroup, d_kind, d_pos, d_base, (const ScoreGroup *)ctx->scratch[1].p,
+                           nprops, d_pgroup, d_kind, d_pos, d_base, dev<const ScoreGroup>(ctx, BUF_SCORE_GROUPS),
                            d_hr, d_dense, d_ref, d_href, d_out, ctx->d_err);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
@@ -8348,10 +8442,10 @@ static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_of
             C.valid = false;
             if (score_plan(in, gin, ctx->opt, false, P))
                 return fail(ctx, RF_ERR_ARG, "rf_score_dense: empty group");
-            if (int e = upload(ctx, ctx->scratch[11], P.items)) return e;
-            if (int e = upload(ctx, ctx->scratch[12], P.groups)) return e;
-            if (int e = upload(ctx, ctx->scratch[13], P.reads)) return e;
-            if (int e = upload(ctx, ctx->scratch[14], P.gstart)) return e;
+            if (int e = upload(ctx, ctx->scratch[BUF_DENSE_ITEMS], P.items)) return e;
+            if (int e = upload(ctx, ctx->scratch[BUF_DENSE_GROUPS], P.groups)) return e;
+            if (int e = upload(ctx, ctx->scratch[BUF_DENSE_READS], P.reads)) return e;
+            if (int e = upload(ctx, ctx->scratch[BUF_DENSE_GSTART], P.gstart)) return e;
             C.valid = true;
             C.gen = ctx->layout_gen;
             C.ngroups = ngroups;
@@ -8363,24 +8457,25 @@ static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_of
     }
     const size_t nitems = P.items.size();
     const bool split = score_split((int64_t)nitems, P.max_reads, ctx->opt.score_mode, false);
-    if (int e = ensure_buf(ctx, ctx->scratch[15], sizeof(double) * std::max<int64_t>(P.dense_total, 1)))
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_DENSE_TOTALS], sizeof(double) * std::max<int64_t>(P.dense_total, 1)))
         return e;
     if (split)
-        if (int e = ensure_buf(ctx, ctx->scratch[10], sizeof(double) * std::max<int64_t>(P.split_total, 1)))
+        if (int e = ensure_buf(ctx, ctx->scratch[BUF_RING_OR_SPLIT],
+                               sizeof(double) * std::max<int64_t>(P.split_total, 1)))
             return e;
-    double *d_dense = (double *)ctx->scratch[15].p;
+    double *d_dense = dev<double>(ctx, BUF_DENSE_TOTALS);
     HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     unsigned gy = 0;
     if (nitems) {
         gy = launch_scorer(ctx, P.pick, (unsigned)nitems, split ? (unsigned)P.max_reads : 1u,
-                           (const WorkItem *)ctx->scratch[11].p, (const ScoreGroup *)ctx->scratch[12].p,
-                           (const ScoreRead *)ctx->scratch[13].p, d_dense,
-                           split ? (double *)ctx->scratch[10].p : nullptr);
+                           dev<const WorkItem>(ctx, BUF_DENSE_ITEMS), dev<const ScoreGroup>(ctx, BUF_DENSE_GROUPS),
+                           dev<const ScoreRead>(ctx, BUF_DENSE_READS), d_dense,
+                           split ? dev<double>(ctx, BUF_RING_OR_SPLIT) : nullptr);
         if (split)
             hipLaunchKernelGGL(k_reduce, dim3((unsigned)((P.dense_total + 255) / 256)), dim3(256), 0,
-                               ctx->stream, (const ScoreGroup *)ctx->scratch[12].p, ngroups,
-                               (const int64_t *)ctx->scratch[14].p, P.dense_total,
-                               (const double *)ctx->scratch[10].p, d_dense);
+                               ctx->stream, dev<const ScoreGroup>(ctx, BUF_DENSE_GROUPS), ngroups,
+                               dev<const int64_t>(ctx, BUF_DENSE_GSTART), P.dense_total,
+                               dev<const double>(ctx, BUF_RING_OR_SPLIT), d_dense);
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
@@ -8438,12 +8533,12 @@ int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
                 return fail(ctx, RF_ERR_ARG, "rf_score_dense_ref: reference uses a different template");
         }
     }
-    // the reads' fold: totals in scratch[15]
+    // the reads' fold: totals in BUF_DENSE_TOTALS
     if (int e = score_dense_impl(ctx, ngroups, slot_off, slots, nullptr, hipMemcpyDeviceToHost))
         return e;
     const ScorePlan &P = ctx->dplan.plan;
     ctx->codon_dense_ms = 0;
-    double *d_dense = (double *)ctx->scratch[15].p;
+    double *d_dense = dev<double>(ctx, BUF_DENSE_TOTALS);
     if (any_ref) {
         std::vector<CodonDenseGroup> cg;
         int64_t nblk = 0;
@@ -8458,10 +8553,10 @@ int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
         }
         if (nblk > INT32_MAX)
             return fail(ctx, RF_ERR_ARG, "rf_score_dense_ref: too many slots for one launch");
-        if (int e = upload(ctx, ctx->scratch[34], cg)) return e;
+        if (int e = upload(ctx, ctx->scratch[BUF_CODON_GROUPS], cg)) return e;
         HIPCHK(ctx, hipEventRecord(ctx->ev_codon, ctx->stream));
         hipLaunchKernelGGL(k_codon_dense, dim3((unsigned)nblk), dim3(64), 0, ctx->stream,
-                           (const CodonDenseGroup *)ctx->scratch[34].p, (int)cg.size(),
+                           dev<const CodonDenseGroup>(ctx, BUF_CODON_GROUPS), (int)cg.size(),
                            (const uint8_t *)ctx->bytes_arena.d, (const double *)ctx->tab_arena.d,
                            (const double *)ctx->band_arena.d, d_dense);
         HIPCHK(ctx, hipGetLastError());
@@ -8619,7 +8714,7 @@ int rf_last_timing(const rf_ctx *ctx, double *dp_ms, double *score_ms, double *g
 // alignment_error_probs's per-column sums on the device (k_aln_sums) for
 // rf_aln_error_sums (rifraf_batch.cpp): returns 1 (nothing done) when a read
 // has no row codes -- the caller then folds the moves on the host.  out NULL:
-// the sums stay on the device (scratch[19], rf_qv_probs).  A launch
+// the sums stay on the device (BUF_ALN_SUMS, rf_qv_probs).  A launch
 // whose largest group has more than ALN_MARKS_MIN_READS reads uses
 // k_aln_marks + k_aln_fold (RF_OPT_ALN_MARKS_MIN; tests set 0: always).
 int rf_internal_aln_sums_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
@@ -8665,9 +8760,9 @@ int rf_internal_aln_sums_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_o
     if (ns > 0)
         if (int e = launch_backtraces(ctx, tasks, nullptr, 0))
             return e;
-    if (int e = upload(ctx, ctx->scratch[17], rd)) return e;
-    if (int e = upload(ctx, ctx->scratch[18], gr)) return e;
-    if (int e = ensure_buf(ctx, ctx->scratch[19], (size_t)std::max<int64_t>(rows * 4 * 8, 16))) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_ALN_READS], rd)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_ALN_GROUPS], gr)) return e;
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_ALN_SUMS], (size_t)std::max<int64_t>(rows * 4 * 8, 16))) return e;
     int maxr = 0;
     for (int32_t g = 0; g < ngroups; ++g)
         maxr = std::max(maxr, slot_off[g + 1] - slot_off[g]);
@@ -8685,36 +8780,38 @@ int rf_internal_aln_sums_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_o
             }
         }
         gcol[ngroups] = nc;
-        if (int e = upload(ctx, ctx->scratch[21], rbase)) return e;
-        if (int e = upload(ctx, ctx->scratch[22], gcol)) return e;
-        if (int e = upload(ctx, ctx->scratch[23], gbase)) return e;
-        if (int e = ensure_buf(ctx, ctx->scratch[24], (size_t)std::max<int64_t>(nm * 4, 16))) return e;
-        HIPCHK(ctx, hipMemsetAsync(ctx->scratch[24].p, 0, (size_t)nm * 4, ctx->stream));
+        if (int e = upload(ctx, ctx->scratch[BUF_ALN_READ_BASE], rbase)) return e;
+        if (int e = upload(ctx, ctx->scratch[BUF_ALN_GROUP_COL], gcol)) return e;
+        if (int e = upload(ctx, ctx->scratch[BUF_ALN_GROUP_BASE], gbase)) return e;
+        if (int e = ensure_buf(ctx, ctx->scratch[BUF_ALN_MARKS], (size_t)std::max<int64_t>(nm * 4, 16))) return e;
+        HIPCHK(ctx, hipMemsetAsync(ctx->scratch[BUF_ALN_MARKS].p, 0, (size_t)nm * 4, ctx->stream));
         hipLaunchKernelGGL(k_aln_marks, dim3((unsigned)ns), dim3(64), 0, ctx->stream,
-                           (const AlnSumGroup *)ctx->scratch[18].p, ngroups, (const AlnSumRead *)ctx->scratch[17].p,
-                           (const int64_t *)ctx->scratch[21].p, (const double *)ctx->tab_arena.d,
-                           (const int8_t *)ctx->scratch[3].p, (const int32_t *)ctx->scratch[4].p,
-                           (uint32_t *)ctx->scratch[24].p);
+                           dev<const AlnSumGroup>(ctx, BUF_ALN_GROUPS), ngroups,
+                           dev<const AlnSumRead>(ctx, BUF_ALN_READS),
+                           dev<const int64_t>(ctx, BUF_ALN_READ_BASE), (const double *)ctx->tab_arena.d,
+                           dev<const int8_t>(ctx, BUF_MOVES_OR_CTASKS), dev<const int32_t>(ctx, BUF_COUNTS_OR_PROPS),
+                           dev<uint32_t>(ctx, BUF_ALN_MARKS));
         if (nc > 0)
             hipLaunchKernelGGL(k_aln_fold, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ctx->stream,
-                               (const AlnSumGroup *)ctx->scratch[18].p, ngroups, (const int64_t *)ctx->scratch[22].p,
-                               (const int64_t *)ctx->scratch[23].p, (const uint32_t *)ctx->scratch[24].p,
-                               (const double *)D.lut.p, (const double *)D.errlut.p, (double *)ctx->scratch[19].p, nc);
+                               dev<const AlnSumGroup>(ctx, BUF_ALN_GROUPS), ngroups,
+                               dev<const int64_t>(ctx, BUF_ALN_GROUP_COL),
+                               dev<const int64_t>(ctx, BUF_ALN_GROUP_BASE), dev<const uint32_t>(ctx, BUF_ALN_MARKS),
+                               (const double *)D.lut.p, (const double *)D.errlut.p, dev<double>(ctx, BUF_ALN_SUMS), nc);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, pre_d2h(ctx));
         if (out)
-            HIPCHK(ctx, hipMemcpyAsync(out, ctx->scratch[19].p, (size_t)rows * 4 * 8, hipMemcpyDeviceToHost,
+            HIPCHK(ctx, hipMemcpyAsync(out, ctx->scratch[BUF_ALN_SUMS].p, (size_t)rows * 4 * 8, hipMemcpyDeviceToHost,
                                        ctx->stream));
     } else if (ngroups > 0) {
         hipLaunchKernelGGL(k_aln_sums, dim3((unsigned)ngroups), dim3(256), 0, ctx->stream,
-                           (const AlnSumGroup *)ctx->scratch[18].p, (const AlnSumRead *)ctx->scratch[17].p,
-                           (const double *)ctx->tab_arena.d, (const int8_t *)ctx->scratch[3].p,
-                           (const int32_t *)ctx->scratch[4].p, (const double *)D.lut.p, (const double *)D.errlut.p,
-                           (double *)ctx->scratch[19].p);
+                           dev<const AlnSumGroup>(ctx, BUF_ALN_GROUPS), dev<const AlnSumRead>(ctx, BUF_ALN_READS),
+                           (const double *)ctx->tab_arena.d, dev<const int8_t>(ctx, BUF_MOVES_OR_CTASKS),
+                           dev<const int32_t>(ctx, BUF_COUNTS_OR_PROPS), (const double *)D.lut.p,
+                           (const double *)D.errlut.p, dev<double>(ctx, BUF_ALN_SUMS));
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, pre_d2h(ctx));
         if (out)
-            HIPCHK(ctx, hipMemcpyAsync(out, ctx->scratch[19].p, (size_t)rows * 4 * 8, hipMemcpyDeviceToHost,
+            HIPCHK(ctx, hipMemcpyAsync(out, ctx->scratch[BUF_ALN_SUMS].p, (size_t)rows * 4 * 8, hipMemcpyDeviceToHost,
                                        ctx->stream));
     }
     HIPCHK(ctx, stream_wait(ctx));
@@ -8865,10 +8962,10 @@ extern "C" int rf_qv_probs(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off
     if (ngroups == 0)
         return 0;
     (void)hipSetDevice(ctx->device);
-    // 1. dense totals, kept on the device (scratch[15], dplan's group offsets)
+    // 1. dense totals, kept on the device (BUF_DENSE_TOTALS, dplan's group offsets)
     if (int e = score_dense_impl(ctx, ngroups, slot_off, slots, nullptr, hipMemcpyDeviceToHost))
         return e;
-    // 2. the alignment sums, kept on the device (scratch[19]); 1 = a read
+    // 2. the alignment sums, kept on the device (BUF_ALN_SUMS); 1 = a read
     //    without row codes: the caller takes the host path
     if (int e = rf_internal_aln_sums_dev(ctx, ngroups, slot_off, slots, tlen, nullptr))
         return e;
@@ -8888,14 +8985,14 @@ extern "C" int rf_qv_probs(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off
         q.m = tlen[g];
         rows += tlen[g];
     }
-    if (int e = upload(ctx, ctx->scratch[25], gq)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_QV_GROUPS], gq)) return e;
     const size_t npos = (size_t)rows * 5, nins = (size_t)(rows + ngroups) * 4, naln = (size_t)rows;
     const size_t ob = align_up((npos + nins + naln) * 8, 256);
-    if (int e = ensure_buf(ctx, ctx->scratch[26], ob + (size_t)ngroups * 4)) return e;
-    double *d_pos = (double *)ctx->scratch[26].p, *d_ins = d_pos + npos, *d_aln = d_ins + nins;
-    int32_t *d_gerr = (int32_t *)((char *)ctx->scratch[26].p + ob);
-    hipLaunchKernelGGL(k_qv, dim3((unsigned)ngroups), dim3(256), 0, ctx->stream, (const QvGroup *)ctx->scratch[25].p,
-                       (const double *)ctx->scratch[15].p, (const double *)ctx->scratch[19].p,
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_QV_OUT], ob + (size_t)ngroups * 4)) return e;
+    double *d_pos = dev<double>(ctx, BUF_QV_OUT), *d_ins = d_pos + npos, *d_aln = d_ins + nins;
+    int32_t *d_gerr = (int32_t *)(dev<char>(ctx, BUF_QV_OUT) + ob);
+    hipLaunchKernelGGL(k_qv, dim3((unsigned)ngroups), dim3(256), 0, ctx->stream, dev<const QvGroup>(ctx, BUF_QV_GROUPS),
+                       dev<const double>(ctx, BUF_DENSE_TOTALS), dev<const double>(ctx, BUF_ALN_SUMS),
                        (const uint8_t *)ctx->bytes_arena.d, d_pos, d_ins, d_aln, d_gerr);
     HIPCHK(ctx, hipGetLastError());
     std::vector<int32_t> gerr(ngroups);
