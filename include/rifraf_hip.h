@@ -219,7 +219,16 @@ int rf_code_stats(const rf_ctx *ctx, int64_t *entries3, int64_t *entries1, int64
  *   del      at off[k]+k .. off[k+1]+k+1         (n_k+1, :49-53)
  *   cins     cins_off[k]..cins_off[k+1]           (n_k-2 or 0, :57-64)
  *   cdel     cdel_off[k]..cdel_off[k+1]           (n_k+1 or 0, :65-72)
- * cins/cdel/cins_off/cdel_off may be NULL (no codon moves). */
+ * cins/cdel/cins_off/cdel_off may be NULL (no codon moves).
+ * Refusals change nothing.  All three upload calls check their pointers and
+ * every sequence's lengths (n_k >= 1, cins 0 or n_k - 2 entries, cdel 0 or
+ * n_k + 1) before their first state change: after RF_ERR_ARG the ids, their
+ * tables and row codes, the code dictionary (rf_code_stats) and the bands
+ * filled from the ids are as before the call, and still readable.  So are
+ * they after rf_set_sequences_codes(_prep)'s RF_ERR_STATE ("row-code
+ * dictionary full").  Any other failure (RF_ERR_HIP: an allocation, a HIP
+ * error) comes after that point: the ids it named are then unknown to
+ * rf_realign and their bands stale, until a later upload of them succeeds. */
 int rf_set_sequences(rf_ctx *ctx, int32_t first, int32_t nseq,
                      const uint8_t *bases, const int64_t *off,
                      const double *match, const double *mismatch,
@@ -717,6 +726,36 @@ int rf_host_score_plan(int32_t nreads, const int32_t *n, const int32_t *m, const
                        const int32_t *opt_key, const int32_t *opt_val, int32_t per_seq, int32_t empty_ok,
                        int32_t *pick, int32_t *split, int32_t item_cap, int32_t *items, int32_t *nitems,
                        int64_t *dense_off, int64_t *split_off);
+
+/* The row codes of rf_set_sequences on the host alone: no context, no GPU
+ * (csrc/rifraf_seq_upload.h, DESIGN.md §4 "Sequence uploads").  nseq sequences
+ * in rf_set_sequences' layout (bases, match, mismatch, ins at off[k], del at
+ * off[k] + k; codon tables do not enter the records) are coded as nup uploads,
+ * upload u the sequences [up[u], up[u + 1]) (up[0] = 0, up[nup] = nseq), on
+ * nthreads host threads and a dictionary of the call's own.  flags[u] bit 0:
+ * the upload starts a fresh dictionary (as one that replaces every coded
+ * sequence of a context); bit 1: its dictionary entries are undone after it,
+ * as rf_set_sequences_codes does when it refuses.  Outputs: per sequence
+ * coded (a full dictionary leaves it 0) and finite (no non-finite value among
+ * its 4 n + 1 table values); one 8-B record per position, at off[k] - off[0]
+ * (bits 0-15 the code of (match, mismatch, ins)[i], 16-31 / 32-47 the codes of
+ * del[i] / del[i + 1], 48-55 the base; zeros for an uncoded sequence); the
+ * dictionary's values after the last upload, val3 (4 doubles per triple code:
+ * match, mismatch, ins, 0) and val1 (a del value per code), each with room
+ * for 65,536 codes; sizes[3] = triple codes, del codes, reads left uncoded.
+ * The records and values do not depend on nthreads. */
+int rf_host_row_codes(int32_t nseq, const uint8_t *bases, const int64_t *off, const double *match,
+                      const double *mismatch, const double *ins, const double *del, int32_t nup, const int32_t *up,
+                      const uint8_t *flags, int32_t nthreads, uint8_t *coded, uint8_t *finite, uint64_t *records,
+                      double *val3, double *val1, int64_t *sizes);
+/* The staging chunks of one upload of nseq sequences (off, cins_off, cdel_off
+ * as rf_set_sequences'; codes != 0: rf_set_sequences_codes', no codon tables)
+ * at RF_OPT_STAGE_KB = stage_kb, or within `budget` bytes when that is
+ * positive: end[c] is one past the last sequence of chunk c (room for nseq),
+ * *nchunks their number.  A chunk takes one sequence, then further ones while
+ * its staged bytes fit the budget. */
+int rf_host_upload_chunks(int32_t nseq, const int64_t *off, const int64_t *cins_off, const int64_t *cdel_off,
+                          int32_t codes, int32_t stage_kb, int64_t budget, int32_t *end, int32_t *nchunks);
 
 #ifdef __cplusplus
 }

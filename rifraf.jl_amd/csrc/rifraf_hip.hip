@@ -61,6 +61,7 @@
 #include "../../include/rifraf_hip.h"
 #include "rifraf_dp_plan.h"
 #include "rifraf_score_plan.h"
+#include "rifraf_seq_upload.h"
 
 #define RF_INF (__builtin_inf())
 
@@ -100,9 +101,7 @@ __device__ __forceinline__ size_t bidx(int d, int jj, int P)
 // device-side descriptors
 // ---------------------------------------------------------------------
 
-constexpr int RF_CODES = 1 << 16;   // entries of the row codes' dictionary (DPTask: rifraf_dp_plan.h)
-// doubles from a read's table start to its row-code records
-__host__ __device__ inline int64_t row_code_off(int64_t n, int64_t nci, int64_t ncd) { return 4 * n + 1 + nci + ncd; }
+// RF_CODES, row_code_off, seq_table_len: rifraf_seq_upload.h
 
 // ScoreRead, ScoreGroup, WorkItem: rifraf_score_plan.h
 
@@ -5468,7 +5467,7 @@ struct DevBuf {
 // never have work in flight at once: a buffer with two users (X_OR_Y) holds
 // one content at a time, in stream order.  A new user takes a new enumerator.
 // The wait is each call's own stream_wait after its last launch or copy that
-// touches a buffer: upload_sequence_chunk, rf_set_sequences_codes (after every
+// touches a buffer: tables_chunk and set_sequences_codes_impl (after every
 // chunk) and rf_set_templates*; realign_run; pair_download, for every set;
 // rf_backtrace, rf_alignment_proposals, rf_score, score_dense_impl,
 // rf_score_dense_ref, rf_internal_aln_sums_dev and rf_qv_probs.  Nothing else
@@ -5489,16 +5488,16 @@ enum Buf : int {
     // kind, base, the per-group flags and gstart (counts).
     BUF_MOVES_OR_CTASKS,
     BUF_COUNTS_OR_PROPS,
-    // Segment of the sequence and template uploads (upload_sequence_chunk,
-    // rf_set_sequences_codes, rf_set_templates*); upload_sequence_chunk uses it
-    // twice and waits for the stream in between | rf_score: its work block
+    // Segment of the sequence and template uploads (scatter_staged, for
+    // tables_chunk, set_sequences_codes_impl and rf_set_templates*);
+    // tables_chunk uses it twice and waits for the stream in between | rf_score: its work block
     // (dense totals, split partials, k_codon's columns and outputs, totals)
     BUF_SEGS_OR_WORK,
-    // upload_sequence_chunk: the staged tables | rf_set_sequences_codes:
-    // CodeSeq; it waits for the stream after every chunk
+    // tables_chunk: the staged tables | set_sequences_codes_impl: CodeSeq;
+    // each waits for the stream after every chunk
     BUF_TABS_OR_CSEQS,
     // the staged bases of the sequence and template uploads (with
-    // rf_set_sequences_codes, the codes behind them) | launch_dp: the sink the
+    // set_sequences_codes_impl, the codes behind them) | launch_dp: the sink the
     // lean kernels' padding tasks store to (written, never read)
     BUF_BYTES_OR_SINK,
     BUF_DP_TASKS,    // rf_realign: DPTask in device order; kept while rf_ctx::rplan is valid
@@ -5523,7 +5522,7 @@ enum Buf : int {
     // (k_aln_fold / k_aln_sums), downloaded by it or read by rf_qv_probs' k_qv
     // -- inside the rf_qv_probs call that ran it, on the stream.
     BUF_ALN_SUMS,
-    BUF_CODE_LUTS,   // rf_set_sequences_codes: CodeLut
+    BUF_CODE_LUTS,   // set_sequences_codes_impl: CodeLut (code_tables)
     // rf_internal_aln_sums_dev's two-launch path: the reads' mark offsets, the
     // groups' column and mark offsets, the marks
     BUF_ALN_READ_BASE,
@@ -5575,109 +5574,11 @@ int rf_internal_host_threads()
 
 namespace {
 inline int host_threads() { return rf_internal_host_threads(); }
-template <class F>
-void parallel_for(int nth, F fn)
-{
-    if (nth <= 1) {
-        fn(0);
-        return;
-    }
-    std::vector<std::thread> th;
-    for (int t = 1; t < nth; ++t)
-        th.emplace_back(fn, t);
-    fn(0);
-    for (auto &x : th)
-        x.join();
-}
-
-// Code dictionary of the row codes (RF_TASK_CODED): every distinct
-// (match, mismatch, ins) triple and del value of the context's reads gets a
-// 16-bit code, first come first served, keyed by the exact bit patterns.  A
-// read whose values would need a code past RF_CODES - 1 stays uncoded (its
-// DP reads the tables directly; counted in `uncoded_reads`, rf_code_stats).
-// Entries are only appended while any coded sequence outside an upload is
-// still valid, so codes of earlier reads stay valid; an upload that replaces
-// every coded sequence of the context starts a fresh dictionary, so a
-// long-lived context refilled batch after batch does not fill it up.  `lut`
-// is the device copy (RF_CODES x 4 triple doubles, then RF_CODES del doubles).
-struct CodeDict {
-    struct K3 {
-        uint64_t a, b, c;
-        bool operator==(const K3 &o) const { return a == o.a && b == o.b && c == o.c; }
-    };
-    struct H3 {
-        size_t operator()(const K3 &k) const
-        {
-            return (size_t)((k.a * 0x9E3779B97F4A7C15ull) ^ (k.b * 0xC2B2AE3D27D4EB4Full) ^ (k.c * 0x165667B19E3779F9ull));
-        }
-    };
-    std::unordered_map<K3, uint32_t, H3> t3;
-    std::unordered_map<uint64_t, uint32_t> d1;
-    std::vector<double> t3v, d1v;   // host copies of the entries
-    size_t up3 = 0, up1 = 0;        // entries already on the device
-    int64_t uncoded_reads = 0;      // reads left uncoded because the dictionary was full
-    int64_t resets = 0;
-    DevBuf lut;
-    // per triple entry: log10(1 - 10^match) - log10(3), the off-base value of
-    // base_distribution (model.jl:804-809), host libm; device copy errlut
-    std::vector<double> errv;
-    size_t uperr = 0;
-    DevBuf errlut;
-
-    void reset()
-    {
-        t3.clear();
-        d1.clear();
-        t3v.clear();
-        d1v.clear();
-        errv.clear();
-        up3 = up1 = uperr = 0;
-        ++resets;
-    }
-
-    static uint64_t bits(double x)
-    {
-        uint64_t u;
-        std::memcpy(&u, &x, 8);
-        return u;
-    }
-    // read-only lookups (safe from several threads while nothing is inserted)
-    int32_t find3(const K3 &k) const
-    {
-        auto it = t3.find(k);
-        return it == t3.end() ? -1 : (int32_t)it->second;
-    }
-    int32_t find1(uint64_t k) const
-    {
-        auto it = d1.find(k);
-        return it == d1.end() ? -1 : (int32_t)it->second;
-    }
-    // per-thread direct-mapped front cache of the lookups (a read set has few
-    // distinct values; misses fall through to the maps)
-    struct Cache {
-        std::vector<std::pair<K3, int32_t>> c3 = std::vector<std::pair<K3, int32_t>>(1024, {K3{}, -2});
-        std::vector<std::pair<uint64_t, int32_t>> c1 = std::vector<std::pair<uint64_t, int32_t>>(1024, {0, -2});
-    };
-    int32_t find3(const K3 &k, Cache &C) const
-    {
-        auto &e = C.c3[(H3()(k) >> 32) & 1023];
-        if (e.second != -2 && e.first == k)
-            return e.second;
-        const int32_t v = find3(k);
-        if (v >= 0)
-            e = {k, v};
-        return v;
-    }
-    int32_t find1(uint64_t k, Cache &C) const
-    {
-        auto &e = C.c1[((k * 0x9E3779B97F4A7C15ull) >> 40) & 1023];
-        if (e.second != -2 && e.first == k)
-            return e.second;
-        const int32_t v = find1(k);
-        if (v >= 0)
-            e = {k, v};
-        return v;
-    }
+// parallel_for, CodeDict: rifraf_seq_upload.h.  The context's dictionary with
+// its device copies: `lut` (RF_CODES x 4 triple doubles, then RF_CODES del
+// doubles, filled by send_dictionary) and `errlut` (CodeDict::errv).
+struct DevCodeDict : CodeDict {
+    DevBuf lut, errlut;
 };
 
 // Tuning options (rf_set_option keys, include/rifraf_hip.h).  Every option
@@ -5716,7 +5617,7 @@ struct rf_ctx {
     Arena bytes_arena;  // sequence + template bases
     Arena tab_arena;    // sequence tables
     Arena band_arena;   // A / B bands
-    CodeDict codes;     // row-code dictionary (RF_TASK_CODED)
+    DevCodeDict codes;  // row-code dictionary (RF_TASK_CODED)
     std::vector<SeqObj> seqs;
     std::vector<TplObj> tpls;
     std::vector<Slot> slots;
@@ -6489,271 +6390,235 @@ int64_t rf_device_bytes(const rf_ctx *ctx)
     return t;
 }
 
-// rf_set_sequences's staging of sequences [k0, k1) of one call (their regions
-// exist): host tables + row codes into pinned memory, H2D, device scatter.
-int upload_sequence_chunk(rf_ctx *ctx, int32_t first, int32_t k0, int32_t k1, const uint8_t *bases,
-                          const int64_t *off, const double *match, const double *mismatch, const double *ins,
-                          const double *del, const double *cins, const int64_t *cins_off, const double *cdel,
-                          const int64_t *cdel_off)
+// ---------------------------------------------------------------------
+// Sequence uploads (DESIGN.md §4 "Sequence uploads").  rf_set_sequences and
+// rf_set_sequences_codes(_prep) are one list of steps, each written once:
+//   upload_check      the arguments and lengths: every RF_ERR_ARG comes from
+//                     here, before anything changes
+//   fresh_dictionary  a new code dictionary when nothing outside the ids is coded
+//   upload_begin      epoch, records, versions, one growth per arena, regions
+//   per chunk (chunk_end): ensure_pinned, the path's own staging and launches,
+//                     scatter_staged for the bases, and a stream_wait, since the
+//                     next chunk reuses the staging and descriptor buffers
+//   send_dictionary   new dictionary entries to the device
+//   upload_finish     valid, layout_gen
+// The host work that touches no device is rifraf_seq_upload.h's.
+// ---------------------------------------------------------------------
+
+static int upload_check(rf_ctx *ctx, const char *who, bool pointers, int32_t first, int32_t nseq, const int64_t *off,
+                        const int64_t *cins_off, const int64_t *cdel_off)
 {
-    int64_t nt = 0, nb = 0;
-    for (int32_t k = k0; k < k1; ++k) {
-        const SeqObj &S = ctx->seqs[first + k];
-        nt += row_code_off(S.n, S.ncins, S.ncdel) + S.n;
-        nb += S.n;
-    }
-    const int32_t nseq = k1 - k0;
-    const size_t stage_bytes = (size_t)std::max<int64_t>(nt, 1) * 8 + (size_t)std::max<int64_t>(nb, 1);
-    if (ctx->pinned_bytes < stage_bytes) {
-        if (ctx->pinned)
-            (void)hipHostFree(ctx->pinned);
-        ctx->pinned = nullptr;
-        ctx->pinned_bytes = 0;
-        const size_t want = std::max(stage_bytes + stage_bytes / 2, (size_t)1 << 22);
-        if (hipHostMalloc(&ctx->pinned, want, hipHostMallocDefault) != hipSuccess)
-            return fail(ctx, RF_ERR_HIP, "rf_set_sequences: pinned staging allocation failed");
-        ctx->pinned_bytes = want;
-    }
-    double *host_tabs = (double *)ctx->pinned;
-    uint8_t *host_bases = (uint8_t *)ctx->pinned + (size_t)std::max<int64_t>(nt, 1) * 8;
-    std::vector<Segment> sb(nseq), st(nseq);
-    std::vector<int64_t> at(nseq + 1, 0);
+    if (!ctx || first < 0 || nseq < 0 || !pointers)
+        return fail(ctx, RF_ERR_ARG, std::string(who) + ": bad arguments");
     for (int32_t k = 0; k < nseq; ++k) {
-        const SeqObj &S = ctx->seqs[first + k0 + k];
-        at[k + 1] = at[k] + row_code_off(S.n, S.ncins, S.ncdel) + S.n;
-        st[k] = {at[k] * 8, S.tabs.off, (at[k + 1] - at[k]) * 8, 0};
-        sb[k] = {off[k0 + k] - off[k0], S.bases.off, S.n, 0};
-    }
-    // The host work per position (staging copies, the finiteness test, the
-    // row codes) runs on host threads over ranges of sequences.  Row codes in
-    // three passes so the dictionary is only written by one thread: new keys
-    // per range (read-only lookups), their insertion in range order (= the
-    // serial first-occurrence order), then the records (read-only lookups).
-    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (nt + (1 << 20) - 1) >> 20));
-    std::vector<int32_t> rng(nth + 1);
-    for (int t = 0; t <= nth; ++t)
-        rng[t] = (int32_t)((int64_t)nseq * t / nth);
-    CodeDict &D = ctx->codes;
-    auto table = [&](int32_t k) { return host_tabs + at[k]; };
-    std::vector<std::vector<CodeDict::K3>> new3(nth);
-    std::vector<std::vector<uint64_t>> new1(nth);
-    parallel_for(nth, [&](int t) {
-        std::unordered_set<CodeDict::K3, CodeDict::H3> s3;
-        std::unordered_set<uint64_t> s1;
-        CodeDict::Cache cache;
-        for (int32_t k = rng[t]; k < rng[t + 1]; ++k) {
-            const SeqObj &S = ctx->seqs[first + k0 + k];
-            const int64_t n = S.n, nci = S.ncins, ncd = S.ncdel;
-            double *h = table(k);
-            const int32_t kg = k0 + k;   // index into the caller's arrays
-            std::memcpy(h, match + off[kg], n * 8);
-            std::memcpy(h + n, mismatch + off[kg], n * 8);
-            std::memcpy(h + 2 * n, ins + off[kg], n * 8);
-            std::memcpy(h + 3 * n, del + off[kg] + kg, (n + 1) * 8);
-            if (nci)
-                std::memcpy(h + 4 * n + 1, cins + cins_off[kg], nci * 8);
-            if (ncd)
-                std::memcpy(h + 4 * n + 1 + nci, cdel + cdel_off[kg], ncd * 8);
-            bool fin = true;
-            for (int64_t e = 0; e < 4 * n + 1; ++e)
-                fin = fin && std::isfinite(h[e]);
-            ctx->seqs[first + k0 + k].finite = fin;
-            for (int64_t i = 0; i < n; ++i) {
-                const CodeDict::K3 key{CodeDict::bits(h[i]), CodeDict::bits(h[n + i]), CodeDict::bits(h[2 * n + i])};
-                if (D.find3(key, cache) < 0 && s3.insert(key).second)
-                    new3[t].push_back(key);
-            }
-            for (int64_t i = 0; i <= n; ++i) {
-                const uint64_t key = CodeDict::bits(h[3 * n + i]);
-                if (D.find1(key, cache) < 0 && s1.insert(key).second)
-                    new1[t].push_back(key);
-            }
-        }
-    });
-    for (int t = 0; t < nth; ++t) {
-        for (const auto &key : new3[t])
-            if (D.find3(key) < 0 && D.t3.size() < (size_t)RF_CODES) {
-                D.t3.emplace(key, (uint32_t)D.t3.size());
-                double v[3];
-                std::memcpy(v, &key.a, 8), std::memcpy(v + 1, &key.b, 8), std::memcpy(v + 2, &key.c, 8);
-                D.t3v.insert(D.t3v.end(), {v[0], v[1], v[2], 0.0});
-            }
-        for (uint64_t key : new1[t])
-            if (D.find1(key) < 0 && D.d1.size() < (size_t)RF_CODES) {
-                D.d1.emplace(key, (uint32_t)D.d1.size());
-                double v;
-                std::memcpy(&v, &key, 8);
-                D.d1v.push_back(v);
-            }
-    }
-    parallel_for(nth, [&](int t) {
-        CodeDict::Cache cache;
-        for (int32_t k = rng[t]; k < rng[t + 1]; ++k) {
-            const SeqObj &S = ctx->seqs[first + k0 + k];
-            const int64_t n = S.n;
-            const double *h = table(k);
-            uint64_t *rec = (uint64_t *)(table(k) + row_code_off(n, S.ncins, S.ncdel));
-            const uint8_t *bs = bases + off[k0 + k];
-            bool ok = true;
-            int32_t dprev = D.find1(CodeDict::bits(h[3 * n]), cache);
-            ok = dprev >= 0;
-            for (int64_t i = 0; i < n && ok; ++i) {
-                const int32_t c3 = D.find3({CodeDict::bits(h[i]), CodeDict::bits(h[n + i]), CodeDict::bits(h[2 * n + i])}, cache);
-                const int32_t dn = D.find1(CodeDict::bits(h[3 * n + i + 1]), cache);
-                ok = c3 >= 0 && dn >= 0;
-                rec[i] = (uint64_t)(uint32_t)c3 | ((uint64_t)(uint32_t)dprev << 16) | ((uint64_t)(uint32_t)dn << 32) |
-                         ((uint64_t)bs[i] << 48);
-                dprev = dn;
-            }
-            ctx->seqs[first + k0 + k].coded = ok;
-        }
-    });
-    for (int32_t k = 0; k < nseq; ++k)
-        D.uncoded_reads += ctx->seqs[first + k0 + k].coded ? 0 : 1;
-    // 3. new code-dictionary entries, one H2D copy each + device scatter
-    {
-        CodeDict &D = ctx->codes;
-        if (int e = ensure_buf(ctx, D.lut, (size_t)RF_CODES * 5 * 8)) return e;
-        const size_t n3 = D.t3v.size() / 4, n1 = D.d1v.size();
-        if (n3 > D.up3)
-            HIPCHK(ctx, hipMemcpyAsync((double *)D.lut.p + 4 * D.up3, D.t3v.data() + 4 * D.up3, (n3 - D.up3) * 32,
-                                       hipMemcpyHostToDevice, ctx->stream));
-        if (n1 > D.up1)
-            HIPCHK(ctx, hipMemcpyAsync((double *)D.lut.p + 4 * (size_t)RF_CODES + D.up1, D.d1v.data() + D.up1,
-                                       (n1 - D.up1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        D.up3 = n3;
-        D.up1 = n1;
-    }
-    if (int e = ensure_buf(ctx, ctx->scratch[BUF_TABS_OR_CSEQS], (size_t)std::max<int64_t>(nt * 8, 16))) return e;
-    if (int e = ensure_buf(ctx, ctx->scratch[BUF_BYTES_OR_SINK], (size_t)std::max<int64_t>(nb, 16))) return e;
-    if (nseq > 0) {
-        std::memcpy(host_bases, bases + off[k0], nb);
-        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_TABS_OR_CSEQS].p, host_tabs, nt * 8, hipMemcpyHostToDevice,
-                                   ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_BYTES_OR_SINK].p, host_bases, nb, hipMemcpyHostToDevice,
-                                   ctx->stream));
-        if (int e = upload(ctx, ctx->scratch[BUF_SEGS_OR_WORK], st)) return e;
-        hipLaunchKernelGGL(k_scatter, dim3(nseq), dim3(256), 0, ctx->stream, dev<const Segment>(ctx, BUF_SEGS_OR_WORK),
-                           dev<const uint8_t>(ctx, BUF_TABS_OR_CSEQS), (uint8_t *)ctx->tab_arena.d);
-        HIPCHK(ctx, stream_wait(ctx));   // BUF_SEGS_OR_WORK is reused below
-        if (int e = upload(ctx, ctx->scratch[BUF_SEGS_OR_WORK], sb)) return e;
-        hipLaunchKernelGGL(k_scatter, dim3(nseq), dim3(256), 0, ctx->stream, dev<const Segment>(ctx, BUF_SEGS_OR_WORK),
-                           dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK), (uint8_t *)ctx->bytes_arena.d);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, stream_wait(ctx));
+        const int64_t n = off[k + 1] - off[k];
+        const int64_t nci = cins_off ? cins_off[k + 1] - cins_off[k] : 0;
+        const int64_t ncd = cdel_off ? cdel_off[k + 1] - cdel_off[k] : 0;
+        if (n < 1)
+            return fail(ctx, RF_ERR_ARG, std::string(who) + ": empty sequence");
+        if ((nci != 0 && nci != n - 2) || (ncd != 0 && ncd != n + 1))
+            return fail(ctx, RF_ERR_ARG, std::string(who) + ": inconsistent table lengths");
     }
     return 0;
 }
 
+// a fresh code dictionary when no coded sequence outside this upload is
+// still valid (nothing references the old codes)
+static void fresh_dictionary(rf_ctx *ctx, int32_t first, int32_t nseq)
+{
+    for (size_t k = 0; k < ctx->seqs.size(); ++k) {
+        const bool outside = (int64_t)k < first || (int64_t)k >= (int64_t)first + nseq;
+        if (outside && ctx->seqs[k].valid && ctx->seqs[k].coded)
+            return;
+    }
+    if (!(ctx->codes.t3.empty() && ctx->codes.d1.empty()))
+        ctx->codes.reset();
+}
+
+// The first state change of an upload (the lengths have been checked).  Bands
+// filled from these ids are stale from here on, also when the upload fails
+// later; until upload_finish the ids are not valid.
+static int upload_begin(rf_ctx *ctx, int32_t first, int32_t nseq, const int64_t *off, const int64_t *cins_off,
+                        const int64_t *cdel_off)
+{
+    (void)hipSetDevice(ctx->device);
+    ++ctx->state_epoch;
+    if ((int64_t)first + nseq > (int64_t)ctx->seqs.size())
+        ctx->seqs.resize(first + nseq);
+    // each arena grows at most once for the whole upload
+    int64_t need_b = 0, need_t = 0;
+    for (int32_t k = 0; k < nseq; ++k) {
+        SeqObj &S = ctx->seqs[first + k];
+        S.version = ++ctx->seq_counter;
+        S.valid = false;
+        S.n = (int32_t)(off[k + 1] - off[k]);
+        S.ncins = (int32_t)(cins_off ? cins_off[k + 1] - cins_off[k] : 0);
+        S.ncdel = (int32_t)(cdel_off ? cdel_off[k + 1] - cdel_off[k] : 0);
+        const int64_t bb = align_up(std::max<int64_t>(S.n, 16), 256);
+        const int64_t tb = align_up(std::max<int64_t>(seq_table_len(S.n, S.ncins, S.ncdel) * 8, 16), 256);
+        if (!(S.bases.off >= 0 && S.bases.cap >= bb)) need_b += bb;
+        if (!(S.tabs.off >= 0 && S.tabs.cap >= tb)) need_t += tb;
+    }
+    if (ctx->bytes_arena.top + need_b + ARENA_GUARD > ctx->bytes_arena.cap)
+        if (int e = arena_grow(ctx, ctx->bytes_arena, need_b, nullptr)) return e;
+    if (ctx->tab_arena.top + need_t + ARENA_GUARD > ctx->tab_arena.cap)
+        if (int e = arena_grow(ctx, ctx->tab_arena, need_t, nullptr)) return e;
+    // regions (a growth moves earlier regions: offsets are read after this loop)
+    for (int32_t k = 0; k < nseq; ++k) {
+        SeqObj &S = ctx->seqs[first + k];
+        if (int e = region_ensure(ctx, ctx->bytes_arena, S.bases, S.n)) return e;
+        if (int e = region_ensure(ctx, ctx->tab_arena, S.tabs, seq_table_len(S.n, S.ncins, S.ncdel) * 8)) return e;
+    }
+    return 0;
+}
+
+static void upload_finish(rf_ctx *ctx, int32_t first, int32_t nseq)
+{
+    for (int32_t k = 0; k < nseq; ++k)
+        ctx->seqs[first + k].valid = true;
+    ++ctx->layout_gen;
+}
+
+// ctx->pinned holds `bytes`: the host staging of one chunk
+static int ensure_pinned(rf_ctx *ctx, size_t bytes)
+{
+    if (ctx->pinned_bytes >= bytes)
+        return 0;
+    if (ctx->pinned)
+        (void)hipHostFree(ctx->pinned);
+    ctx->pinned = nullptr;
+    ctx->pinned_bytes = 0;
+    const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 22);
+    if (hipHostMalloc(&ctx->pinned, want, hipHostMallocDefault) != hipSuccess)
+        return fail(ctx, RF_ERR_HIP, "sequence upload: pinned staging allocation failed");
+    ctx->pinned_bytes = want;
+    return 0;
+}
+
+// new code-dictionary entries to the device, one H2D copy per kind
+static int send_dictionary(rf_ctx *ctx)
+{
+    DevCodeDict &D = ctx->codes;
+    if (int e = ensure_buf(ctx, D.lut, (size_t)RF_CODES * 5 * 8)) return e;
+    const size_t n3 = D.t3v.size() / 4, n1 = D.d1v.size();
+    if (n3 > D.up3)
+        HIPCHK(ctx, hipMemcpyAsync((double *)D.lut.p + 4 * D.up3, D.t3v.data() + 4 * D.up3, (n3 - D.up3) * 32,
+                                   hipMemcpyHostToDevice, ctx->stream));
+    if (n1 > D.up1)
+        HIPCHK(ctx, hipMemcpyAsync((double *)D.lut.p + 4 * (size_t)RF_CODES + D.up1, D.d1v.data() + D.up1,
+                                   (n1 - D.up1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    D.up3 = n3;
+    D.up1 = n1;
+    return 0;
+}
+
+// One k_scatter launch: the segments of the staged bytes in `src` to their
+// places in arena `a`.  The descriptors go through BUF_SEGS_OR_WORK, which the
+// stream must have read before the next call of this (the callers' waits).
+static int scatter_staged(rf_ctx *ctx, const std::vector<Segment> &sg, Buf src, Arena &a)
+{
+    if (int e = upload(ctx, ctx->scratch[BUF_SEGS_OR_WORK], sg)) return e;
+    hipLaunchKernelGGL(k_scatter, dim3((unsigned)sg.size()), dim3(256), 0, ctx->stream,
+                       dev<const Segment>(ctx, BUF_SEGS_OR_WORK), dev<const uint8_t>(ctx, src), (uint8_t *)a.d);
+    return 0;
+}
+
+// One chunk of rf_set_sequences, sequences [k0, k1) of the call: their tables
+// and bases packed into pinned memory and coded there (code_rows), one H2D
+// copy each, and a scatter each to the regions.
+static int tables_chunk(rf_ctx *ctx, int32_t first, int32_t k0, int32_t k1, const uint8_t *bases, const int64_t *off,
+                        const double *match, const double *mismatch, const double *ins, const double *del,
+                        const double *cins, const int64_t *cins_off, const double *cdel, const int64_t *cdel_off)
+{
+    const int32_t nseq = k1 - k0;
+    const int64_t nb = off[k1] - off[k0];
+    std::vector<Segment> sb(nseq), st(nseq);
+    int64_t nt = 0;
+    for (int32_t k = 0; k < nseq; ++k) {
+        const SeqObj &S = ctx->seqs[first + k0 + k];
+        const int64_t len = seq_table_len(S.n, S.ncins, S.ncdel);
+        st[k] = {nt * 8, S.tabs.off, len * 8, 0};
+        sb[k] = {off[k0 + k] - off[k0], S.bases.off, S.n, 0};
+        nt += len;
+    }
+    if (int e = ensure_pinned(ctx, (size_t)nt * 8 + (size_t)nb)) return e;
+    double *host_tabs = (double *)ctx->pinned;
+    uint8_t *host_bases = (uint8_t *)ctx->pinned + (size_t)nt * 8;
+    std::vector<RowSeq> rs(nseq);
+    for (int32_t k = 0; k < nseq; ++k) {
+        const SeqObj &S = ctx->seqs[first + k0 + k];
+        rs[k] = {host_tabs + st[k].src / 8, bases + off[k0 + k], S.n, S.ncins, S.ncdel, false, false};
+    }
+    // the host work per position (staging copies, the finiteness test, the
+    // row codes) runs on host threads, one per MB of tables
+    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (nt + (1 << 20) - 1) >> 20));
+    code_rows(ctx->codes, rs.data(), nseq, nth, [&](int32_t k) {
+        const int32_t kg = k0 + k;   // index into the caller's arrays
+        pack_tables(rs[k], match + off[kg], mismatch + off[kg], ins + off[kg], del + off[kg] + kg,
+                    rs[k].nci ? cins + cins_off[kg] : nullptr, rs[k].ncd ? cdel + cdel_off[kg] : nullptr);
+    });
+    for (int32_t k = 0; k < nseq; ++k) {
+        ctx->seqs[first + k0 + k].finite = rs[k].finite;
+        ctx->seqs[first + k0 + k].coded = rs[k].coded;
+    }
+    if (int e = send_dictionary(ctx)) return e;
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_TABS_OR_CSEQS], (size_t)nt * 8)) return e;
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_BYTES_OR_SINK], (size_t)std::max<int64_t>(nb, 16))) return e;
+    std::memcpy(host_bases, bases + off[k0], nb);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_TABS_OR_CSEQS].p, host_tabs, nt * 8, hipMemcpyHostToDevice,
+                               ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_BYTES_OR_SINK].p, host_bases, nb, hipMemcpyHostToDevice, ctx->stream));
+    if (int e = scatter_staged(ctx, st, BUF_TABS_OR_CSEQS, ctx->tab_arena)) return e;
+    HIPCHK(ctx, stream_wait(ctx));   // between the two uses of BUF_SEGS_OR_WORK
+    if (int e = scatter_staged(ctx, sb, BUF_BYTES_OR_SINK, ctx->bytes_arena)) return e;
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, stream_wait(ctx));   // after the chunk: the next one reuses the pinned staging and all three buffers
+    return 0;
+}
+
+// A refusal (RF_ERR_ARG) leaves the context as it was: see upload_check.
 int rf_set_sequences(rf_ctx *ctx, int32_t first, int32_t nseq, const uint8_t *bases,
                      const int64_t *off, const double *match, const double *mismatch,
                      const double *ins, const double *del, const double *cins,
                      const int64_t *cins_off, const double *cdel, const int64_t *cdel_off)
 {
-    if (!ctx || first < 0 || nseq < 0 || (nseq > 0 && (!bases || !off || !match || !mismatch || !ins || !del)))
-        return fail(ctx, RF_ERR_ARG, "rf_set_sequences: bad arguments");
-    (void)hipSetDevice(ctx->device);
-    ++ctx->state_epoch;
-    if ((int64_t)first + nseq > (int64_t)ctx->seqs.size())
-        ctx->seqs.resize(first + nseq);
-    // bands filled from these ids are stale from here on, also when the
-    // upload fails half way
-    for (int32_t k = 0; k < nseq; ++k)
-        ctx->seqs[first + k].version = ++ctx->seq_counter;
-    // a fresh code dictionary when no coded sequence outside this upload is
-    // still valid (nothing references the old codes)
-    {
-        bool others = false;
-        for (size_t k = 0; k < ctx->seqs.size() && !others; ++k)
-            others = ((int64_t)k < first || (int64_t)k >= (int64_t)first + nseq) && ctx->seqs[k].valid &&
-                     ctx->seqs[k].coded;
-        if (!others && !(ctx->codes.t3.empty() && ctx->codes.d1.empty()))
-            ctx->codes.reset();
-    }
-    // 0. grow each arena at most once for the whole batch
-    {
-        int64_t need_b = 0, need_t = 0;
-        for (int32_t k = 0; k < nseq; ++k) {
+    if (int e = upload_check(ctx, "rf_set_sequences", nseq <= 0 || (bases && off && match && mismatch && ins && del),
+                             first, nseq, off, cins_off, cdel_off))
+        return e;
+    fresh_dictionary(ctx, first, nseq);
+    if (int e = upload_begin(ctx, first, nseq, off, cins_off, cdel_off)) return e;
+    // chunks of at most RF_OPT_STAGE_KB of tables: a bounded pinned staging
+    // buffer and device scratch, whatever the size of the upload
+    const int64_t budget = tables_stage_budget(ctx->opt.stage_kb);
+    for (int32_t k0 = 0, k1; k0 < nseq; k0 = k1) {
+        k1 = chunk_end(k0, nseq, budget, [&](int32_t k) {
             const SeqObj &S = ctx->seqs[first + k];
-            const int64_t n = off[k + 1] - off[k];
-            const int64_t nci = cins_off ? cins_off[k + 1] - cins_off[k] : 0;
-            const int64_t ncd = cdel_off ? cdel_off[k + 1] - cdel_off[k] : 0;
-            const int64_t bb = align_up(std::max<int64_t>(n, 16), 256);
-            const int64_t tb = align_up(std::max<int64_t>((row_code_off(n, nci, ncd) + n) * 8, 16), 256);
-            if (!(S.bases.off >= 0 && S.bases.cap >= bb)) need_b += bb;
-            if (!(S.tabs.off >= 0 && S.tabs.cap >= tb)) need_t += tb;
-        }
-        if (ctx->bytes_arena.top + need_b + ARENA_GUARD > ctx->bytes_arena.cap)
-            if (int e = arena_grow(ctx, ctx->bytes_arena, need_b, nullptr)) return e;
-        if (ctx->tab_arena.top + need_t + ARENA_GUARD > ctx->tab_arena.cap)
-            if (int e = arena_grow(ctx, ctx->tab_arena, need_t, nullptr)) return e;
-    }
-    // 1. regions (arena growth may move earlier regions: offsets are read after)
-    int64_t nb = 0, nt = 0;
-    for (int32_t k = 0; k < nseq; ++k) {
-        SeqObj &S = ctx->seqs[first + k];
-        const int64_t n = off[k + 1] - off[k];
-        const int64_t nci = cins_off ? cins_off[k + 1] - cins_off[k] : 0;
-        const int64_t ncd = cdel_off ? cdel_off[k + 1] - cdel_off[k] : 0;
-        if (n < 1 || (nci != 0 && nci != n - 2) || (ncd != 0 && ncd != n + 1))
-            return fail(ctx, RF_ERR_ARG, "rf_set_sequences: inconsistent table lengths");
-        S.n = (int32_t)n;
-        S.ncins = (int32_t)nci;
-        S.ncdel = (int32_t)ncd;
-        if (int e = region_ensure(ctx, ctx->bytes_arena, S.bases, n))
+            return tables_stage_bytes(S.n, S.ncins, S.ncdel);
+        });
+        if (int e = tables_chunk(ctx, first, k0, k1, bases, off, match, mismatch, ins, del, cins, cins_off, cdel,
+                                 cdel_off))
             return e;
-        // tables [match|mismatch|ins|del|cins|cdel], then one row-code record per position
-        if (int e = region_ensure(ctx, ctx->tab_arena, S.tabs, (row_code_off(n, nci, ncd) + n) * 8))
-            return e;
-        nb += n;
-        nt += row_code_off(n, nci, ncd) + n;
     }
-    // 2.-3. in chunks of at most RF_OPT_STAGE_KB of tables (a bounded pinned
-    // staging buffer and device scratch, whatever the batch size): pack the
-    // chunk's tables [match|mismatch|ins|del|cins|cdel|row codes] and bases
-    // into pinned memory, then one H2D copy each + a device scatter.
-    (void)nb;
-    (void)nt;
-    int32_t k0 = 0;
-    while (k0 < nseq) {
-        int32_t k1 = k0;
-        int64_t ct = 0;
-        while (k1 < nseq) {
-            const SeqObj &S = ctx->seqs[first + k1];
-            const int64_t len = row_code_off(S.n, S.ncins, S.ncdel) + S.n;
-            if (k1 > k0 && (ct + len) * 8 > (int64_t)std::max(ctx->opt.stage_kb, 1) * 1024)
-                break;
-            ct += len;
-            ++k1;
-        }
-        if (int e = upload_sequence_chunk(ctx, first, k0, k1, bases, off, match, mismatch, ins, del, cins, cins_off,
-                                          cdel, cdel_off))
-            return e;
-        k0 = k1;
-    }
-    for (int32_t k = 0; k < nseq; ++k)
-        ctx->seqs[first + k].valid = true;
-    ++ctx->layout_gen;
+    upload_finish(ctx, first, nseq);
     return 0;
 }
 
-static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, const uint8_t *bases,
-                                    const int64_t *off, const uint8_t *codes, const double *lp_t,
-                                    const double *match_t, double s_mis, double s_ins, double s_del,
-                                    const double *p10_t, const double *grid, double *est, int32_t *ucode,
-                                    double *tsum)
-{
-    const bool prep = p10_t != nullptr;
-    if (!ctx || first < 0 || nseq < 0 || (nseq > 0 && (!bases || !off || !codes || !lp_t || !match_t)))
-        return fail(ctx, RF_ERR_ARG, "rf_set_sequences_codes: bad arguments");
-    (void)hipSetDevice(ctx->device);
-    ++ctx->state_epoch;
-    for (int32_t k = 0; k < nseq; ++k)
-        if (off[k + 1] - off[k] < 1)
-            return fail(ctx, RF_ERR_ARG, "rf_set_sequences_codes: empty sequence");
-    const int64_t N = nseq > 0 ? off[nseq] - off[0] : 0;
-    // codes present, per-code values and finiteness
+// The codes path's per-code values: which codes occur, the four table values
+// of each and whether they are finite, and the device's CodeLut.
+struct CodeTables {
     bool present[256] = {};
+    bool fin[256];
+    std::vector<CodeLut> lut = std::vector<CodeLut>(256);
+};
+
+// The 256-entry LUT of an upload of N positions: the table values by the
+// RifrafSequence constructor's FP64 adds, and the dictionary codes of the
+// codes present.  RF_ERR_STATE when the dictionary cannot hold them: the
+// entries this call added are dropped again (the caller then uploads host
+// tables; codes no sequence uses must not crowd out later uploads).
+static int code_tables(rf_ctx *ctx, int64_t N, const uint8_t *codes, const double *lp_t, const double *match_t,
+                       double s_mis, double s_ins, double s_del, CodeTables &T)
+{
     {
         // one byte store per position (~0.5 ns): threads from 512 K positions
         // (c3's 2.6 M: 1.3 ms on one thread)
@@ -6761,113 +6626,52 @@ static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, co
         std::vector<std::array<uint8_t, 256>> pr(nth);
         parallel_for(nth, [&](int t) {
             pr[t].fill(0);
-            for (int64_t i = off[0] + N * t / nth; i < off[0] + N * (t + 1) / nth; ++i)
+            for (int64_t i = N * t / nth; i < N * (t + 1) / nth; ++i)
                 pr[t][codes[i]] = 1;
         });
         for (int t = 0; t < nth; ++t)
             for (int c = 0; c < 256; ++c)
-                present[c] = present[c] || pr[t][c];
-    }
-    double mt[256], mm[256], is[256], dl[256];
-    bool fin[256];
-    for (int c = 0; c < 256; ++c) {
-        mt[c] = match_t[c];
-        mm[c] = lp_t[c] + s_mis;
-        is[c] = lp_t[c] + s_ins;
-        dl[c] = lp_t[c] + s_del;
-        fin[c] = std::isfinite(mt[c]) && std::isfinite(mm[c]) && std::isfinite(is[c]) && std::isfinite(dl[c]);
-    }
-    // a fresh code dictionary when no coded sequence outside this upload is
-    // still valid (as rf_set_sequences)
-    {
-        bool others = false;
-        for (size_t k = 0; k < ctx->seqs.size() && !others; ++k)
-            others = ((int64_t)k < first || (int64_t)k >= (int64_t)first + nseq) && ctx->seqs[k].valid &&
-                     ctx->seqs[k].coded;
-        if (!others && !(ctx->codes.t3.empty() && ctx->codes.d1.empty()))
-            ctx->codes.reset();
+                T.present[c] = T.present[c] || pr[t][c];
     }
     CodeDict &D = ctx->codes;
-    std::vector<CodeLut> lut(256);
-    // entries added by this call, dropped again if the dictionary fills up
-    // (the caller then uploads host tables; codes no sequence uses must not
-    // crowd out later uploads)
-    std::vector<CodeDict::K3> added3;
-    std::vector<uint64_t> added1;
+    const CodeDict::Mark mark = D.mark();
     for (int c = 0; c < 256; ++c) {
-        lut[c] = {lp_t[c], mt[c], 0, 0, 0, 0};
-        if (!present[c])
+        const double mt = match_t[c], mm = lp_t[c] + s_mis, is = lp_t[c] + s_ins, dl = lp_t[c] + s_del;
+        T.fin[c] = std::isfinite(mt) && std::isfinite(mm) && std::isfinite(is) && std::isfinite(dl);
+        T.lut[c] = {lp_t[c], mt, 0, 0, 0, 0};
+        if (!T.present[c])
             continue;
-        const CodeDict::K3 key{CodeDict::bits(mt[c]), CodeDict::bits(mm[c]), CodeDict::bits(is[c])};
-        int32_t i3 = D.find3(key);
-        if (i3 < 0 && D.t3.size() < (size_t)RF_CODES) {
-            i3 = (int32_t)D.t3.size();
-            D.t3.emplace(key, (uint32_t)i3);
-            D.t3v.insert(D.t3v.end(), {mt[c], mm[c], is[c], 0.0});
-            added3.push_back(key);
-        }
-        int32_t i1 = D.find1(CodeDict::bits(dl[c]));
-        if (i1 < 0 && D.d1.size() < (size_t)RF_CODES) {
-            i1 = (int32_t)D.d1.size();
-            D.d1.emplace(CodeDict::bits(dl[c]), (uint32_t)i1);
-            D.d1v.push_back(dl[c]);
-            added1.push_back(CodeDict::bits(dl[c]));
-        }
-        if (i3 < 0 || i1 < 0) {   // dictionary full: the caller uploads host tables instead
-            for (const auto &k : added3)
-                D.t3.erase(k);
-            for (const auto &k : added1)
-                D.d1.erase(k);
-            D.t3v.resize(D.t3v.size() - 4 * added3.size());
-            D.d1v.resize(D.d1v.size() - added1.size());
+        T.lut[c].id3 = D.insert3(CodeDict::key3(mt, mm, is));
+        T.lut[c].id1 = D.insert1(CodeDict::bits(dl));
+        if (T.lut[c].id3 < 0 || T.lut[c].id1 < 0) {
+            D.undo(mark);
             return fail(ctx, RF_ERR_STATE, "rf_set_sequences_codes: row-code dictionary full");
         }
-        lut[c].id3 = i3;
-        lut[c].id1 = i1;
     }
-    if ((int64_t)first + nseq > (int64_t)ctx->seqs.size())
-        ctx->seqs.resize(first + nseq);
-    for (int32_t k = 0; k < nseq; ++k)   // as rf_set_sequences: bands of these ids are stale
-        ctx->seqs[first + k].version = ++ctx->seq_counter;
-    // regions: bases + tables [match|mismatch|ins|del|row codes] (arena growth
-    // at most once per arena; offsets are read after every allocation)
-    {
-        int64_t need_b = 0, need_t = 0;
-        for (int32_t k = 0; k < nseq; ++k) {
-            const SeqObj &S = ctx->seqs[first + k];
-            const int64_t n = off[k + 1] - off[k];
-            const int64_t bb = align_up(std::max<int64_t>(n, 16), 256);
-            const int64_t tb = align_up(std::max<int64_t>((row_code_off(n, 0, 0) + n) * 8, 16), 256);
-            if (!(S.bases.off >= 0 && S.bases.cap >= bb)) need_b += bb;
-            if (!(S.tabs.off >= 0 && S.tabs.cap >= tb)) need_t += tb;
-        }
-        if (ctx->bytes_arena.top + need_b + ARENA_GUARD > ctx->bytes_arena.cap)
-            if (int e = arena_grow(ctx, ctx->bytes_arena, need_b, nullptr)) return e;
-        if (ctx->tab_arena.top + need_t + ARENA_GUARD > ctx->tab_arena.cap)
-            if (int e = arena_grow(ctx, ctx->tab_arena, need_t, nullptr)) return e;
-    }
-    for (int32_t k = 0; k < nseq; ++k) {
-        SeqObj &S = ctx->seqs[first + k];
-        const int64_t n = off[k + 1] - off[k];
-        S.n = (int32_t)n;
-        S.ncins = S.ncdel = 0;
-        if (int e = region_ensure(ctx, ctx->bytes_arena, S.bases, n)) return e;
-        if (int e = region_ensure(ctx, ctx->tab_arena, S.tabs, (row_code_off(n, 0, 0) + n) * 8)) return e;
-    }
-    // new dictionary entries to the device
-    if (int e = ensure_buf(ctx, D.lut, (size_t)RF_CODES * 5 * 8)) return e;
-    {
-        const size_t n3 = D.t3v.size() / 4, n1 = D.d1v.size();
-        if (n3 > D.up3)
-            HIPCHK(ctx, hipMemcpyAsync((double *)D.lut.p + 4 * D.up3, D.t3v.data() + 4 * D.up3, (n3 - D.up3) * 32,
-                                       hipMemcpyHostToDevice, ctx->stream));
-        if (n1 > D.up1)
-            HIPCHK(ctx, hipMemcpyAsync((double *)D.lut.p + 4 * (size_t)RF_CODES + D.up1, D.d1v.data() + D.up1,
-                                       (n1 - D.up1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        D.up3 = n3;
-        D.up1 = n1;
-    }
-    if (int e = upload(ctx, ctx->scratch[BUF_CODE_LUTS], lut)) return e;
+    return 0;
+}
+
+// Refusals leave the context as it was: RF_ERR_ARG (upload_check) and the
+// full dictionary's RF_ERR_STATE (code_tables; a dictionary that
+// fresh_dictionary has just emptied holds any 256 codes, so the refusal meets
+// one that was kept).
+static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, const uint8_t *bases,
+                                    const int64_t *off, const uint8_t *codes, const double *lp_t,
+                                    const double *match_t, double s_mis, double s_ins, double s_del,
+                                    const double *p10_t, const double *grid, double *est, int32_t *ucode,
+                                    double *tsum)
+{
+    const bool prep = p10_t != nullptr;
+    if (int e = upload_check(ctx, "rf_set_sequences_codes", nseq <= 0 || (bases && off && codes && lp_t && match_t),
+                             first, nseq, off, nullptr, nullptr))
+        return e;
+    const int64_t N = nseq > 0 ? off[nseq] - off[0] : 0;
+    fresh_dictionary(ctx, first, nseq);
+    CodeTables T;
+    if (int e = code_tables(ctx, N, nseq > 0 ? codes + off[0] : codes, lp_t, match_t, s_mis, s_ins, s_del, T)) return e;
+    if (int e = upload_begin(ctx, first, nseq, off, nullptr, nullptr)) return e;
+    if (int e = send_dictionary(ctx)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_CODE_LUTS], T.lut)) return e;
     // prep (rf_set_sequences_codes_prep): p10 | match tables, the 256 x 256
     // grid, then est / tsum (nseq doubles each) and ucode (nseq ints)
     const size_t prep_tab = 512 * 8, prep_grid = 65536 * 8, prep_out = (size_t)std::max(nseq, 1) * 20;
@@ -6894,26 +6698,13 @@ static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, co
     double *d_est = (double *)(dev<char>(ctx, BUF_CODE_PREP) + prep_tab + prep_grid);
     double *d_tsum = d_est + std::max(nseq, 1);
     int32_t *d_ucode = (int32_t *)(d_tsum + std::max(nseq, 1));
-    // chunks of sequences: codes + bases staged in pinned memory, one H2D,
+    // chunks of sequences: bases + codes staged in pinned memory, one H2D,
     // the bases scattered to their regions, the tables built in place
-    int32_t k0 = 0;
-    const int64_t chunk_bytes = std::max<int64_t>((int64_t)ctx->opt.stage_kb * 1024 / 4, 1 << 20);
-    while (k0 < nseq) {
-        int32_t k1 = k0 + 1;
-        while (k1 < nseq && 2 * (off[k1 + 1] - off[k0]) <= chunk_bytes)
-            ++k1;
+    const int64_t budget = codes_stage_budget(ctx->opt.stage_kb);
+    for (int32_t k0 = 0, k1; k0 < nseq; k0 = k1) {
+        k1 = chunk_end(k0, nseq, budget, [&](int32_t k) { return codes_stage_bytes(off[k + 1] - off[k]); });
         const int64_t nb = off[k1] - off[k0];
-        const size_t stage = (size_t)(2 * nb);
-        if (ctx->pinned_bytes < stage) {
-            if (ctx->pinned)
-                (void)hipHostFree(ctx->pinned);
-            ctx->pinned = nullptr;
-            ctx->pinned_bytes = 0;
-            const size_t want = std::max(stage + stage / 2, (size_t)1 << 22);
-            if (hipHostMalloc(&ctx->pinned, want, hipHostMallocDefault) != hipSuccess)
-                return fail(ctx, RF_ERR_HIP, "rf_set_sequences_codes: pinned staging allocation failed");
-            ctx->pinned_bytes = want;
-        }
+        if (int e = ensure_pinned(ctx, (size_t)(2 * nb))) return e;
         uint8_t *hb = (uint8_t *)ctx->pinned, *hc = hb + nb;
         std::memcpy(hb, bases + off[k0], nb);
         std::memcpy(hc, codes + off[k0], nb);
@@ -6926,11 +6717,9 @@ static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, co
         }
         if (int e = ensure_buf(ctx, ctx->scratch[BUF_BYTES_OR_SINK], (size_t)std::max<int64_t>(2 * nb, 16))) return e;
         HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_BYTES_OR_SINK].p, hb, 2 * nb, hipMemcpyHostToDevice, ctx->stream));
-        if (int e = upload(ctx, ctx->scratch[BUF_SEGS_OR_WORK], sg)) return e;
+        // every copy of the chunk before its first launch
         if (int e = upload(ctx, ctx->scratch[BUF_TABS_OR_CSEQS], cs)) return e;
-        hipLaunchKernelGGL(k_scatter, dim3(k1 - k0), dim3(256), 0, ctx->stream,
-                           dev<const Segment>(ctx, BUF_SEGS_OR_WORK),
-                           dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK), (uint8_t *)ctx->bytes_arena.d);
+        if (int e = scatter_staged(ctx, sg, BUF_BYTES_OR_SINK, ctx->bytes_arena)) return e;
         hipLaunchKernelGGL(k_tables, dim3(k1 - k0), dim3(256), 0, ctx->stream,
                            dev<const CodeSeq>(ctx, BUF_TABS_OR_CSEQS),
                            dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK) + nb, dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK),
@@ -6943,14 +6732,13 @@ static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, co
                                (const double *)(dev<char>(ctx, BUF_CODE_PREP) + prep_tab), d_est + k0, d_ucode + k0,
                                d_tsum + k0);
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, stream_wait(ctx));   // staging and descriptors are reused
-        k0 = k1;
+        HIPCHK(ctx, stream_wait(ctx));   // after the chunk: the next one reuses the pinned staging and all three buffers
     }
     // finiteness per sequence (lean DP / scorer eligibility): every sequence
     // is finite when every code present is; else one pass per sequence
     bool all_fin = true;
     for (int c = 0; c < 256; ++c)
-        all_fin = all_fin && (!present[c] || fin[c]);
+        all_fin = all_fin && (!T.present[c] || T.fin[c]);
     if (all_fin) {
         for (int32_t k = 0; k < nseq; ++k)
             ctx->seqs[first + k].finite = true;
@@ -6960,16 +6748,14 @@ static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, co
             for (int32_t k = (int32_t)((int64_t)nseq * t / nth); k < (int32_t)((int64_t)nseq * (t + 1) / nth); ++k) {
                 bool f = true;
                 for (int64_t i = off[k]; i < off[k + 1] && f; ++i)
-                    f = fin[codes[i]];
+                    f = T.fin[codes[i]];
                 ctx->seqs[first + k].finite = f;
             }
         });
     }
-    for (int32_t k = 0; k < nseq; ++k) {
+    for (int32_t k = 0; k < nseq; ++k)
         ctx->seqs[first + k].coded = true;
-        ctx->seqs[first + k].valid = true;
-    }
-    ++ctx->layout_gen;
+    upload_finish(ctx, first, nseq);
     if (prep && nseq > 0) {
         // est | tsum | ucode are contiguous on the device: one copy into the
         // pinned landing zone
@@ -7054,9 +6840,7 @@ int rf_set_templates_ids(rf_ctx *ctx, int32_t ntpl, const int32_t *ids, const ui
         if (int e = ensure_buf(ctx, ctx->scratch[BUF_BYTES_OR_SINK], (size_t)std::max<int64_t>(nb, 16))) return e;
         HIPCHK(ctx, hipMemcpyAsync(ctx->scratch[BUF_BYTES_OR_SINK].p, bases + off[0], nb, hipMemcpyHostToDevice,
                                    ctx->stream));
-        if (int e = upload(ctx, ctx->scratch[BUF_SEGS_OR_WORK], sg)) return e;
-        hipLaunchKernelGGL(k_scatter, dim3(ntpl), dim3(256), 0, ctx->stream, dev<const Segment>(ctx, BUF_SEGS_OR_WORK),
-                           dev<const uint8_t>(ctx, BUF_BYTES_OR_SINK), (uint8_t *)ctx->bytes_arena.d);
+        if (int e = scatter_staged(ctx, sg, BUF_BYTES_OR_SINK, ctx->bytes_arena)) return e;
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, stream_wait(ctx));
@@ -8639,6 +8423,21 @@ int rf_host_score_plan(int32_t nreads, const int32_t *n, const int32_t *m, const
     return 0;
 }
 
+int rf_host_row_codes(int32_t nseq, const uint8_t *bases, const int64_t *off, const double *match,
+                      const double *mismatch, const double *ins, const double *del, int32_t nup, const int32_t *up,
+                      const uint8_t *flags, int32_t nthreads, uint8_t *coded, uint8_t *finite, uint64_t *records,
+                      double *val3, double *val1, int64_t *sizes)
+{
+    return host_row_codes(nseq, bases, off, match, mismatch, ins, del, nup, up, flags, nthreads, coded, finite,
+                          records, val3, val1, sizes);
+}
+
+int rf_host_upload_chunks(int32_t nseq, const int64_t *off, const int64_t *cins_off, const int64_t *cdel_off,
+                          int32_t codes, int32_t stage_kb, int64_t budget, int32_t *end, int32_t *nchunks)
+{
+    return host_upload_chunks(nseq, off, cins_off, cdel_off, codes, stage_kb, budget, end, nchunks);
+}
+
 int rf_slot_geometry(rf_ctx *ctx, int32_t slot, int32_t which, int32_t *nrows, int32_t *ncols,
                      int32_t *bw, int32_t *H)
 {
@@ -8732,7 +8531,7 @@ int rf_internal_aln_sums_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_o
         if (!ctx->seqs[ctx->slots[slots[k]].a.seq].coded)
             return 1;
     // errlut for the dictionary entries added since the last call
-    CodeDict &D = ctx->codes;
+    DevCodeDict &D = ctx->codes;
     const size_t n3 = D.t3v.size() / 4;
     const double log3 = std::log10(3.0);
     for (size_t e = D.errv.size(); e < n3; ++e)

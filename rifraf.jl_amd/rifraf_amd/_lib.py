@@ -87,6 +87,9 @@ _SIGNATURES = {
                                    c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, POINTER(c_int32),
                                    c_void_p, c_void_p]),
     "rf_last_score_launch": (c_int, [c_void_p, c_void_p]),
+    "rf_host_row_codes": (c_int, [c_int32] + [c_void_p] * 6 + [c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 6),
+    "rf_host_upload_chunks": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p,
+                                      POINTER(c_int32)]),
     "rf_set_option": (c_int, [c_void_p, c_int32, c_int32]),
     "rf_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int32)]),
 }
@@ -228,6 +231,48 @@ def host_score_plan(n, m, bw, read_off, stride=None, finite=None, per_seq=False,
         raise ValueError(f"rf_host_score_plan: bad arguments ({rc})")
     return ScorePlan(SCORE_KERNELS[pick[0]], int(pick[1]), int(pick[2]), bool(split[0]), bool(split[1]),
                      [tuple(int(x) for x in it) for it in items[:ni.value]], dense_off.tolist(), split_off[:ng].tolist())
+
+
+RF_CODES = 65536   # entries of the row codes' dictionary, per kind
+# rf_host_row_codes' outputs: val3 is (codes, 4) -- match, mismatch, ins, 0 -- and val1 one del value per code
+RowCodes = namedtuple("RowCodes", "coded finite records val3 val1 uncoded_reads")
+
+
+def host_row_codes(bases, off, match, mismatch, ins, dele, uploads=None, flags=None, nthreads=1):
+    """rf_host_row_codes: the row codes of rf_set_sequences' tables on the host
+    alone (no context, no GPU).  uploads: the boundaries of the uploads in the
+    sequence list (default one upload of them all); flags per upload: 1 starts
+    a fresh dictionary, 2 undoes the upload's dictionary entries after it.
+    Returns a RowCodes."""
+    off = np.ascontiguousarray(off, np.int64)
+    nseq = len(off) - 1
+    up = np.ascontiguousarray([0, nseq] if uploads is None else uploads, np.int32)
+    fl = np.ascontiguousarray(np.zeros(len(up) - 1) if flags is None else flags, np.uint8)
+    f64 = [np.ascontiguousarray(a, np.float64) for a in (match, mismatch, ins, dele)]
+    bases = np.ascontiguousarray(bases, np.uint8)
+    coded, finite = np.zeros(max(nseq, 1), np.uint8), np.zeros(max(nseq, 1), np.uint8)
+    rec = np.zeros(max(int(off[-1] - off[0]), 1), np.uint64)
+    val3, val1, sizes = np.zeros((RF_CODES, 4)), np.zeros(RF_CODES), np.zeros(3, np.int64)
+    rc = load().rf_host_row_codes(nseq, ptr(bases), ptr(off), *(ptr(a) for a in f64), len(up) - 1, ptr(up), ptr(fl),
+                                  int(nthreads), ptr(coded), ptr(finite), ptr(rec), ptr(val3), ptr(val1), ptr(sizes))
+    if rc != 0:
+        raise ValueError(f"rf_host_row_codes: bad arguments ({rc})")
+    return RowCodes(coded[:nseq].astype(bool), finite[:nseq].astype(bool), rec[:int(off[-1] - off[0])],
+                    val3[:sizes[0]].copy(), val1[:sizes[1]].copy(), int(sizes[2]))
+
+
+def host_upload_chunks(off, codes, stage_kb=262144, budget=0, cins_off=None, cdel_off=None):
+    """rf_host_upload_chunks: the ends of the staging chunks of one upload by
+    rf_set_sequences (codes False) or rf_set_sequences_codes (True) at the
+    stage_kb option, or within `budget` bytes when that is positive."""
+    off = np.ascontiguousarray(off, np.int64)
+    i64 = lambda a: None if a is None else np.ascontiguousarray(a, np.int64)   # noqa: E731
+    end, nc = np.zeros(max(len(off) - 1, 1), np.int32), c_int32()
+    rc = load().rf_host_upload_chunks(len(off) - 1, ptr(off), ptr(i64(cins_off)), ptr(i64(cdel_off)), int(bool(codes)),
+                                      int(stage_kb), int(budget), ptr(end), ctypes.byref(nc))
+    if rc != 0:
+        raise ValueError(f"rf_host_upload_chunks: bad arguments ({rc})")
+    return end[:nc.value].tolist()
 
 
 def ptr(a: np.ndarray | None):
