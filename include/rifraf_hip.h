@@ -29,6 +29,9 @@
  *                        estimate_probs  src/model.jl:385-399,499-526,737-791
  *                        (per-sequence: score_nocodon :242-285 / codon
  *                        score_proposal :302-383 / seq_score_deletion :227-236)
+ *   rf_candidates     <- get_candidates' filter and choose_candidates over
+ *                        the dense table, on the device
+ *                        src/model.jl:499-526, src/proposals.jl:104-115
  *   rf_download_band  <- BandedArray data (tests)   src/bandedarrays.jl:5-42
  *
  * Conventions
@@ -166,6 +169,12 @@ const char *rf_last_error(const rf_ctx *ctx);
                                    pairs is at least 512, as measured for 16 to
                                    62,500 pairs.  Same moves and
                                    counts under every value                      */
+#define RF_OPT_CAND_DEVICE  35   /* the native driver's get_candidates + choose_candidates
+                                   (rf_rifraf_batch): 1: rf_candidates, on the device;
+                                   0 (default): rf_alignment_proposals + rf_score and the
+                                   host filter and sort.  Same candidates, chosen lists
+                                   and runs under both values (DESIGN.md §4 "Candidate
+                                   selection" has the measurement behind the default)  */
 /* Keys 3, 5-8, 14 and 20 selected scorer variants measured slower and removed
    in round 3 (k_score_lean, the 128-lane k_score_ws, k_score_seg /
    k_score_segc, 16-diagonal k_score_segl, the unspecialised k_score_w2);
@@ -472,6 +481,82 @@ int rf_score_dense_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off,
  * out == NULL included. */
 int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off,
                        const int32_t *slots, const int32_t *ref_slot, double *out);
+
+/* Candidate selection on the device: the iteration loop's get_candidates ->
+ * choose_candidates (model.jl:499-526, proposals.jl:104-115) for many groups
+ * (clusters) at once, without the proposal list, the mask or the totals
+ * crossing to the host.  The call is rf_score_dense -- rf_score_dense_ref when
+ * ref_slot is not NULL, ref_slot[g] = -1 for a group without a reference --
+ * followed by two kernels over the dense table, which stays on the device.
+ *
+ * Slot (p, k) of group g (k = 0..3 Substitution, 4 Deletion, 5..8 Insertion,
+ * as rf_score_dense) is a proposal under source[g]:
+ *   0  all_proposals with substitutions and indels (INIT / SCORE without
+ *      seeds, model.jl:401-456); order within a position: Sub A..T, Del,
+ *      Ins A..T
+ *   1  alignment_proposals with indels (model.jl:483-497): the walks of
+ *      rf_alignment_proposals run into a device mask that is not downloaded;
+ *      order within a position Sub A..T, Ins A..T, Del -- the (pos, kind,
+ *      base) order in which that call's mask is read
+ *   2  alignment_proposals, substitutions only; order as 1
+ *   3  every substitution (all_proposals in REFINE)
+ *   4  in_mask's bytes for this group (FRAME: seeded all_proposals,
+ *      indel_correction_only); order as 0.  in_mask has rf_score_dense's row
+ *      layout for all groups; only the rows of source-4 groups are read, and it
+ *      may be NULL when there are none
+ * Under every source Sub and Del at p = 0 and the substitution to the
+ * consensus base are no proposals, and Insertion(0, b) comes before position 1.
+ * A proposal is a candidate iff total > score[g] on the FP64 total rf_score
+ * returns for it (NaN compares false).  A proposal slot that holds NaN fails
+ * the call as rf_score fails for a list with that proposal: RF_ERR_NUMERIC,
+ * "failed to compute a valid score"; other slots may hold anything.
+ *
+ * Candidates are reported in proposal order; the chosen list is
+ * choose_candidates': by descending score, equal scores to the earlier
+ * proposal (a stable sort), skipping a candidate with |pos - q| < min_dist for
+ * a position q chosen before it -- in rank order.  ncand[g] and nchosen[g] are
+ * the true counts; the record arrays (kind 0 Sub / 1 Ins / 2 Del, 1-based pos,
+ * base, score) receive the first off[g + 1] - off[g] entries of group g at
+ * off[g].  Each set of four arrays is given together with its offsets or left
+ * NULL (counts only); ncand and nchosen may be NULL too.
+ *
+ * Checks, stale-band refusals and messages are rf_score_dense(_ref)'s; a group
+ * without reads is RF_ERR_ARG.  A template longer than 393,184 is RF_ERR_ARG
+ * (the chooser's position bitmap lives in LDS).  The call fills no band, makes
+ * none stale, and a refused call changes nothing. */
+int rf_candidates(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
+                  const int32_t *ref_slot, const double *score, const uint8_t *source,
+                  const uint8_t *in_mask, int32_t min_dist,
+                  int32_t *ncand, const int64_t *cand_off, uint8_t *cand_kind, int32_t *cand_pos,
+                  uint8_t *cand_base, double *cand_score,
+                  int32_t *nchosen, const int64_t *chosen_off, uint8_t *ch_kind, int32_t *ch_pos,
+                  uint8_t *ch_base, double *ch_score);
+/* The same two kernels over a table the caller holds on the host (a table
+ * summed elsewhere, e.g. across ranks): group g has a consensus of m[g] bases
+ * at cons[cons_off[g] ...], its (m[g] + 1) x 9 totals in `table` and, for
+ * sources 1, 2 and 4, its mask bytes in `mask` (both in rf_score_dense's row
+ * layout; for sources 1 and 2 the mask is what rf_alignment_proposals
+ * returned).  Needs no slots, sequences or bands.  Outputs as rf_candidates. */
+int rf_candidates_table(rf_ctx *ctx, int32_t ngroups, const int32_t *m, const uint8_t *cons,
+                        const int64_t *cons_off, const double *table, const uint8_t *mask,
+                        const double *score, const uint8_t *source, int32_t min_dist,
+                        int32_t *ncand, const int64_t *cand_off, uint8_t *cand_kind, int32_t *cand_pos,
+                        uint8_t *cand_base, double *cand_score,
+                        int32_t *nchosen, const int64_t *chosen_off, uint8_t *ch_kind, int32_t *ch_pos,
+                        uint8_t *ch_base, double *ch_score);
+/* rf_candidates_table on the host alone: no context, no GPU
+ * (csrc/rifraf_candidates.h).  Returns 0, RF_ERR_ARG, or RF_ERR_NUMERIC for
+ * NaN in a proposal slot.  No template length limit. */
+int rf_host_candidates(int32_t ngroups, const int32_t *m, const uint8_t *cons, const int64_t *cons_off,
+                       const double *table, const uint8_t *mask, const double *score,
+                       const uint8_t *source, int32_t min_dist,
+                       int32_t *ncand, const int64_t *cand_off, uint8_t *cand_kind, int32_t *cand_pos,
+                       uint8_t *cand_base, double *cand_score,
+                       int32_t *nchosen, const int64_t *chosen_off, uint8_t *ch_kind, int32_t *ch_pos,
+                       uint8_t *ch_base, double *ch_score);
+/* Kernel time of k_cand_select and k_cand_choose in the last rf_candidates /
+ * rf_candidates_table call, milliseconds.  Either pointer may be NULL. */
+int rf_last_candidates_ms(const rf_ctx *ctx, double *select_ms, double *choose_ms);
 
 /* Native batched rifraf() (src/model.jl:1116-1275) for reference-free
  * clusters: the INIT stage of every cluster runs in lockstep on this context

@@ -241,6 +241,7 @@ struct Driver {
     std::vector<Read> reads;
     std::vector<Clu> clu;
     std::vector<int32_t> fixed_off, fixed;   // the caller's fixed batches
+    bool cand_device = false;                // RF_OPT_CAND_DEVICE, read when the run starts
 
     // RIFRAF_BATCH_TIMING: wall time and count of each engine call kind
     // (stderr at the end of rf_rifraf_batch; diagnostics only)
@@ -749,6 +750,72 @@ struct Driver {
         });
     }
 
+    // ---------------- get_candidates and choose_candidates on the device
+    // (RF_OPT_CAND_DEVICE = 1): one rf_candidates call for `cs`.  The proposal
+    // source follows the stage as in get_candidates above; FRAME's seeded
+    // all_proposals goes down as a mask.  cands[c] receives the chosen list in
+    // rank order (empty iff there is no candidate): handle_candidates needs no
+    // more, so no candidate record crosses to the host.
+    void get_candidates_device(std::vector<int> cs, std::vector<std::vector<Cand>> &cands)
+    {
+        cs.erase(std::remove_if(cs.begin(), cs.end(), [&](int c) { return clu[c].failed; }), cs.end());
+        batched(cs, [&](const std::vector<int> &s) {
+            std::vector<int32_t> off{0}, sl, ref;
+            std::vector<int64_t> choff{0};
+            std::vector<uint8_t> src, mask;
+            std::vector<double> score;
+            std::vector<Prop> props;
+            bool frame = false;
+            int64_t rows = 0;
+            for (int c : s) {
+                const Clu &C = clu[c];
+                for (int k = 0; k < (int)C.batch.size(); ++k)
+                    sl.push_back(C.slot0 + k);
+                off.push_back((int32_t)sl.size());
+                ref.push_back(C.stage == ST_FRAME ? C.ref_slot : -1);
+                frame = frame || C.stage == ST_FRAME;
+                const bool aln = P.do_alignment_proposals && (C.stage == ST_INIT || C.stage == ST_REFINE);
+                src.push_back((uint8_t)(C.stage == ST_FRAME ? 4 : C.stage == ST_INIT ? (aln ? 1 : 0) : (aln ? 2 : 3)));
+                score.push_back(C.score);
+                // chosen positions lie in 0..m, min_dist apart
+                const int64_t m = (int64_t)C.cons.size();
+                choff.push_back(choff.back() + (P.min_dist >= 1 ? m / P.min_dist + 1 : 8 * m + 4));
+                rows += m + 1;
+            }
+            if (frame) {
+                mask.assign((size_t)rows * 9, 0);
+                int64_t row = 0;
+                for (int c : s) {
+                    const Clu &C = clu[c];
+                    if (C.stage == ST_FRAME) {
+                        all_proposals(C.stage, C.cons, C.seeds, props);
+                        for (const Prop &p : props)
+                            mask[(size_t)(row + p.pos) * 9 + (p.kind == SUB ? p.base : p.kind == DEL ? 4 : 5 + p.base)] = 1;
+                    }
+                    row += (int64_t)C.cons.size() + 1;
+                }
+            }
+            const size_t n = s.size(), cap = (size_t)choff.back();
+            std::vector<int32_t> ncand(n), nch(n), pos(cap);
+            std::vector<uint8_t> kind(cap), base(cap);
+            std::vector<double> tot(cap);
+            if (int e = timed(T_SCORE, [&] {
+                    return rf_candidates(ctx, (int32_t)n, off.data(), sl.data(), frame ? ref.data() : nullptr,
+                                         score.data(), src.data(), frame ? mask.data() : nullptr, P.min_dist,
+                                         ncand.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nch.data(),
+                                         choff.data(), kind.data(), pos.data(), base.data(), tot.data());
+                }))
+                return e;
+            for (size_t g = 0; g < n; ++g) {
+                auto &out = cands[s[g]];
+                out.clear();
+                for (int64_t i = choff[g]; i < choff[g] + nch[g]; ++i)
+                    out.push_back({{kind[i], pos[i], base[i]}, tot[i]});
+            }
+            return 0;
+        });
+    }
+
     // ---------------- choose_candidates (proposals.jl:104-115)
     std::vector<Cand> choose(std::vector<Cand> cands) const
     {
@@ -832,7 +899,7 @@ struct Driver {
         for (int c : cs) {
             Clu &C = clu[c];
             C.old_cons = C.cons;
-            C.chosen = choose(cands[c]);
+            C.chosen = cand_device ? cands[c] : choose(cands[c]);
             std::vector<uint8_t> nc;
             if (!apply(C.old_cons, C.chosen, nc)) {
                 fail_cluster(c, "AmbiguousProposalsError");
@@ -988,6 +1055,8 @@ struct Driver {
         for (int c = 0; c < (int)clu.size(); ++c)
             live.push_back(c);
         std::vector<std::vector<Cand>> cands(clu.size());
+        int32_t cd = 0;
+        cand_device = rf_get_option(ctx, RF_OPT_CAND_DEVICE, &cd) == 0 && cd == 1;
         for (int it = 1; it <= P.max_iters && !live.empty(); ++it) {
             std::vector<int> act;
             for (int c : live) {
@@ -1035,7 +1104,10 @@ struct Driver {
                 clu[c].sip_pre = false;   // the scratch slot is refilled from here on (has_single_indels)
             for (int c : gc)
                 cands[c].clear();
-            get_candidates(gc, cands);
+            if (cand_device)
+                get_candidates_device(gc, cands);
+            else
+                get_candidates(gc, cands);
             std::vector<int> hc;
             for (int c : gc) {
                 Clu &C = clu[c];

@@ -62,6 +62,7 @@
 #include "rifraf_dp_plan.h"
 #include "rifraf_score_plan.h"
 #include "rifraf_seq_upload.h"
+#include "rifraf_candidates.h"
 
 #define RF_INF (__builtin_inf())
 
@@ -5470,7 +5471,7 @@ struct DevBuf {
 // touches a buffer: tables_chunk and set_sequences_codes_impl (after every
 // chunk) and rf_set_templates*; realign_run; pair_download, for every set;
 // rf_backtrace, rf_alignment_proposals, rf_score, score_dense_impl,
-// rf_score_dense_ref, rf_internal_aln_sums_dev and rf_qv_probs.  Nothing else
+// rf_score_dense_ref, rf_internal_aln_sums_dev, rf_qv_probs and cand_run.  Nothing else
 // enforces it: an entry point that returned with work in flight would have to
 // take buffers of its own, and a context serves one call at a time.
 enum Buf : int {
@@ -5548,6 +5549,18 @@ enum Buf : int {
     BUF_PAIR_INDEX,
     BUF_PAIR_INDEX_OFF,
     BUF_PAIR_LENGTHS,
+    // The candidate calls (cand_run, which waits for the stream after its
+    // downloads).  The proposal mask of rf_candidates, (m + 1) x 9 bytes per
+    // group at dplan's dense_off: the caller's rows of source 4, marked on top
+    // by the walks of sources 1 and 2, read by k_cand_select / k_cand_choose
+    // and never downloaded | rf_candidates_table: the caller's mask
+    BUF_CAND_MASK,
+    BUF_CAND_GROUPS,   // CandGroup
+    // the counts (ncand, then nchosen, per group), the chosen records, the
+    // candidate records: one download
+    BUF_CAND_OUT,
+    BUF_CAND_TABLE,    // rf_candidates_table: the caller's table
+    BUF_CAND_CONS,     // rf_candidates_table: the caller's consensus bases
     BUF_COUNT
 };
 
@@ -5603,6 +5616,7 @@ struct Opts : DpOpts, ScoreOpts {
     int pair_chunk = PS_CHUNK;   // RF_OPT_PAIR_CHUNK: pairs per launch set of rf_pair_scores / rf_pair_align
     int pair_trace_mb = PA_TRACE_MB;   // RF_OPT_PAIR_TRACE_MB: MB of move trace per launch set of rf_pair_align
     int pair_walk = 0;                 // RF_OPT_PAIR_WALK: 0 auto, 1 k_pa_walk (lane per pair), 2 k_pa_walk_w (wave per pair)
+    int cand_device = 0;    // RF_OPT_CAND_DEVICE: 1 = the native driver selects and chooses candidates with rf_candidates
 };
 
 }  // namespace
@@ -5655,6 +5669,8 @@ struct rf_ctx {
     double pair_ms = 0;         // kernels of the last rf_pair_scores
     double pa_fill_ms = 0, pa_walk_ms = 0;   // fills / walks of the last rf_pair_align
     double pa_emit_ms = 0;                   // k_pa_emit of the last rf_pair_align_text
+    double cand_select_ms = 0, cand_choose_ms = 0;   // k_cand_select / k_cand_choose of the last candidate call
+    hipEvent_t ev_cand[3] = {};
     hipEvent_t ev_codon = nullptr;
     hipEvent_t ev_block = nullptr;   // blocking-sync event (RF_OPT_SYNC_BLOCK)
     Opts opt;
@@ -6043,6 +6059,7 @@ void load_env_opts(Opts &o)
     o.bt_nw = env_int("RIFRAF_BT_NW", o.bt_nw);
     o.pair_trace_mb = env_int("RIFRAF_PAIR_TRACE_MB", o.pair_trace_mb);
     o.pair_walk = env_int("RIFRAF_PAIR_WALK", o.pair_walk);
+    o.cand_device = env_int("RIFRAF_CAND_DEVICE", o.cand_device);
 }
 
 // Launches the picked scorer over nitems items (split: partials of gy reads,
@@ -6214,6 +6231,8 @@ int rf_create(int device, rf_ctx **out)
     for (auto &e : ctx->ev)
         (void)hipEventCreate(&e);
     (void)hipEventCreate(&ctx->ev_codon);
+    for (auto &e : ctx->ev_cand)
+        (void)hipEventCreate(&e);
     (void)hipEventCreateWithFlags(&ctx->ev_block, hipEventBlockingSync | hipEventDisableTiming);
     (void)hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming);
     for (int i = 0; i < 3; ++i) {
@@ -6266,6 +6285,9 @@ int rf_destroy(rf_ctx *ctx)
         (void)hipEventDestroy(e);
     if (ctx->ev_codon)
         (void)hipEventDestroy(ctx->ev_codon);
+    for (auto &e : ctx->ev_cand)
+        if (e)
+            (void)hipEventDestroy(e);
     if (ctx->ev_block)
         (void)hipEventDestroy(ctx->ev_block);
     for (int i = 0; i < 3; ++i) {
@@ -6304,6 +6326,7 @@ static int *opt_slot(rf_ctx *ctx, int32_t key)
     case RF_OPT_PAIR_CHUNK: return &o.pair_chunk;
     case RF_OPT_PAIR_TRACE_MB: return &o.pair_trace_mb;
     case RF_OPT_PAIR_WALK: return &o.pair_walk;
+    case RF_OPT_CAND_DEVICE: return &o.cand_device;
     default: return dp_opt(o, key);   // the DP launch planner's
     }
 }
@@ -8807,5 +8830,477 @@ extern "C" int rf_qv_probs(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off
             err_out[1] = g;
             break;
         }
+    return 0;
+}
+
+// ---------------------------------------------------------------------
+// Candidate selection on the device: get_candidates' filter
+// (model.jl:499-526) and choose_candidates (proposals.jl:104-115) over a dense
+// table in rf_score_dense's layout, one workgroup of 256 per group (one
+// cluster).  Which slots are proposals, and their order, is stated once in
+// rifraf_candidates.h (with the host restatement, rf_host_candidates) and in
+// DESIGN.md §4 "Candidate selection".
+//
+// k_cand_select walks the group's 9 (m + 1) slots in proposal order, 256
+// consecutive order indices at a time (one contiguous stretch of the table
+// and of the mask, permuted only within a position's nine slots), and
+// compacts the candidates in that order: a ballot per wave, the waves' counts
+// through LDS, a running base.  Records past the capacity are counted only.
+//
+// k_cand_choose is the greedy choice without a sorted list: each round takes
+// the first candidate in (descending score, proposal order) that comes after
+// the last chosen one and whose position is not suppressed -- a block argmax
+// over the table -- and then suppresses the positions nearer than min_dist in
+// a bitmap of m + 1 bits in LDS.  Its memory does not depend on the number of
+// candidates; it runs nchosen + 1 rounds.
+// ---------------------------------------------------------------------
+struct alignas(16) CandGroup {
+    int64_t table_off;    // doubles: the group's (m + 1) x 9 totals
+    int64_t mask_off;     // bytes: its (m + 1) x 9 mask (sources 1, 2, 4)
+    int64_t cons_off;     // bytes: its consensus
+    int64_t cand_off, chosen_off;   // records
+    double score;         // state.score
+    int32_t m, source;
+    int32_t cand_cap, chosen_cap;
+};
+
+struct alignas(16) CandRec {
+    double score;
+    int32_t pos;
+    uint8_t kind, base, pad[2];
+};
+
+// the candidate at order index t of the group, if it is one: slot index and total
+__device__ __forceinline__ bool cand_at(const CandGroup &G, const double *__restrict__ T,
+                                        const uint8_t *__restrict__ M, const uint8_t *__restrict__ cons, int64_t t,
+                                        int &p, int &k, double &tot, int *__restrict__ err)
+{
+    p = (int)(t / 9);
+    k = cand_slot_of_rank(G.source, (int)(t - (int64_t)p * 9));
+    const int64_t at = (int64_t)p * 9 + k;
+    const int mb = cand_source_reads_mask(G.source) ? M[at] : 0;
+    // the cheap tests first: most slots of a mask are no proposals
+    if (cand_source_reads_mask(G.source) && !mb)
+        return false;
+    if (!cand_is_proposal(G.source, p, k, p > 0 ? (int)cons[p - 1] : -1, mb))
+        return false;
+    tot = T[at];
+    if (tot != tot) {
+        if (err)
+            set_err(err, 3);   // k_gather's: failed to compute a valid score
+        return false;
+    }
+    return tot > G.score;
+}
+
+__device__ __forceinline__ CandRec cand_rec(int p, int k, double tot)
+{
+    CandRec r;
+    r.score = tot;
+    r.pos = p;
+    r.kind = (uint8_t)cand_kind_of_slot(k);
+    r.base = (uint8_t)cand_base_of_slot(k);
+    r.pad[0] = r.pad[1] = 0;
+    return r;
+}
+
+__global__ void __launch_bounds__(256) k_cand_select(const CandGroup *__restrict__ groups,
+                                                     const double *__restrict__ table,
+                                                     const uint8_t *__restrict__ mask,
+                                                     const uint8_t *__restrict__ bases, CandRec *__restrict__ cand,
+                                                     int32_t *__restrict__ ncand, int *__restrict__ err)
+{
+    __shared__ int wsum[4];
+    const CandGroup G = groups[blockIdx.x];
+    const double *T = table + G.table_off;
+    const uint8_t *M = mask + G.mask_off;
+    const uint8_t *cons = bases + G.cons_off;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t total = 9 * ((int64_t)G.m + 1);
+    int base = 0;
+    for (int64_t t0 = 0; t0 < total; t0 += 256) {
+        const int64_t t = t0 + tid;
+        int p = 0, k = 0;
+        double tot = 0.0;
+        const bool is = t < total && cand_at(G, T, M, cons, t, p, k, tot, err);
+        const unsigned long long bal = __ballot(is);
+        if (lane == 0)
+            wsum[w] = __popcll(bal);
+        __syncthreads();
+        int wbase = 0, tile = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = wsum[i];
+            wbase += i < w ? c : 0;
+            tile += c;
+        }
+        const int idx = base + wbase + __popcll(bal & ((1ull << lane) - 1ull));
+        if (is && idx < G.cand_cap)
+            cand[G.cand_off + idx] = cand_rec(p, k, tot);
+        base += tile;
+        __syncthreads();   // wsum is written again
+    }
+    if (tid == 0)
+        ncand[blockIdx.x] = base;
+}
+
+__global__ void __launch_bounds__(256) k_cand_choose(const CandGroup *__restrict__ groups,
+                                                     const double *__restrict__ table,
+                                                     const uint8_t *__restrict__ mask,
+                                                     const uint8_t *__restrict__ bases, int min_dist,
+                                                     const int32_t *__restrict__ ncand,
+                                                     CandRec *__restrict__ chosen, int32_t *__restrict__ nchosen)
+{
+    extern __shared__ uint32_t supp[];   // min_dist >= 1: bit p set = position p is too near a chosen one
+    __shared__ double rs[4];
+    __shared__ int64_t ro[4];
+    const CandGroup G = groups[blockIdx.x];
+    const double *T = table + G.table_off;
+    const uint8_t *M = mask + G.mask_off;
+    const uint8_t *cons = bases + G.cons_off;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t total = 9 * ((int64_t)G.m + 1);
+    const bool dist = min_dist >= 1;
+    if (ncand[blockIdx.x] == 0) {   // the usual end of a stage: nothing to choose from
+        if (tid == 0)
+            nchosen[blockIdx.x] = 0;
+        return;
+    }
+    if (dist)
+        for (int i = tid; i < (G.m + 32) / 32; i += 256)
+            supp[i] = 0;
+    __syncthreads();
+    int n = 0;
+    double last_s = 0.0;
+    int64_t last_o = -1;
+    for (;;) {
+        double bs = 0.0;
+        int64_t bo = -1;   // none yet
+        for (int64_t t = tid; t < total; t += 256) {
+            int p, k;
+            double tot;
+            if (dist && ((supp[(int)(t / 9) >> 5] >> ((int)(t / 9) & 31)) & 1u))
+                continue;
+            if (!cand_at(G, T, M, cons, t, p, k, tot, nullptr))
+                continue;
+            if (n > 0 && !cand_before(last_s, last_o, tot, t))
+                continue;   // chosen already, or skipped for good
+            if (bo < 0 || cand_before(tot, t, bs, bo)) {
+                bs = tot;
+                bo = t;
+            }
+        }
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double os = __shfl_xor(bs, off);
+            const int64_t oo = __shfl_xor(bo, off);
+            if (oo >= 0 && (bo < 0 || cand_before(os, oo, bs, bo))) {
+                bs = os;
+                bo = oo;
+            }
+        }
+        if (lane == 0) {
+            rs[w] = bs;
+            ro[w] = bo;
+        }
+        __syncthreads();
+        bs = rs[0];
+        bo = ro[0];
+#pragma unroll
+        for (int i = 1; i < 4; ++i)
+            if (ro[i] >= 0 && (bo < 0 || cand_before(rs[i], ro[i], bs, bo))) {
+                bs = rs[i];
+                bo = ro[i];
+            }
+        if (bo < 0)
+            break;
+        const int p = (int)(bo / 9);
+        if (tid == 0 && n < G.chosen_cap)
+            chosen[G.chosen_off + n] = cand_rec(p, cand_slot_of_rank(G.source, (int)(bo - (int64_t)p * 9)), bs);
+        ++n;
+        last_s = bs;
+        last_o = bo;
+        if (dist) {
+            const int64_t lo = max((int64_t)0, (int64_t)p - (min_dist - 1));
+            const int64_t hi = min((int64_t)G.m, (int64_t)p + (min_dist - 1));
+            for (int64_t q = lo + tid; q <= hi; q += 256)
+                atomicOr(&supp[q >> 5], 1u << (q & 31));
+        }
+        __syncthreads();   // the bitmap, and rs / ro before the next round writes them
+    }
+    if (tid == 0)
+        nchosen[blockIdx.x] = n;
+}
+
+namespace {
+
+// widest template whose suppression bitmap k_cand_choose holds in 48 KB of LDS
+constexpr int64_t CAND_MAX_M = 48 * 1024 * 8 - 32;
+
+// the outputs of the candidate calls, as the caller passed them
+struct CandOut {
+    int32_t *ncand;
+    const int64_t *cand_off;
+    uint8_t *cand_kind;
+    int32_t *cand_pos;
+    uint8_t *cand_base;
+    double *cand_score;
+    int32_t *nchosen;
+    const int64_t *chosen_off;
+    uint8_t *ch_kind;
+    int32_t *ch_pos;
+    uint8_t *ch_base;
+    double *ch_score;
+};
+
+int cand_check(rf_ctx *ctx, const char *fn, int32_t ngroups, const CandOut &o)
+{
+    if (const char *why = cand_check_outputs(ngroups, o.cand_off, o.cand_kind, o.cand_pos, o.cand_base, o.cand_score))
+        return fail(ctx, RF_ERR_ARG, std::string(fn) + ": candidate " + why);
+    if (const char *why = cand_check_outputs(ngroups, o.chosen_off, o.ch_kind, o.ch_pos, o.ch_base, o.ch_score))
+        return fail(ctx, RF_ERR_ARG, std::string(fn) + ": chosen " + why);
+    return 0;
+}
+
+// H2D copy of caller memory into a context buffer, through the pinned ring when it fits
+int upload_raw(rf_ctx *ctx, DevBuf &b, const void *src, size_t bytes)
+{
+    if (int e = ensure_buf(ctx, b, std::max<size_t>(bytes, 16)))
+        return e;
+    if (!bytes)
+        return 0;
+    char *h;
+    if (int e = ring_take(ctx, bytes, &h))
+        return e;
+    if (h)
+        std::memcpy(h, src, bytes);
+    HIPCHK(ctx, hipMemcpyAsync(b.p, h ? (const void *)h : src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+
+// The two kernels over groups whose table, mask and consensus offsets are
+// set: record offsets and capacities from the caller's, one download of the
+// counts and the records, one wait.
+int cand_run(rf_ctx *ctx, const char *fn, std::vector<CandGroup> &gr, const double *d_table, const uint8_t *d_mask,
+             const uint8_t *d_cons, int32_t min_dist, const CandOut &o)
+{
+    const int32_t ng = (int32_t)gr.size();
+    ctx->cand_select_ms = ctx->cand_choose_ms = 0;
+    if (ng == 0)
+        return 0;
+    int64_t max_m = 0;
+    for (int32_t g = 0; g < ng; ++g) {
+        CandGroup &G = gr[g];
+        max_m = std::max<int64_t>(max_m, G.m);
+        G.cand_off = o.cand_kind ? o.cand_off[g] - o.cand_off[0] : 0;
+        G.chosen_off = o.ch_kind ? o.chosen_off[g] - o.chosen_off[0] : 0;
+        G.cand_cap = o.cand_kind ? (int32_t)std::min<int64_t>(o.cand_off[g + 1] - o.cand_off[g], INT32_MAX) : 0;
+        G.chosen_cap = o.ch_kind ? (int32_t)std::min<int64_t>(o.chosen_off[g + 1] - o.chosen_off[g], INT32_MAX) : 0;
+    }
+    if (max_m > CAND_MAX_M)
+        return fail(ctx, RF_ERR_ARG, std::string(fn) + ": template too long for the suppression bitmap");
+    const int64_t ncd = o.cand_kind ? o.cand_off[ng] - o.cand_off[0] : 0;
+    const int64_t nch = o.ch_kind ? o.chosen_off[ng] - o.chosen_off[0] : 0;
+    const size_t cb = (size_t)align_up((int64_t)ng * 2 * 4, 256);
+    const size_t bytes = cb + (size_t)(nch + ncd) * sizeof(CandRec);
+    if (int e = upload(ctx, ctx->scratch[BUF_CAND_GROUPS], gr)) return e;
+    if (int e = ensure_buf(ctx, ctx->scratch[BUF_CAND_OUT], bytes)) return e;
+    if (int e = ensure_hdn(ctx, bytes)) return e;
+    int32_t *d_cnt = dev<int32_t>(ctx, BUF_CAND_OUT);
+    CandRec *d_ch = (CandRec *)(dev<char>(ctx, BUF_CAND_OUT) + cb), *d_cd = d_ch + nch;
+    const CandGroup *d_gr = dev<const CandGroup>(ctx, BUF_CAND_GROUPS);
+    const size_t lds = min_dist >= 1 ? (size_t)((max_m + 32) / 32) * 4 : 4;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_cand[0], ctx->stream));
+    hipLaunchKernelGGL(k_cand_select, dim3((unsigned)ng), dim3(256), 0, ctx->stream, d_gr, d_table, d_mask, d_cons,
+                       d_cd, d_cnt, ctx->d_err);
+    HIPCHK(ctx, hipEventRecord(ctx->ev_cand[1], ctx->stream));
+    hipLaunchKernelGGL(k_cand_choose, dim3((unsigned)ng), dim3(256), lds, ctx->stream, d_gr, d_table, d_mask, d_cons,
+                       (int)min_dist, (const int32_t *)d_cnt, d_ch, d_cnt + ng);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->ev_cand[2], ctx->stream));
+    HIPCHK(ctx, pre_d2h(ctx));
+    HIPCHK(ctx, hipMemcpyAsync((char *)ctx->hdn + HDN_RES, d_cnt, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, land_err(ctx));
+    HIPCHK(ctx, stream_wait(ctx));   // gr sources its upload until here
+    float a = 0, b = 0;
+    (void)hipEventElapsedTime(&a, ctx->ev_cand[0], ctx->ev_cand[1]);
+    (void)hipEventElapsedTime(&b, ctx->ev_cand[1], ctx->ev_cand[2]);
+    ctx->cand_select_ms = a;
+    ctx->cand_choose_ms = b;
+    if (int e = check_err_hdn(ctx))
+        return e;
+    const int32_t *cnt = (const int32_t *)((const char *)ctx->hdn + HDN_RES);
+    const CandRec *ch = (const CandRec *)((const char *)ctx->hdn + HDN_RES + cb), *cd = ch + nch;
+    auto unpack = [](const CandRec *r, int64_t n, uint8_t *kind, int32_t *pos, uint8_t *base, double *sc) {
+        for (int64_t i = 0; i < n; ++i) {
+            kind[i] = r[i].kind;
+            pos[i] = r[i].pos;
+            base[i] = r[i].base;
+            sc[i] = r[i].score;
+        }
+    };
+    for (int32_t g = 0; g < ng; ++g) {
+        const CandGroup &G = gr[g];
+        if (o.ncand)
+            o.ncand[g] = cnt[g];
+        if (o.nchosen)
+            o.nchosen[g] = cnt[ng + g];
+        if (o.cand_kind) {
+            const int64_t at = o.cand_off[g];
+            unpack(cd + G.cand_off, std::min<int64_t>(cnt[g], G.cand_cap), o.cand_kind + at, o.cand_pos + at,
+                   o.cand_base + at, o.cand_score + at);
+        }
+        if (o.ch_kind) {
+            const int64_t at = o.chosen_off[g];
+            unpack(ch + G.chosen_off, std::min<int64_t>(cnt[ng + g], G.chosen_cap), o.ch_kind + at, o.ch_pos + at,
+                   o.ch_base + at, o.ch_score + at);
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int rf_candidates(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
+                             const int32_t *ref_slot, const double *score, const uint8_t *source,
+                             const uint8_t *in_mask, int32_t min_dist, int32_t *ncand, const int64_t *cand_off,
+                             uint8_t *cand_kind, int32_t *cand_pos, uint8_t *cand_base, double *cand_score,
+                             int32_t *nchosen, const int64_t *chosen_off, uint8_t *ch_kind, int32_t *ch_pos,
+                             uint8_t *ch_base, double *ch_score)
+{
+    if (!ctx || ngroups < 0 || (ngroups > 0 && (!slot_off || !slots || !score || !source)))
+        return fail(ctx, RF_ERR_ARG, "rf_candidates: bad arguments");
+    const CandOut o{ncand, cand_off, cand_kind, cand_pos, cand_base, cand_score,
+                    nchosen, chosen_off, ch_kind, ch_pos, ch_base, ch_score};
+    if (int e = cand_check(ctx, "rf_candidates", ngroups, o))
+        return e;
+    bool walks = false, given = false;
+    for (int32_t g = 0; g < ngroups; ++g) {
+        if (source[g] >= CAND_SRC_COUNT)
+            return fail(ctx, RF_ERR_ARG, "rf_candidates: unknown source");
+        walks = walks || source[g] == CAND_SRC_ALN || source[g] == CAND_SRC_ALN_SUBS;
+        given = given || source[g] == CAND_SRC_MASK;
+    }
+    if (given && !in_mask)
+        return fail(ctx, RF_ERR_ARG, "rf_candidates: source 4 needs a mask");
+    // 1. the dense table, with the reference term where a group has one: its
+    //    checks and refusals; the totals stay in BUF_DENSE_TOTALS
+    if (int e = ref_slot ? rf_score_dense_ref(ctx, ngroups, slot_off, slots, ref_slot, nullptr)
+                         : score_dense_impl(ctx, ngroups, slot_off, slots, nullptr, hipMemcpyDeviceToHost))
+        return e;
+    if (ngroups == 0)
+        return 0;
+    const ScorePlan &P = ctx->dplan.plan;
+    std::vector<CandGroup> gr(ngroups);
+    for (int32_t g = 0; g < ngroups; ++g) {
+        CandGroup &G = gr[g];
+        G.table_off = G.mask_off = P.groups[g].dense_off;
+        G.cons_off = P.groups[g].tb;
+        G.score = score[g];
+        G.m = P.groups[g].m;
+        G.source = source[g];
+    }
+    // 2. the mask: the caller's rows, then the walks' marks (with indels: a
+    //    group of source 2 reads the substitution slots only)
+    std::vector<uint8_t> hmask;   // sources its upload until cand_run's wait
+    if (given) {
+        hmask.assign((size_t)P.dense_total, 0);
+        for (int32_t g = 0; g < ngroups; ++g)
+            if (source[g] == CAND_SRC_MASK)
+                std::memcpy(hmask.data() + gr[g].mask_off, in_mask + gr[g].mask_off, (size_t)(gr[g].m + 1) * 9);
+        if (int e = upload(ctx, ctx->scratch[BUF_CAND_MASK], hmask)) return e;
+    } else if (walks) {
+        if (int e = ensure_buf(ctx, ctx->scratch[BUF_CAND_MASK], std::max<int64_t>(P.dense_total, 16))) return e;
+        HIPCHK(ctx, hipMemsetAsync(ctx->scratch[BUF_CAND_MASK].p, 0, P.dense_total, ctx->stream));
+    }
+    if (walks) {
+        std::vector<int32_t> ws;
+        std::vector<int64_t> wmask;
+        for (int32_t g = 0; g < ngroups; ++g)
+            if (source[g] == CAND_SRC_ALN || source[g] == CAND_SRC_ALN_SUBS)
+                for (int32_t k = slot_off[g]; k < slot_off[g + 1]; ++k) {
+                    ws.push_back(slots[k]);
+                    wmask.push_back(gr[g].mask_off);
+                }
+        std::vector<BTTask> tasks;
+        std::vector<int64_t> offs;
+        if (int e = build_bt_tasks(ctx, "rf_candidates", (int32_t)ws.size(), ws.data(), tasks, offs))
+            return e;
+        for (size_t k = 0; k < tasks.size(); ++k)
+            tasks[k].mask = wmask[k];
+        if (int e = launch_backtraces(ctx, tasks, dev<uint8_t>(ctx, BUF_CAND_MASK), 1))
+            return e;
+    }
+    // 3. select and choose
+    const int e = cand_run(ctx, "rf_candidates", gr, dev<const double>(ctx, BUF_DENSE_TOTALS),
+                           dev<const uint8_t>(ctx, BUF_CAND_MASK), (const uint8_t *)ctx->bytes_arena.d, min_dist, o);
+    if (walks && e != RF_ERR_HIP)
+        note_bt_ms(ctx);
+    return e;
+}
+
+extern "C" int rf_candidates_table(rf_ctx *ctx, int32_t ngroups, const int32_t *m, const uint8_t *cons,
+                                   const int64_t *cons_off, const double *table, const uint8_t *mask,
+                                   const double *score, const uint8_t *source, int32_t min_dist, int32_t *ncand,
+                                   const int64_t *cand_off, uint8_t *cand_kind, int32_t *cand_pos, uint8_t *cand_base,
+                                   double *cand_score, int32_t *nchosen, const int64_t *chosen_off, uint8_t *ch_kind,
+                                   int32_t *ch_pos, uint8_t *ch_base, double *ch_score)
+{
+    if (!ctx)
+        return RF_ERR_ARG;
+    if (const char *why = cand_check_table(ngroups, m, cons, cons_off, table, mask, score, source))
+        return fail(ctx, RF_ERR_ARG, std::string("rf_candidates_table: ") + why);
+    const CandOut o{ncand, cand_off, cand_kind, cand_pos, cand_base, cand_score,
+                    nchosen, chosen_off, ch_kind, ch_pos, ch_base, ch_score};
+    if (int e = cand_check(ctx, "rf_candidates_table", ngroups, o))
+        return e;
+    (void)hipSetDevice(ctx->device);
+    // the consensus bases packed group after group; table and mask as given
+    std::vector<CandGroup> gr(ngroups);
+    std::vector<uint8_t> hc;
+    int64_t rows = 0;
+    bool reads_mask = false;
+    for (int32_t g = 0; g < ngroups; ++g) {
+        CandGroup &G = gr[g];
+        G.table_off = G.mask_off = rows * 9;
+        G.cons_off = (int64_t)hc.size();
+        if (m[g] > 0)
+            hc.insert(hc.end(), cons + cons_off[g], cons + cons_off[g] + m[g]);
+        G.score = score[g];
+        G.m = m[g];
+        G.source = source[g];
+        reads_mask = reads_mask || cand_source_reads_mask(source[g]);
+        rows += (int64_t)m[g] + 1;
+    }
+    if (int e = upload_raw(ctx, ctx->scratch[BUF_CAND_TABLE], table, (size_t)rows * 9 * 8)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_CAND_CONS], hc)) return e;   // hc: alive until cand_run's wait
+    if (int e = upload_raw(ctx, ctx->scratch[BUF_CAND_MASK], mask, reads_mask ? (size_t)rows * 9 : 0)) return e;
+    return cand_run(ctx, "rf_candidates_table", gr, dev<const double>(ctx, BUF_CAND_TABLE),
+                    dev<const uint8_t>(ctx, BUF_CAND_MASK), dev<const uint8_t>(ctx, BUF_CAND_CONS), min_dist, o);
+}
+
+extern "C" int rf_host_candidates(int32_t ngroups, const int32_t *m, const uint8_t *cons, const int64_t *cons_off,
+                                  const double *table, const uint8_t *mask, const double *score,
+                                  const uint8_t *source, int32_t min_dist, int32_t *ncand, const int64_t *cand_off,
+                                  uint8_t *cand_kind, int32_t *cand_pos, uint8_t *cand_base, double *cand_score,
+                                  int32_t *nchosen, const int64_t *chosen_off, uint8_t *ch_kind, int32_t *ch_pos,
+                                  uint8_t *ch_base, double *ch_score)
+{
+    if (cand_check_table(ngroups, m, cons, cons_off, table, mask, score, source) ||
+        cand_check_outputs(ngroups, cand_off, cand_kind, cand_pos, cand_base, cand_score) ||
+        cand_check_outputs(ngroups, chosen_off, ch_kind, ch_pos, ch_base, ch_score))
+        return RF_ERR_ARG;
+    return host_candidates(ngroups, m, cons, cons_off, table, mask, score, source, min_dist, ncand, cand_off,
+                           cand_kind, cand_pos, cand_base, cand_score, nchosen, chosen_off, ch_kind, ch_pos, ch_base,
+                           ch_score);
+}
+
+extern "C" int rf_last_candidates_ms(const rf_ctx *ctx, double *select_ms, double *choose_ms)
+{
+    if (!ctx)
+        return RF_ERR_ARG;
+    if (select_ms)
+        *select_ms = ctx->cand_select_ms;
+    if (choose_ms)
+        *choose_ms = ctx->cand_choose_ms;
     return 0;
 }

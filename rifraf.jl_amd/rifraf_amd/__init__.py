@@ -25,6 +25,9 @@ def __getattr__(name):
     if name in ("Engine", "RifrafError"):
         from . import engine
         return getattr(engine, name)
+    if name in ("host_candidates", "CAND_SOURCES"):
+        from . import _lib
+        return getattr(_lib, name)
     if name in ("rifraf", "RifrafParams", "RifrafResult", "RifrafState", "correct_shifts",
                 "calibrate_phreds"):
         from . import model

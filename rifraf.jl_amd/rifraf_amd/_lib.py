@@ -90,6 +90,10 @@ _SIGNATURES = {
     "rf_host_row_codes": (c_int, [c_int32] + [c_void_p] * 6 + [c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 6),
     "rf_host_upload_chunks": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p,
                                       POINTER(c_int32)]),
+    "rf_candidates": (c_int, [c_void_p, c_int32] + [c_void_p] * 6 + [c_int32] + [c_void_p] * 12),
+    "rf_candidates_table": (c_int, [c_void_p, c_int32] + [c_void_p] * 7 + [c_int32] + [c_void_p] * 12),
+    "rf_host_candidates": (c_int, [c_int32] + [c_void_p] * 7 + [c_int32] + [c_void_p] * 12),
+    "rf_last_candidates_ms": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
     "rf_set_option": (c_int, [c_void_p, c_int32, c_int32]),
     "rf_get_option": (c_int, [c_void_p, c_int32, POINTER(c_int32)]),
 }
@@ -100,7 +104,7 @@ OPTIONS = {"score_mode": 1, "score_kernel": 2, "lean_lds_kb": 4, "dp_psplit": 10
            "band_pad": 17, "dp_wide": 18, "aln_sums_host": 19,
            "aln_marks_min": 22, "sync_block": 23, "dp_nl64": 24, "dp_lat": 26,
            "score_wgs": 27, "seg_wgs": 28, "dp_pfit": 29, "dp_mc": 30, "bt_nw": 31, "pair_chunk": 32,
-           "pair_trace_mb": 33, "pair_walk": 34}
+           "pair_trace_mb": 33, "pair_walk": 34, "cand_device": 35}
 # symbolic values of the enum-like options
 OPTION_VALUES = {"score_mode": {"auto": 0, "fused": 1, "split": 2},
                  "score_kernel": {"auto": 0, "general": 1, "seg": 2, "ws": 3},
@@ -273,6 +277,112 @@ def host_upload_chunks(off, codes, stage_kb=262144, budget=0, cins_off=None, cde
     if rc != 0:
         raise ValueError(f"rf_host_upload_chunks: bad arguments ({rc})")
     return end[:nc.value].tolist()
+
+
+# the `source` byte of the candidate calls (include/rifraf_hip.h rf_candidates)
+CAND_SOURCES = {"all": 0, "alignment": 1, "alignment_subs": 2, "subs": 3, "mask": 4}
+
+
+class CandidateIO:
+    """The arguments that rf_candidates, rf_candidates_table and
+    rf_host_candidates share -- scores, sources, min_dist and the twelve
+    output arguments -- for groups of rows[g] = m_g + 1 table rows, and the
+    outputs read back as ScoredProposal lists.  cand_cap / chosen_cap: None
+    gives every group room for all its 9 rows[g] slots, a number or one per
+    group that many records, False no record arrays at all (counts only)."""
+
+    def __init__(self, rows, scores, sources, min_dist, cand_cap=None, chosen_cap=None):
+        self.rows = [int(r) for r in rows]
+        G = self.G = len(self.rows)
+        self.scores = np.ascontiguousarray(scores, np.float64).reshape(-1)
+        src = [CAND_SOURCES.get(s, s) for s in sources]
+        self.sources = np.ascontiguousarray(src, np.uint8).reshape(-1)
+        if len(self.scores) != G or len(self.sources) != G:
+            raise ValueError("one score and one source per group")
+        self.min_dist = int(min_dist)
+        self.counts = [np.zeros(max(G, 1), np.int32) for _ in range(2)]
+        self.recs = []
+        for cap in (cand_cap, chosen_cap):
+            if cap is False:
+                self.recs.append(None)
+                continue
+            caps = [9 * r for r in self.rows] if cap is None else (
+                [int(cap)] * G if np.isscalar(cap) else [int(c) for c in cap])
+            off = np.zeros(G + 1, np.int64)
+            if G:
+                np.cumsum(caps, out=off[1:])
+            n = max(int(off[-1]), 1)
+            self.recs.append((off, np.full(n, 255, np.uint8), np.full(n, -1, np.int32), np.full(n, 255, np.uint8),
+                              np.full(n, np.nan)))
+
+    def args(self):
+        """score, source, [mask goes between them and min_dist in rf_candidates: see callers]"""
+        out = []
+        for cnt, rec in zip(self.counts, self.recs):
+            out.append(ptr(cnt))
+            out += [None] * 5 if rec is None else [ptr(a) for a in rec]
+        return out
+
+    def results(self, with_counts=False):
+        from .proposals import Proposal, ScoredProposal
+        lists = []
+        for cnt, rec in zip(self.counts, self.recs):
+            per = []
+            for g in range(self.G):
+                if rec is None:
+                    per.append(None)
+                    continue
+                off, kind, pos, base, sc = rec
+                a, n = int(off[g]), min(int(cnt[g]), int(off[g + 1] - off[g]))
+                per.append([ScoredProposal(Proposal(int(kind[i]), int(pos[i]), int(base[i])), float(sc[i]))
+                            for i in range(a, a + n)])
+            lists.append(per)
+        if with_counts:
+            return [(lists[0][g], lists[1][g], int(self.counts[0][g]), int(self.counts[1][g])) for g in range(self.G)]
+        return [(lists[0][g], lists[1][g]) for g in range(self.G)]
+
+
+def pack_candidate_tables(cons, tables, masks=None):
+    """Per-group consensus arrays, (m + 1, 9) tables and optional (m + 1, 9)
+    masks (None entries allowed) as rf_candidates_table's flat arguments:
+    (m, cons, cons_off, table, mask or None, rows)."""
+    m = np.ascontiguousarray([len(c) for c in cons], np.int32)
+    cons_off = np.zeros(len(cons) + 1, np.int64)
+    np.cumsum(m, out=cons_off[1:])
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(c, np.uint8) for c in cons]) if len(cons)
+                                else np.zeros(0), np.uint8)
+    if len(flat) == 0:
+        flat = np.zeros(1, np.uint8)
+    rows = [int(x) + 1 for x in m]
+    tabs = [np.asarray(t, np.float64).reshape(-1, 9) for t in tables]
+    if [len(t) for t in tabs] != rows:
+        raise ValueError("a table has m + 1 rows of 9")
+    table = np.ascontiguousarray(np.concatenate(tabs) if tabs else np.zeros((1, 9)))
+    mask = None
+    if masks is not None and any(k is not None for k in masks):
+        mask = np.ascontiguousarray(np.concatenate(
+            [np.zeros((r, 9), np.uint8) if k is None else np.asarray(k, np.uint8).reshape(r, 9)
+             for k, r in zip(masks, rows)]))
+    return m, flat, cons_off, table, mask, rows
+
+
+def host_candidates(cons, tables, scores, sources, min_dist, masks=None, cand_cap=None, chosen_cap=None,
+                    with_counts=False):
+    """rf_host_candidates: candidate selection and choose_candidates over
+    dense tables on the host alone (no context, no GPU).  cons / tables /
+    masks: one consensus, (m + 1, 9) table and (for sources 1, 2, 4) mask per
+    group; sources: 0..4 or CAND_SOURCES names.  Returns per group
+    (candidates, chosen) as ScoredProposal lists -- with_counts: also the true
+    counts.  NaN in a proposal slot raises ArithmeticError."""
+    m, flat, cons_off, table, mask, rows = pack_candidate_tables(cons, tables, masks)
+    io = CandidateIO(rows, scores, sources, min_dist, cand_cap, chosen_cap)
+    rc = load().rf_host_candidates(io.G, ptr(m), ptr(flat), ptr(cons_off), ptr(table), ptr(mask), ptr(io.scores),
+                                   ptr(io.sources), io.min_dist, *io.args())
+    if rc == -3:
+        raise ArithmeticError("failed to compute a valid score")
+    if rc != 0:
+        raise ValueError(f"rf_host_candidates: bad arguments ({rc})")
+    return io.results(with_counts)
 
 
 def ptr(a: np.ndarray | None):

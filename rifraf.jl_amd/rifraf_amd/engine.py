@@ -701,6 +701,56 @@ class Engine:
             at += r
         return res
 
+    def candidates(self, groups, scores, sources, min_dist, ref_slots=None, masks=None, cand_cap=None,
+                   chosen_cap=None, with_counts=False):
+        """rf_candidates: get_candidates' filter and choose_candidates on the
+        device.  groups: batch-slot arrays (one per cluster) or PackedGroups;
+        scores: state.score per group; sources: 0..4 or _lib.CAND_SOURCES
+        names ("all", "alignment", "alignment_subs", "subs", "mask");
+        ref_slots: one per group, -1 for none; masks: (m + 1, 9) masks for
+        the groups of source "mask" (None for the others).  Returns per group
+        (candidates, chosen) as ScoredProposal lists, candidates in proposal
+        order and chosen in rank order.  cand_cap / chosen_cap bound the
+        records returned per group (False: none, the list is None);
+        with_counts adds the true counts."""
+        pg = groups if isinstance(groups, PackedGroups) else pack_groups(groups)
+        G, slot_off, slots = pg.n, pg.slot_off, pg.slots
+        rows = [self.geometry(int(slots[slot_off[g]]), RF_BAND_B)[1] if slot_off[g + 1] > slot_off[g] else 1
+                for g in range(G)]
+        io = _lib.CandidateIO(rows, scores, sources, min_dist, cand_cap, chosen_cap)
+        refs = None
+        if ref_slots is not None:
+            refs = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
+            if len(refs) != G:
+                raise ValueError("one reference slot per group (-1: none)")
+            if not G:
+                refs = np.full(1, -1, np.int32)
+        mask = None
+        if masks is not None and any(k is not None for k in masks):
+            mask = np.ascontiguousarray(np.concatenate(
+                [np.zeros((r, 9), np.uint8) if k is None else np.asarray(k, np.uint8).reshape(r, 9)
+                 for k, r in zip(masks, rows)]))
+        self._check(self.lib.rf_candidates(self.ctx, G, ptr(slot_off), ptr(slots), ptr(refs), ptr(io.scores),
+                                           ptr(io.sources), ptr(mask), io.min_dist, *io.args()))
+        return io.results(with_counts)
+
+    def candidates_table(self, cons, tables, scores, sources, min_dist, masks=None, cand_cap=None, chosen_cap=None,
+                         with_counts=False):
+        """rf_candidates_table: the same selection over dense tables held on
+        the host (e.g. summed across ranks); arguments and result as
+        _lib.host_candidates, which is its host restatement."""
+        m, flat, cons_off, table, mask, rows = _lib.pack_candidate_tables(cons, tables, masks)
+        io = _lib.CandidateIO(rows, scores, sources, min_dist, cand_cap, chosen_cap)
+        self._check(self.lib.rf_candidates_table(self.ctx, io.G, ptr(m), ptr(flat), ptr(cons_off), ptr(table),
+                                                 ptr(mask), ptr(io.scores), ptr(io.sources), io.min_dist, *io.args()))
+        return io.results(with_counts)
+
+    def last_candidates_ms(self):
+        """(k_cand_select, k_cand_choose) kernel ms of the last candidates call."""
+        a, b = c_double(), c_double()
+        self._check(self.lib.rf_last_candidates_ms(self.ctx, byref(a), byref(b)))
+        return a.value, b.value
+
     def score_dense_dev(self, groups, dev_ptr: int):
         """rf_score_dense_dev: dense totals written to device memory at
         dev_ptr (sum_g (m_g+1)*9 doubles on this engine's device)."""
