@@ -5467,13 +5467,16 @@ struct DevBuf {
 // every exported call waits for that stream before it returns, so two calls
 // never have work in flight at once: a buffer with two users (X_OR_Y) holds
 // one content at a time, in stream order.  A new user takes a new enumerator.
-// The wait is each call's own stream_wait after its last launch or copy that
-// touches a buffer: tables_chunk and set_sequences_codes_impl (after every
-// chunk) and rf_set_templates*; realign_run; pair_download, for every set;
-// rf_backtrace, rf_alignment_proposals, rf_score, score_dense_impl,
-// rf_score_dense_ref, rf_internal_aln_sums_dev, rf_qv_probs and cand_run.  Nothing else
-// enforces it: an entry point that returned with work in flight would have to
-// take buffers of its own, and a context serves one call at a time.
+// A call that lands results or the error flag in the pinned zone waits in
+// land_wait, behind its last launch and copy (the landing helpers, below).
+// The calls that wait elsewhere, with a stream_wait of their own: realign_run
+// (the flag's copy goes first) and rf_score (its pageable per-read downloads
+// follow the flag's copy); the calls whose results go straight to the caller
+// -- score_dense_impl, rf_score_dense_ref, rf_internal_aln_sums_dev (before
+// its check_err) and rf_qv_probs; pair_download, for every set; and the
+// uploads: tables_chunk and set_sequences_codes_impl after every chunk,
+// rf_set_templates*.  An entry point that returned with work in flight would
+// have to take buffers of its own, and a context serves one call at a time.
 enum Buf : int {
     BUF_SCORE_ITEMS,    // rf_score: WorkItem
     BUF_SCORE_GROUPS,   // rf_score: ScoreGroup
@@ -5564,6 +5567,31 @@ enum Buf : int {
     BUF_COUNT
 };
 
+// The context's timing events (rf_ctx::ev), each named for the point on the
+// stream that it marks.  A call records its marks around its launches and
+// reads the time between two of them (mark_ms) after its stream wait.  A new
+// point takes a new enumerator.
+enum Ev : int {
+    EV_DP_BEGIN,   // rf_realign: around launch_dp
+    EV_DP_END,
+    EV_SCORER_BEGIN,   // rf_score and score_dense_impl: before the scorer (and k_reduce)
+    EV_CODON_BEGIN,    // rf_score: before k_codon
+    EV_SCORER_END,     // after the scorer and k_codon; rf_score's k_gather begins here
+    EV_GATHER_END,     // rf_score: after k_gather
+    EV_WALKS_BEGIN,    // launch_backtraces: around k_bt_win (and its descriptor upload)
+    EV_WALKS_END,
+    EV_CODON_DENSE_BEGIN,   // rf_score_dense_ref: around k_codon_dense
+    EV_CODON_DENSE_END,
+    EV_PAIR_FILL_BEGIN,   // a launch set of the pair calls: the fills, the walk, k_pa_emit
+    EV_PAIR_FILL_END,
+    EV_PAIR_WALK_END,
+    EV_PAIR_EMIT_END,
+    EV_CAND_SELECT_BEGIN,   // cand_run: k_cand_select, then k_cand_choose
+    EV_CAND_CHOOSE_BEGIN,
+    EV_CAND_CHOOSE_END,
+    EV_COUNT
+};
+
 }  // namespace
 
 // Host worker threads: OMP_NUM_THREADS when set (the GPU box's CPU share),
@@ -5625,7 +5653,7 @@ struct rf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t side[3] = {};   // concurrent DP class launches (fork/join on `stream`)
-    hipEvent_t ev[6];
+    hipEvent_t ev[EV_COUNT] = {};   // by Ev: the point on the stream each marks
     hipEvent_t fork = nullptr, join[3] = {};
     std::string err;
     Arena bytes_arena;  // sequence + template bases
@@ -5649,16 +5677,12 @@ struct rf_ctx {
     // MB took ~14 ms per cluster upload on the box: page locking per call)
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
-    // pinned landing zone for small per-call results (rf_realign's scores and
-    // the error flag): one D2H + one synchronize per call
-    void *hout = nullptr;
-    size_t hout_bytes = 0;
     // pinned ring for the per-call descriptor uploads (upload()): the runtime
     // stages a pageable H2D copy through a blit of its own
     void *up = nullptr;
     size_t up_bytes = 0, up_off = 0;
-    // pinned landing zone for the other calls' downloads (ensure_hdn): the
-    // error flag at 0, results from 16
+    // pinned landing zone for every call's downloads (ensure_landing): the
+    // error flag at 0, results from HDN_RES
     void *hdn = nullptr;
     size_t hdn_bytes = 0;
     DevBuf grow_segs;   // compaction descriptors (arena_grow may run inside other uploads)
@@ -5670,8 +5694,6 @@ struct rf_ctx {
     double pa_fill_ms = 0, pa_walk_ms = 0;   // fills / walks of the last rf_pair_align
     double pa_emit_ms = 0;                   // k_pa_emit of the last rf_pair_align_text
     double cand_select_ms = 0, cand_choose_ms = 0;   // k_cand_select / k_cand_choose of the last candidate call
-    hipEvent_t ev_cand[3] = {};
-    hipEvent_t ev_codon = nullptr;
     hipEvent_t ev_block = nullptr;   // blocking-sync event (RF_OPT_SYNC_BLOCK)
     Opts opt;
     uint64_t opt_gen = 0;      // bumped by rf_set_option (scorer plan key)
@@ -5834,10 +5856,10 @@ int ring_take(rf_ctx *ctx, size_t bytes, char **h)
     return 0;
 }
 
-template <class T>
-int upload(rf_ctx *ctx, DevBuf &b, const std::vector<T> &v)
+// H2D copy of host memory into a context buffer, through the pinned ring when
+// it fits; else `src` sources the copy until the call's stream wait
+int upload(rf_ctx *ctx, DevBuf &b, const void *src, size_t bytes)
 {
-    const size_t bytes = v.size() * sizeof(T);
     if (int e = ensure_buf(ctx, b, std::max<size_t>(bytes, 16)))
         return e;
     if (!bytes)
@@ -5846,10 +5868,15 @@ int upload(rf_ctx *ctx, DevBuf &b, const std::vector<T> &v)
     if (int e = ring_take(ctx, bytes, &h))
         return e;
     if (h)
-        std::memcpy(h, v.data(), bytes);
-    HIPCHK(ctx, hipMemcpyAsync(b.p, h ? (const void *)h : (const void *)v.data(), bytes, hipMemcpyHostToDevice,
-                               ctx->stream));
+        std::memcpy(h, src, bytes);
+    HIPCHK(ctx, hipMemcpyAsync(b.p, h ? (const void *)h : src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return 0;
+}
+
+template <class T>
+int upload(rf_ctx *ctx, DevBuf &b, const std::vector<T> &v)
+{
+    return upload(ctx, b, v.data(), v.size() * sizeof(T));
 }
 
 // Collect every live region of an arena, for compaction.
@@ -5946,42 +5973,17 @@ int region_ensure(rf_ctx *ctx, Arena &a, Region &r, int64_t bytes)
     return 0;
 }
 
-// The error flag and `bytes` of results land in ctx->hout (pinned, 16-B
-// error slot first); returns the results' host address.
-int ensure_hout(rf_ctx *ctx, size_t bytes)
-{
-    const size_t want = 16 + bytes;
-    if (ctx->hout_bytes >= want)
-        return 0;
-    if (ctx->hout)
-        (void)hipHostFree(ctx->hout);
-    ctx->hout = nullptr;
-    ctx->hout_bytes = 0;
-    const size_t sz = std::max<size_t>(want, 1 << 20);
-    if (hipHostMalloc(&ctx->hout, sz, hipHostMallocDefault) != hipSuccess)
-        return fail(ctx, RF_ERR_HIP, "pinned result buffer allocation failed");
-    ctx->hout_bytes = sz;
-    return 0;
-}
-
-// After the stream was synchronized with the error flag copied to hout.
-int check_err_landed(rf_ctx *ctx)
-{
-    const int h = *(const int *)ctx->hout;
-    if (h) {
-        int z = 0;
-        HIPCHK(ctx, hipMemcpy(ctx->d_err, &z, sizeof(int), hipMemcpyHostToDevice));
-        return fail(ctx, RF_ERR_NUMERIC, numeric_message(h));
-    }
-    return 0;
-}
-
-// Downloads of a call land in ctx->hdn (pinned: a pageable D2H copy is
-// staged by the runtime through a blit and a wait of its own): the error
-// flag at offset 0 (land_err), results from HDN_RES; the call queues them
-// behind its kernels, waits once, then copies the results out.
+// The landing zone: every call's downloads land in ctx->hdn (pinned: a
+// pageable D2H copy is staged by the runtime through a blit and a wait of its
+// own), the error flag at offset 0 and the results from HDN_RES.  A call
+// sizes the zone (ensure_landing), queues its results (land) and the flag
+// (land_flag) behind its kernels, waits for the stream once, reads the flag
+// (check_landed) and copies the results out (landed).  Offsets are bytes from
+// HDN_RES; a call with several parts keeps each 16-byte aligned.
+// pre_d2h goes before the copies of every call but realign_run, whose copies
+// all go to pinned memory and which never called it.
 constexpr size_t HDN_RES = 16;
-int ensure_hdn(rf_ctx *ctx, size_t bytes)
+int ensure_landing(rf_ctx *ctx, size_t bytes)
 {
     const size_t want = HDN_RES + bytes;
     if (ctx->hdn_bytes >= want)
@@ -5999,14 +6001,35 @@ int ensure_hdn(rf_ctx *ctx, size_t bytes)
     return 0;
 }
 
-// queue the error flag's copy into ctx->hdn (after ensure_hdn)
-hipError_t land_err(rf_ctx *ctx)
+// the landed bytes at offset `at`, as an array of T
+template <class T>
+const T *landed(const rf_ctx *ctx, size_t at = 0)
+{
+    return (const T *)((const char *)ctx->hdn + HDN_RES + at);
+}
+
+// queue the download of `bytes` at `src` on the device to offset `at`
+hipError_t land(rf_ctx *ctx, size_t at, const void *src, size_t bytes)
+{
+    return hipMemcpyAsync((char *)ctx->hdn + HDN_RES + at, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
+}
+
+// queue the error flag's copy
+hipError_t land_flag(rf_ctx *ctx)
 {
     return hipMemcpyAsync(ctx->hdn, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
 }
 
-// after the stream wait: the landed error flag
-int check_err_hdn(rf_ctx *ctx)
+// the end of a call's stream work: the flag behind everything queued so far,
+// then the call's one wait
+hipError_t land_wait(rf_ctx *ctx)
+{
+    const hipError_t e = land_flag(ctx);
+    return e != hipSuccess ? e : stream_wait(ctx);
+}
+
+// after the wait: the landed error flag; a raised one is cleared on the device
+int check_landed(rf_ctx *ctx)
 {
     const int h = *(const int *)ctx->hdn;
     if (h) {
@@ -6017,14 +6040,21 @@ int check_err_hdn(rf_ctx *ctx)
     return 0;
 }
 
+// the whole call end of a call that lands nothing but the flag
 int check_err(rf_ctx *ctx)
 {
-    if (int e = ensure_hdn(ctx, 0))
+    if (int e = ensure_landing(ctx, 0))
         return e;
     HIPCHK(ctx, pre_d2h(ctx));
-    HIPCHK(ctx, land_err(ctx));
-    HIPCHK(ctx, stream_wait(ctx));
-    return check_err_hdn(ctx);
+    HIPCHK(ctx, land_wait(ctx));
+    return check_landed(ctx);
+}
+
+// milliseconds between two marks of the stream, after the wait (0 if the query fails)
+double mark_ms(const rf_ctx *ctx, Ev a, Ev b)
+{
+    float ms = 0;
+    return hipEventElapsedTime(&ms, ctx->ev[a], ctx->ev[b]) == hipSuccess ? ms : 0.0;
 }
 
 int env_int(const char *name, int dflt)
@@ -6230,9 +6260,6 @@ int rf_create(int device, rf_ctx **out)
     load_env_opts(ctx->opt);
     for (auto &e : ctx->ev)
         (void)hipEventCreate(&e);
-    (void)hipEventCreate(&ctx->ev_codon);
-    for (auto &e : ctx->ev_cand)
-        (void)hipEventCreate(&e);
     (void)hipEventCreateWithFlags(&ctx->ev_block, hipEventBlockingSync | hipEventDisableTiming);
     (void)hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming);
     for (int i = 0; i < 3; ++i) {
@@ -6273,8 +6300,6 @@ int rf_destroy(rf_ctx *ctx)
         (void)hipFree(ctx->codes.errlut.p);
     if (ctx->pinned)
         (void)hipHostFree(ctx->pinned);
-    if (ctx->hout)
-        (void)hipHostFree(ctx->hout);
     if (ctx->up)
         (void)hipHostFree(ctx->up);
     if (ctx->hdn)
@@ -6282,10 +6307,6 @@ int rf_destroy(rf_ctx *ctx)
     if (ctx->d_err)
         (void)hipFree(ctx->d_err);
     for (auto &e : ctx->ev)
-        (void)hipEventDestroy(e);
-    if (ctx->ev_codon)
-        (void)hipEventDestroy(ctx->ev_codon);
-    for (auto &e : ctx->ev_cand)
         if (e)
             (void)hipEventDestroy(e);
     if (ctx->ev_block)
@@ -6783,11 +6804,11 @@ static int set_sequences_codes_impl(rf_ctx *ctx, int32_t first, int32_t nseq, co
         // est | tsum | ucode are contiguous on the device: one copy into the
         // pinned landing zone
         const size_t ob = (size_t)std::max(nseq, 1) * 20;
-        if (int e = ensure_hdn(ctx, ob)) return e;
-        char *hl = (char *)ctx->hdn + HDN_RES;
+        if (int e = ensure_landing(ctx, ob)) return e;
         HIPCHK(ctx, pre_d2h(ctx));
-        HIPCHK(ctx, hipMemcpyAsync(hl, d_est, ob, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, land(ctx, 0, d_est, ob));
         HIPCHK(ctx, stream_wait(ctx));
+        const char *hl = landed<char>(ctx);
         const size_t ns = (size_t)std::max(nseq, 1);
         std::memcpy(est, hl, (size_t)nseq * 8);
         std::memcpy(tsum, hl + ns * 8, (size_t)nseq * 8);
@@ -7231,24 +7252,23 @@ static int realign_run(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const in
     if (int e = ensure_buf(ctx, ctx->scratch[BUF_DP_SCORES], sizeof(double) * 2 * std::max(njobs, 1)))
         return e;
     double *d_out = dev<double>(ctx, BUF_DP_SCORES);
-    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_DP_BEGIN], ctx->stream));
     if (int e = launch_dp(ctx, P.dp, d_out))
         return e;
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    // scores and the error flag into pinned memory, one synchronize
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_DP_END], ctx->stream));
+    // the error flag, then the scores, into the landing zone: one wait
     const size_t ob = (out_score && njobs > 0) ? sizeof(double) * njobs : 0;
-    if (int e = ensure_hout(ctx, ob))
+    if (int e = ensure_landing(ctx, ob))
         return e;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->hout, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, land_flag(ctx));
     if (ob)
-        HIPCHK(ctx, hipMemcpyAsync((char *)ctx->hout + 16, d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, land(ctx, 0, d_out, ob));
     HIPCHK(ctx, stream_wait(ctx));
+    // the scores and the time go out whether or not a fill raised
     if (ob)
-        std::memcpy(out_score, (const char *)ctx->hout + 16, ob);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
-    ctx->dp_ms = ms;
-    if (int e = check_err_landed(ctx))
+        std::memcpy(out_score, landed<double>(ctx), ob);
+    ctx->dp_ms = mark_ms(ctx, EV_DP_BEGIN, EV_DP_END);
+    if (int e = check_landed(ctx))
         return e;
     ctx->last_dp = P.dp.launches;
     return 0;
@@ -7489,9 +7509,6 @@ struct PairIo {
 // sees a pair's k, score, nmoves and nerrors; says whether its moves and texts go to the caller
 using PairEnded = std::function<bool(int64_t, double, int32_t, int32_t)>;
 
-// rf_ctx::ev of a launch set (rf_realign and the scoring calls use the same events)
-enum { EV_PAIR_FILL_START = 0, EV_PAIR_FILL_END = 1, EV_PAIR_WALK_END = 2, EV_PAIR_EMIT_END = 3 };
-
 // Step 1 of a launch set: its descriptors on the device, room for its products
 static int pair_stage(rf_ctx *ctx, const PairSet &s, const PairLanding &L, const PairWants &w)
 {
@@ -7528,7 +7545,7 @@ static int pair_stage(rf_ctx *ctx, const PairSet &s, const PairLanding &L, const
     if (w.emit)
         if (int e = ensure_buf(ctx, b[BUF_PAIR_LENGTHS], L.lens))
             return e;
-    return ensure_hdn(ctx, L.total);
+    return ensure_landing(ctx, L.total);
 }
 
 // Step 2: the fills, then with a trace the walk (k_pa_walk_w or k_pa_walk by
@@ -7543,7 +7560,7 @@ static int pair_launch(rf_ctx *ctx, const PairSet &s, const PairWants &w)
     int8_t *d_mv = w.want_mv() ? dev<int8_t>(ctx, BUF_PAIR_MOVES) : nullptr;
     const int64_t *d_mvoff = dev<const int64_t>(ctx, BUF_PAIR_MOVE_OFF);
     int32_t *d_cnt = dev<int32_t>(ctx, BUF_PAIR_COUNTS);
-    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_FILL_START], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_FILL_BEGIN], ctx->stream));
     if (int e = pair_fill(ctx, s.pl, d_out, d_tr))
         return e;
     HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_FILL_END], ctx->stream));
@@ -7578,10 +7595,7 @@ static int pair_launch(rf_ctx *ctx, const PairSet &s, const PairWants &w)
 static int pair_download(rf_ctx *ctx, const PairSet &s, const PairLanding &L, const PairWants &w)
 {
     const size_t mv = (size_t)s.mv_total;
-    auto get = [&](size_t at, Buf b, size_t bytes) {
-        return hipMemcpyAsync((char *)ctx->hdn + HDN_RES + at, ctx->scratch[b].p, bytes, hipMemcpyDeviceToHost,
-                              ctx->stream);
-    };
+    auto get = [&](size_t at, Buf b, size_t bytes) { return land(ctx, at, ctx->scratch[b].p, bytes); };
     HIPCHK(ctx, get(0, BUF_PAIR_SCORES, L.scores));
     if (w.walk)
         HIPCHK(ctx, get(L.scores, BUF_PAIR_COUNTS, L.counts));
@@ -7605,10 +7619,10 @@ static void pair_collect(rf_ctx *ctx, const PairIo &io, int64_t p0, const PairSe
                          const PairWants &w, const PairEnded &ended)
 {
     const int64_t cn = s.cn;
-    const char *h = (const char *)ctx->hdn + HDN_RES;
-    const double *sc = (const double *)h;
-    const int32_t *cnt = (const int32_t *)(h + L.scores);
-    const int32_t *len = (const int32_t *)(h + L.len_at);   // aln_len, t2s_len, tolerance: cn of each
+    const char *h = landed<char>(ctx);
+    const double *sc = landed<double>(ctx);
+    const int32_t *cnt = landed<int32_t>(ctx, L.scores);
+    const int32_t *len = landed<int32_t>(ctx, L.len_at);   // aln_len, t2s_len, tolerance: cn of each
     const PairText *tx = io.tx;
     for (int64_t i = 0; i < cn; ++i) {
         const int64_t k = io.at(p0 + i);
@@ -7643,19 +7657,14 @@ static void pair_collect(rf_ctx *ctx, const PairIo &io, int64_t p0, const PairSe
             std::memcpy(tx->t2s + tx->t2s_off[k], h + L.ix_at + sizeof(int32_t) * (size_t)s.ixoff[(size_t)i],
                         sizeof(int32_t) * (size_t)il);
     }
-    auto ms = [&](int a, int b) {
-        float t = 0;
-        (void)hipEventElapsedTime(&t, ctx->ev[a], ctx->ev[b]);
-        return t;
-    };
     if (!w.trace) {
-        ctx->pair_ms += ms(EV_PAIR_FILL_START, EV_PAIR_FILL_END);
+        ctx->pair_ms += mark_ms(ctx, EV_PAIR_FILL_BEGIN, EV_PAIR_FILL_END);
         return;
     }
-    ctx->pa_fill_ms += ms(EV_PAIR_FILL_START, EV_PAIR_FILL_END);
-    ctx->pa_walk_ms += ms(EV_PAIR_FILL_END, EV_PAIR_WALK_END);
+    ctx->pa_fill_ms += mark_ms(ctx, EV_PAIR_FILL_BEGIN, EV_PAIR_FILL_END);
+    ctx->pa_walk_ms += mark_ms(ctx, EV_PAIR_FILL_END, EV_PAIR_WALK_END);
     if (w.emit)
-        ctx->pa_emit_ms += ms(EV_PAIR_WALK_END, EV_PAIR_EMIT_END);
+        ctx->pa_emit_ms += mark_ms(ctx, EV_PAIR_WALK_END, EV_PAIR_EMIT_END);
 }
 
 // The body of every pair call (one round of rf_pair_align_smart): the pairs of
@@ -7863,7 +7872,7 @@ static int launch_backtraces(rf_ctx *ctx, std::vector<BTTask> &tasks, uint8_t *d
     std::vector<BTTask> &win = ctx->bt_win;   // alive until the caller's sync
     win = tasks;
     int32_t *d_cnt = dev<int32_t>(ctx, BUF_COUNTS_OR_PROPS);
-    HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_WALKS_BEGIN], ctx->stream));
     if (!win.empty()) {
         if (int e = upload(ctx, ctx->scratch[BUF_BT_TASKS], win))
             return e;
@@ -7877,7 +7886,7 @@ static int launch_backtraces(rf_ctx *ctx, std::vector<BTTask> &tasks, uint8_t *d
                            dev<int8_t>(ctx, BUF_MOVES_OR_CTASKS), d_cnt, d_cnt + nslots, ctx->d_err, d_mask, do_indels);
     }
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_WALKS_END], ctx->stream));
     return 0;
 }
 
@@ -7885,7 +7894,7 @@ static int launch_backtraces(rf_ctx *ctx, std::vector<BTTask> &tasks, uint8_t *d
 static void note_bt_ms(rf_ctx *ctx)
 {
     float ms = 0;
-    if (hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]) == hipSuccess)
+    if (hipEventElapsedTime(&ms, ctx->ev[EV_WALKS_BEGIN], ctx->ev[EV_WALKS_END]) == hipSuccess)
         ctx->bt_ms = ms;
 }
 
@@ -7930,25 +7939,22 @@ int rf_backtrace(rf_ctx *ctx, int32_t nslots, const int32_t *slot, int8_t *moves
     if (nslots > 0)
         if (int e = launch_backtraces(ctx, tasks, nullptr, 0))
             return e;
-    // counts, then the moves, land in ctx->hdn with the error flag: one wait
+    // the counts at 0, then the moves at cb, land with the error flag: one wait
     const size_t cb = (sizeof(int32_t) * 2 * (size_t)nslots + 15) & ~(size_t)15;
-    if (int e = ensure_hdn(ctx, cb + (moves ? (size_t)total : 0)))
+    if (int e = ensure_landing(ctx, cb + (moves ? (size_t)total : 0)))
         return e;
-    const int32_t *cnt = (const int32_t *)((char *)ctx->hdn + HDN_RES);
-    const int8_t *all = (const int8_t *)((char *)ctx->hdn + HDN_RES + cb);
     HIPCHK(ctx, pre_d2h(ctx));
     if (nslots > 0)
-        HIPCHK(ctx, hipMemcpyAsync((void *)cnt, d_cnt, sizeof(int32_t) * 2 * nslots, hipMemcpyDeviceToHost,
-                                   ctx->stream));
+        HIPCHK(ctx, land(ctx, 0, d_cnt, sizeof(int32_t) * 2 * nslots));
     if (moves && total > 0)
-        HIPCHK(ctx, hipMemcpyAsync((void *)all, ctx->scratch[BUF_MOVES_OR_CTASKS].p, total, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    HIPCHK(ctx, land_err(ctx));
-    HIPCHK(ctx, stream_wait(ctx));
+        HIPCHK(ctx, land(ctx, cb, ctx->scratch[BUF_MOVES_OR_CTASKS].p, total));
+    HIPCHK(ctx, land_wait(ctx));
     if (nslots > 0)
         note_bt_ms(ctx);
-    if (int e = check_err_hdn(ctx))
+    if (int e = check_landed(ctx))
         return e;
+    const int32_t *cnt = landed<int32_t>(ctx);
+    const int8_t *all = landed<int8_t>(ctx, cb);
     for (int32_t k = 0; k < nslots; ++k) {
         if (nmoves)
             nmoves[k] = cnt[k];
@@ -7995,17 +8001,15 @@ int rf_alignment_proposals(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off
     if (int e = launch_backtraces(ctx, tasks, dev<uint8_t>(ctx, BUF_READS_OR_MASK), do_indels ? 1 : 0))
         return e;
     HIPCHK(ctx, hipGetLastError());
-    if (int e = ensure_hdn(ctx, mask_total))
+    if (int e = ensure_landing(ctx, mask_total))
         return e;
     HIPCHK(ctx, pre_d2h(ctx));
-    HIPCHK(ctx, hipMemcpyAsync((char *)ctx->hdn + HDN_RES, ctx->scratch[BUF_READS_OR_MASK].p, mask_total,
-                               hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, land_err(ctx));
-    HIPCHK(ctx, stream_wait(ctx));
+    HIPCHK(ctx, land(ctx, 0, ctx->scratch[BUF_READS_OR_MASK].p, mask_total));
+    HIPCHK(ctx, land_wait(ctx));
     note_bt_ms(ctx);
-    if (int e = check_err_hdn(ctx))
+    if (int e = check_landed(ctx))
         return e;
-    std::memcpy(out_mask, (char *)ctx->hdn + HDN_RES, mask_total);
+    std::memcpy(out_mask, landed<uint8_t>(ctx), mask_total);
     return 0;
 }
 
@@ -8136,7 +8140,7 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
     const double *d_tabs = (const double *)ctx->tab_arena.d;
     const double *d_bands = (const double *)ctx->band_arena.d;
 
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SCORER_BEGIN], ctx->stream));
     unsigned gy = 0;
     if (!items.empty()) {
         gy = launch_scorer(ctx, P.pick, (unsigned)items.size(), split ? (unsigned)P.max_reads : 1u,
@@ -8147,27 +8151,26 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
                                ctx->stream, dev<const ScoreGroup>(ctx, BUF_SCORE_GROUPS), ngroups, d_gstart,
                                dense_total, d_split, d_dense);
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_codon, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_CODON_BEGIN], ctx->stream));
     if (!ctasks.empty())
         hipLaunchKernelGGL(k_codon, dim3((unsigned)((ctasks.size() + 63) / 64)), dim3(64), 0,
                            ctx->stream, dev<const CodonTask>(ctx, BUF_MOVES_OR_CTASKS), (int)ctasks.size(),
                            d_bases, d_tabs, d_bands, d_cscr, d_ref);
-    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SCORER_END], ctx->stream));
     if (nprops > 0)
         hipLaunchKernelGGL(k_gather, dim3((unsigned)((nprops + 255) / 256)), dim3(256), 0, ctx->stream,
                            nprops, d_pgroup, d_kind, d_pos, d_base, dev<const ScoreGroup>(ctx, BUF_SCORE_GROUPS),
                            d_hr, d_dense, d_ref, d_href, d_out, ctx->d_err);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-    // the totals land in ctx->hdn with the error flag (per-read columns, a
-    // test / sharding path, stay pageable)
-    if (int e = ensure_hdn(ctx, (size_t)std::max<int64_t>(nprops, 0) * 8))
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_GATHER_END], ctx->stream));
+    // the totals land with the error flag (per-read columns, a test /
+    // sharding path, stay pageable and follow the flag)
+    if (int e = ensure_landing(ctx, (size_t)std::max<int64_t>(nprops, 0) * 8))
         return e;
     HIPCHK(ctx, pre_d2h(ctx));
     if (nprops > 0)
-        HIPCHK(ctx, hipMemcpyAsync((char *)ctx->hdn + HDN_RES, d_out, nprops * 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    HIPCHK(ctx, land_err(ctx));
+        HIPCHK(ctx, land(ctx, 0, d_out, nprops * 8));
+    HIPCHK(ctx, land_flag(ctx));
     std::vector<double> split_host;
     if (out_per_seq && split_total > 0) {
         split_host.resize(split_total);
@@ -8180,12 +8183,9 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
         HIPCHK(ctx, hipMemcpyAsync(ref_host.data(), d_ref, nprops * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(ctx, stream_wait(ctx));
-    float a = 0, b = 0, cms = 0;
-    (void)hipEventElapsedTime(&a, ctx->ev[2], ctx->ev[3]);
-    (void)hipEventElapsedTime(&b, ctx->ev[3], ctx->ev[4]);
-    (void)hipEventElapsedTime(&cms, ctx->ev_codon, ctx->ev[3]);
-    ctx->score_ms = a;
-    ctx->gather_ms = b;
+    ctx->score_ms = mark_ms(ctx, EV_SCORER_BEGIN, EV_SCORER_END);
+    ctx->gather_ms = mark_ms(ctx, EV_SCORER_END, EV_GATHER_END);
+    const double cms = mark_ms(ctx, EV_CODON_BEGIN, EV_SCORER_END);
     ctx->codon_ms = ctasks.empty() ? 0.0 : cms;
     if (out_per_seq) {
         // [k][r] rows, r = batch position (+1 column for the reference, if any)
@@ -8206,10 +8206,10 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
             }
         }
     }
-    if (int e = check_err_hdn(ctx))
+    if (int e = check_landed(ctx))
         return e;
     if (nprops > 0)
-        std::memcpy(out_total, (char *)ctx->hdn + HDN_RES, nprops * 8);
+        std::memcpy(out_total, landed<double>(ctx), nprops * 8);
     note_score_launch(ctx, P.pick, split, items.size(), gy);
     return 0;
 }
@@ -8271,7 +8271,7 @@ static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_of
                                sizeof(double) * std::max<int64_t>(P.split_total, 1)))
             return e;
     double *d_dense = dev<double>(ctx, BUF_DENSE_TOTALS);
-    HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SCORER_BEGIN], ctx->stream));
     unsigned gy = 0;
     if (nitems) {
         gy = launch_scorer(ctx, P.pick, (unsigned)nitems, split ? (unsigned)P.max_reads : 1u,
@@ -8285,15 +8285,13 @@ static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_of
                                dev<const double>(ctx, BUF_RING_OR_SPLIT), d_dense);
     }
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SCORER_END], ctx->stream));
     if (out && P.dense_total > 0) {
         HIPCHK(ctx, pre_d2h(ctx));
         HIPCHK(ctx, hipMemcpyAsync(out, d_dense, sizeof(double) * P.dense_total, out_kind, ctx->stream));
     }
     HIPCHK(ctx, stream_wait(ctx));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]);
-    ctx->score_ms = ms;
+    ctx->score_ms = mark_ms(ctx, EV_SCORER_BEGIN, EV_SCORER_END);
     ctx->gather_ms = 0;
     note_score_launch(ctx, P.pick, split, nitems, gy);
     return 0;
@@ -8361,19 +8359,17 @@ int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
         if (nblk > INT32_MAX)
             return fail(ctx, RF_ERR_ARG, "rf_score_dense_ref: too many slots for one launch");
         if (int e = upload(ctx, ctx->scratch[BUF_CODON_GROUPS], cg)) return e;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_codon, ctx->stream));
+        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_CODON_DENSE_BEGIN], ctx->stream));
         hipLaunchKernelGGL(k_codon_dense, dim3((unsigned)nblk), dim3(64), 0, ctx->stream,
                            dev<const CodonDenseGroup>(ctx, BUF_CODON_GROUPS), (int)cg.size(),
                            (const uint8_t *)ctx->bytes_arena.d, (const double *)ctx->tab_arena.d,
                            (const double *)ctx->band_arena.d, d_dense);
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_CODON_DENSE_END], ctx->stream));
         // cg sources the upload when it does not fit the pinned ring
         HIPCHK(ctx, stream_wait(ctx));
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ctx->ev_codon, ctx->ev[4]);
-        ctx->codon_dense_ms = ms;
-        ctx->score_ms += ms;
+        ctx->codon_dense_ms = mark_ms(ctx, EV_CODON_DENSE_BEGIN, EV_CODON_DENSE_END);
+        ctx->score_ms += ctx->codon_dense_ms;
     }
     if (out && P.dense_total > 0) {
         HIPCHK(ctx, hipMemcpyAsync(out, d_dense, sizeof(double) * P.dense_total, hipMemcpyDeviceToHost,
@@ -9061,22 +9057,6 @@ int cand_check(rf_ctx *ctx, const char *fn, int32_t ngroups, const CandOut &o)
     return 0;
 }
 
-// H2D copy of caller memory into a context buffer, through the pinned ring when it fits
-int upload_raw(rf_ctx *ctx, DevBuf &b, const void *src, size_t bytes)
-{
-    if (int e = ensure_buf(ctx, b, std::max<size_t>(bytes, 16)))
-        return e;
-    if (!bytes)
-        return 0;
-    char *h;
-    if (int e = ring_take(ctx, bytes, &h))
-        return e;
-    if (h)
-        std::memcpy(h, src, bytes);
-    HIPCHK(ctx, hipMemcpyAsync(b.p, h ? (const void *)h : src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return 0;
-}
-
 // The two kernels over groups whose table, mask and consensus offsets are
 // set: record offsets and capacities from the caller's, one download of the
 // counts and the records, one wait.
@@ -9104,32 +9084,28 @@ int cand_run(rf_ctx *ctx, const char *fn, std::vector<CandGroup> &gr, const doub
     const size_t bytes = cb + (size_t)(nch + ncd) * sizeof(CandRec);
     if (int e = upload(ctx, ctx->scratch[BUF_CAND_GROUPS], gr)) return e;
     if (int e = ensure_buf(ctx, ctx->scratch[BUF_CAND_OUT], bytes)) return e;
-    if (int e = ensure_hdn(ctx, bytes)) return e;
+    if (int e = ensure_landing(ctx, bytes)) return e;
     int32_t *d_cnt = dev<int32_t>(ctx, BUF_CAND_OUT);
     CandRec *d_ch = (CandRec *)(dev<char>(ctx, BUF_CAND_OUT) + cb), *d_cd = d_ch + nch;
     const CandGroup *d_gr = dev<const CandGroup>(ctx, BUF_CAND_GROUPS);
     const size_t lds = min_dist >= 1 ? (size_t)((max_m + 32) / 32) * 4 : 4;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_cand[0], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_CAND_SELECT_BEGIN], ctx->stream));
     hipLaunchKernelGGL(k_cand_select, dim3((unsigned)ng), dim3(256), 0, ctx->stream, d_gr, d_table, d_mask, d_cons,
                        d_cd, d_cnt, ctx->d_err);
-    HIPCHK(ctx, hipEventRecord(ctx->ev_cand[1], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_CAND_CHOOSE_BEGIN], ctx->stream));
     hipLaunchKernelGGL(k_cand_choose, dim3((unsigned)ng), dim3(256), lds, ctx->stream, d_gr, d_table, d_mask, d_cons,
                        (int)min_dist, (const int32_t *)d_cnt, d_ch, d_cnt + ng);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(ctx->ev_cand[2], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_CAND_CHOOSE_END], ctx->stream));
     HIPCHK(ctx, pre_d2h(ctx));
-    HIPCHK(ctx, hipMemcpyAsync((char *)ctx->hdn + HDN_RES, d_cnt, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, land_err(ctx));
-    HIPCHK(ctx, stream_wait(ctx));   // gr sources its upload until here
-    float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, ctx->ev_cand[0], ctx->ev_cand[1]);
-    (void)hipEventElapsedTime(&b, ctx->ev_cand[1], ctx->ev_cand[2]);
-    ctx->cand_select_ms = a;
-    ctx->cand_choose_ms = b;
-    if (int e = check_err_hdn(ctx))
+    HIPCHK(ctx, land(ctx, 0, d_cnt, bytes));
+    HIPCHK(ctx, land_wait(ctx));   // gr sources its upload until here
+    ctx->cand_select_ms = mark_ms(ctx, EV_CAND_SELECT_BEGIN, EV_CAND_CHOOSE_BEGIN);
+    ctx->cand_choose_ms = mark_ms(ctx, EV_CAND_CHOOSE_BEGIN, EV_CAND_CHOOSE_END);
+    if (int e = check_landed(ctx))
         return e;
-    const int32_t *cnt = (const int32_t *)((const char *)ctx->hdn + HDN_RES);
-    const CandRec *ch = (const CandRec *)((const char *)ctx->hdn + HDN_RES + cb), *cd = ch + nch;
+    const int32_t *cnt = landed<int32_t>(ctx);
+    const CandRec *ch = landed<CandRec>(ctx, cb), *cd = ch + nch;
     auto unpack = [](const CandRec *r, int64_t n, uint8_t *kind, int32_t *pos, uint8_t *base, double *sc) {
         for (int64_t i = 0; i < n; ++i) {
             kind[i] = r[i].kind;
@@ -9271,9 +9247,9 @@ extern "C" int rf_candidates_table(rf_ctx *ctx, int32_t ngroups, const int32_t *
         reads_mask = reads_mask || cand_source_reads_mask(source[g]);
         rows += (int64_t)m[g] + 1;
     }
-    if (int e = upload_raw(ctx, ctx->scratch[BUF_CAND_TABLE], table, (size_t)rows * 9 * 8)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_CAND_TABLE], table, (size_t)rows * 9 * 8)) return e;
     if (int e = upload(ctx, ctx->scratch[BUF_CAND_CONS], hc)) return e;   // hc: alive until cand_run's wait
-    if (int e = upload_raw(ctx, ctx->scratch[BUF_CAND_MASK], mask, reads_mask ? (size_t)rows * 9 : 0)) return e;
+    if (int e = upload(ctx, ctx->scratch[BUF_CAND_MASK], mask, reads_mask ? (size_t)rows * 9 : 0)) return e;
     return cand_run(ctx, "rf_candidates_table", gr, dev<const double>(ctx, BUF_CAND_TABLE),
                     dev<const uint8_t>(ctx, BUF_CAND_MASK), dev<const uint8_t>(ctx, BUF_CAND_CONS), min_dist, o);
 }

@@ -881,3 +881,57 @@ def test_arena_growth_under_live_bands(x_first):
         assert same(got[bm], oracle.forward(ty, ys[20])[0][bm]).all(), "a moved band of Y differs from the oracle"
     finally:
         e.close()
+
+
+# ---------------------------------------------------------------------
+# one pinned landing zone for every call family
+# ---------------------------------------------------------------------
+@pytest.mark.gpu
+def test_landing_zone_growth_across_call_families():
+    """rf_realign's scores, rf_alignment_proposals' masks and rf_backtrace's
+    counts and moves land in one pinned zone of 1 MB at first.  On a fresh
+    context: a small rf_realign (2 reads, n ~ m ~ 12, bw 3), then the masks
+    of 120 one-read groups at m = 1000 (9 (m + 1) 120 = 1,081,080 bytes: the
+    zone is freed and allocated again), the small rf_realign again, and
+    rf_backtrace of two of the long slots.  Every result is the oracle's, and
+    the two small calls return the same bits."""
+    from _util import make_read
+    rng = np.random.default_rng(6021)
+    G, M = 120, 1000
+    ts, tl = random_seq(12, rng), random_seq(M, rng)
+    small = [make_read(ts, rng, 0.03, 3) for _ in range(2)]
+    large = [make_read(tl, rng, 0.02, 9) for _ in range(G)]
+    assert 9 * (M + 1) * G + 16 > 1 << 20 >= 9 * (M + 1) * (G - 4) + 16, "the masks just outgrow the first zone"
+
+    def fill(t, r):
+        A, mv = oracle.forward(t, r, moves=True)
+        n, m, bw = len(r), len(t), r.bandwidth
+        wk = oracle.backtrace(mv, n + 1, m + 1, bw)
+        return A[n - m + max(m - n, 0) + bw, m], wk, oracle.count_errors(wk, t, r.seq)
+
+    exp_small = np.array([fill(ts, r)[0] for r in small])
+    exp_large = [fill(tl, r) for r in large]
+    sls, sll = np.arange(2, dtype=np.int32), np.arange(2, 2 + G, dtype=np.int32)
+    e = Engine(0)
+    try:
+        e.set_sequences(0, small + large)
+        e.set_templates(0, [ts, tl])
+        first = e.realign(sls, sls, 0, [3, 3], RF_FWD).copy()
+        assert same(first, exp_small).all()
+        got = e.realign(sll, sll, 1, [9] * G, RF_FWD)
+        assert same(got, [x[0] for x in exp_large]).all()
+        masks = e.alignment_proposals([sll[g:g + 1] for g in range(G)], True)
+        for g in range(G):
+            exp = np.zeros((M + 1, 9), np.uint8)
+            kd, p, b = moves_to_proposals_np(exp_large[g][1], tl, large[g].seq)
+            exp[p, dense_slot(kd, b)] = 1
+            np.testing.assert_array_equal(masks[g], exp, err_msg=f"mask of group {g}")
+        again = e.realign(sls, sls, 0, [3, 3], RF_FWD)
+        assert again.tobytes() == first.tobytes()
+        pick = [5, G - 1]
+        moves, nerr = e.backtrace(sll[pick])
+        for j, g in enumerate(pick):
+            np.testing.assert_array_equal(moves[j], exp_large[g][1], err_msg=f"moves of slot {sll[g]}")
+            assert nerr[j] == exp_large[g][2]
+    finally:
+        e.close()

@@ -672,6 +672,64 @@ def test_first_column_raise_among_good_jobs(engine, opts, tier):
         assert bits_equal(scores[k:k + 1], [final_cell(A, len(w.reads[s]), w.m, w.bw)])
 
 
+def test_flag_after_raise_across_call_families(engine, opts):
+    """rf_realign and every other call land the device's error flag in one
+    pinned zone.  A raising rf_realign (the smallest wall case, m = 40)
+    directly before each of rf_realign with a valid read, rf_backtrace,
+    rf_score and rf_candidates_table: each returns 0 and the oracle's result
+    (rf_candidates_table: its host restatement's).  Then the other way round:
+    a raise landed by a call of the other families, followed by a clean
+    rf_realign.  No test here has a walk that raises, so that raise is
+    rf_candidates_table's NaN in a proposal slot.  test_raise_and_state_after
+    already has a raising rf_realign followed by rf_backtrace or
+    rf_score_dense on a slot the call did not name."""
+    import test_candidates_host as CH
+    from rifraf_amd import _lib
+    from test_candidates import assert_same_results
+    tier = "dpx31"
+    w = wall_of(tier)
+    set_tier(opts, tier)
+    t, bw, m = w.t, w.bw, w.m
+    engine.release_bands()
+    engine.set_sequences(0, w.reads)
+    engine.set_templates(0, [t])
+    engine.realign([0, 1, 2, 3], [0, w.repl, 2, w.other], 0, [bw] * 4, RF_FWD | RF_BWD)
+
+    def raise_in_realign():   # slot 1 named alone: the other slots stay current
+        with pytest.raises(RifrafError, match=INVALID):
+            engine.realign([1], [w.wall], 0, [bw], RF_FWD)
+
+    o = w.reads[w.other]
+    Ao, mvo = oracle.forward(t, o, moves=True)
+    wk = oracle.backtrace(mvo, len(o) + 1, m + 1, bw)
+    props = all_proposals_arrays(t)
+    tot, per = oracle_scores(t, props, [o], [Ao], [oracle.backward(t, o)])
+    assert not np.isnan(tot).any()
+    grp = CH.flat_group(6, fill=1.0)
+    cand = ([grp[0]], [grp[1]], [0.0], [0], 1)
+    r = w.reads[w.repl]
+    exp_repl = final_cell(oracle.forward(t, r)[0], len(r), m, bw)
+
+    raise_in_realign()
+    assert bits_equal(engine.realign([1], [w.repl], 0, [bw], RF_FWD), [exp_repl])
+    raise_in_realign()
+    moves, nerr = engine.backtrace([3])
+    np.testing.assert_array_equal(moves[0], wk)
+    assert nerr[0] == oracle.count_errors(wk, t, o.seq)
+    raise_in_realign()
+    check_list_scores(engine, np.array([3], np.int32), -1, props, tot, per)
+    raise_in_realign()
+    got = engine.candidates_table(*cand, masks=[grp[2]], with_counts=True)
+    exp = _lib.host_candidates(*cand, masks=[grp[2]], with_counts=True)
+    assert_same_results(got, exp)
+    assert exp[0][3] > 0
+    # the other way round
+    _, bad, src, _ = next(c for c in CH.NANS if c[3])
+    with pytest.raises(RifrafError, match="failed to compute a valid score"):
+        engine.candidates_table([bad[0]], [bad[1]], [np.inf], [src], 2, masks=[bad[2]])
+    assert bits_equal(engine.realign([1], [w.repl], 0, [bw], RF_FWD), [exp_repl])
+
+
 # ---------------------------------------------------------------------
 # 6. native waves
 # ---------------------------------------------------------------------
