@@ -578,7 +578,9 @@ int rf_last_candidates_ms(const rf_ctx *ctx, double *select_ms, double *choose_m
  *   slot_base[c]: first of the cluster's batch slots; tpl_id[c]: its template
  *   cons / cons_off: the initial consensus per cluster (already uploaded)
  * Outputs per cluster: final score, INIT iterations, status (0 = reached
- * max_iters, 1 = converged, 2 = failed: rf_batch_fetch has the message),
+ * max_iters, 1 = converged, 2 = failed: rf_batch_fetch has the message; a
+ * cluster whose accepted candidates remove every base of its consensus fails
+ * with "empty consensus: ..." before a zero-length template is uploaded),
  * consensus length; out_bw per read = final bandwidth, negated once
  * bandwidth_fixed.  Results stay in the context until rf_batch_release. */
 typedef struct rf_batch_params {

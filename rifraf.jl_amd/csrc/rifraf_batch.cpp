@@ -905,6 +905,10 @@ struct Driver {
                 fail_cluster(c, "AmbiguousProposalsError");
                 continue;
             }
+            if (nc.empty()) {   // model.py's _set_consensus: no zero-length template is ever uploaded
+                fail_cluster(c, EMPTY_CONSENSUS);
+                continue;
+            }
             C.cons.swap(nc);
             up.push_back(c);
         }
@@ -928,6 +932,10 @@ struct Driver {
                 C.chosen.resize(1);
                 std::vector<uint8_t> nc;
                 apply(C.old_cons, C.chosen, nc);
+                if (nc.empty()) {
+                    fail_cluster(c, EMPTY_CONSENSUS);
+                    continue;
+                }
                 C.cons.swap(nc);
                 redo.push_back(c);
             } else {
@@ -938,6 +946,9 @@ struct Driver {
         set_consensus(redo);
     }
     static constexpr double DBL_EPSILON_ = std::numeric_limits<double>::epsilon();
+    // the text of model.py's EMPTY_CONSENSUS: one outcome on every path for an
+    // accepted candidate set that removes every base
+    static constexpr const char *EMPTY_CONSENSUS = "empty consensus: the accepted candidates removed every base";
 
     // ---------------- finish_stage! (model.jl:937-995)
     void finish_stage(std::vector<int> cs)

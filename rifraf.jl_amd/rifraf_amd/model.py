@@ -462,7 +462,16 @@ def get_candidates(state: RifrafState, run: _Run, params: RifrafParams, indel_se
 # stage machine (model.jl:898-1114)
 # ---------------------------------------------------------------------
 
+# The engine's ABI refuses zero-length templates, so a candidate set that
+# removes every base ends the run here, on every engine and in the native
+# driver (rifraf_batch.cpp) with the same text (departures)
+EMPTY_CONSENSUS = "empty consensus: the accepted candidates removed every base"
+
+
 def _set_consensus(state, run, cons):
+    """The consensus after a candidate set is applied (handle_candidates)."""
+    if len(cons) == 0:
+        raise RifrafError(EMPTY_CONSENSUS)
     state.consensus = DNASeq(cons)
     run.set_consensus(state.consensus)
 

@@ -48,6 +48,7 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(m, n, bw) for m in range(1, 13) for n in range(1, 13) for bw in (1, 2, 3, 5)]
 NA = len(SHAPES)                      # 576 alignments per class
 PER_M = NA // 12                      # the 48 alignments of one m are consecutive
+BLOCK_TPL = np.repeat(np.arange(12) * PER_M, PER_M)   # per alignment: the first template of its m
 SEEDS = {"seq": 1201, "ref": 1202, "seq0": 1203, "ref0": 1204, "tie_seq": 1205, "tie_ref": 1206}
 CODON = ("ref", "ref0", "tie_ref")
 NONCODON = ("seq", "seq0", "tie_seq")
@@ -163,6 +164,17 @@ class _Class:
         return self.memo("dense_m", lambda: [
             oracle.cpu_pass(self.templates[g * PER_M], self.seqs[g * PER_M:(g + 1) * PER_M], nthreads=1)[0]
             for g in range(12)])
+
+    def block_walks(self):
+        """The backtrace of each alignment's read against its m's first
+        template (BLOCK_TPL: the consensus the reads of one m share)."""
+        def run():
+            out = []
+            for k, ((m, n, bw), s) in enumerate(zip(SHAPES, self.seqs)):
+                t = self.templates[BLOCK_TPL[k]]
+                out.append(oracle.backtrace(oracle.forward(t, s, moves=True)[1], n + 1, m + 1, bw))
+            return out
+        return self.memo("block_walks", run)
 
     def ref_scores(self):
         """score_proposal of every STAGE_SCORE proposal with the class's
@@ -625,6 +637,18 @@ def test_qv_probs_extended_precision(engine):
     for rs in reads:
         groups.append(np.arange(at, at + len(rs)))
         at += len(rs)
+    worst, worst_abs = check_qv_probs(engine, groups, templates, reads, sc)
+    assert math.isfinite(worst)
+    print(f"k_qv: largest relative error against the 80-bit evaluation {worst:.3e} "
+          f"(values above {QV_ATOL / QV_RTOL:g}); largest absolute error below that {worst_abs:.3e}")
+
+
+def check_qv_probs(engine, groups, templates, reads, sc):
+    """rf_qv_probs of `groups` (slot lists in batch order; templates[g] and
+    reads[g] are group g's consensus and RifrafSequences, sc the A[end, end]
+    of every slot) against the 80-bit evaluation of its own inputs.  Returns
+    the largest relative and absolute errors seen."""
+    tlens = [len(t) for t in templates]
     state = []
     for g in groups:
         tot = 0.0
@@ -669,6 +693,64 @@ def test_qv_probs_extended_precision(engine):
         # rf_qv_probs does not return the state term 10^(score - max) / denominator, so it is
         # the 80-bit one: this bounds the sum of the engine's ins row, not an engine-only identity
         assert np.abs(g_ins.astype(ld).sum(axis=1) + e_state - 1).max() <= 1e-12, f"group {g}: ins rows"
+    return worst, worst_abs
+
+
+def ragged_groups():
+    """144 groups of 1-6 slots in a drawn (batch) order: for each m, the sizes
+    1..6 twice over, drawn without replacement from the 48 alignments of that
+    m, every n and bw among them.  The members of a group share the first
+    template of their m (BLOCK_TPL)."""
+    rng = np.random.default_rng(1400)
+    groups = []
+    for g in range(12):
+        order = g * PER_M + rng.permutation(PER_M)
+        at = 0
+        for size in (1, 2, 3, 4, 5, 6) * 2:
+            groups.append(order[at:at + size].astype(np.int32))
+            at += size
+    return groups
+
+
+@pytest.mark.parametrize("marks_min", [128, 0])
+@pytest.mark.parametrize("name", LEAN)
+def test_sweep_aln_error_sums(engine, opts, name, marks_min):
+    """rf_aln_error_sums' device fold over ragged groups of 1-6 reads at
+    consensus lengths 1..12 against alignment_error_probs's sums
+    (model.jl:817-840) folded on the host over the oracle's walks
+    (model._add_base_distributions), bit for bit: k_aln_sums (aln_marks_min
+    at its default) and the k_aln_marks + k_aln_fold pair (aln_marks_min 0).
+    The host tables are withheld (bptr / mptr None), so a fall-back to the
+    library's host fold would return None."""
+    from rifraf_amd.model import _add_base_distributions
+    c = cls_of(name)
+    opts("aln_marks_min", marks_min)
+    upload(engine, c, RF_FWD | RF_BWD, tpl=BLOCK_TPL)
+    groups = ragged_groups()
+    walks = c.block_walks()
+    tlens = [SHAPES[g[0]][0] for g in groups]
+    got = engine.aln_error_sums_ptr(groups, tlens, None, None, [len(c.seqs[k]) for g in groups for k in g])
+    assert got is not None, "a read has no row codes: the device fold did not run"
+    assert len(got) == len(groups)
+    for g, m, sums in zip(groups, tlens, got):
+        exp = np.zeros((m, 4))
+        _add_base_distributions(exp, [walks[k] for k in g], [c.seqs[k] for k in g])
+        assert sums.shape == (m, 4)
+        assert same(sums, exp).all(), (name, "aln sums", [SHAPES[k] for k in g])
+
+
+@pytest.mark.parametrize("name", LEAN)
+def test_sweep_qv_probs(engine, name):
+    """k_qv over the same ragged groups (consensus lengths 1..12, 1-6 reads)
+    against the 80-bit evaluation of test_qv_probs_extended_precision, at its
+    bound (QV_RTOL / QV_ATOL, rows summing to 1 within 1e-12)."""
+    if np.finfo(np.longdouble).nmant < 63:
+        pytest.skip("np.longdouble has fewer than 64 significand bits on this host")
+    c = cls_of(name)
+    sc = upload(engine, c, RF_FWD | RF_BWD, tpl=BLOCK_TPL)
+    groups = ragged_groups()
+    worst, worst_abs = check_qv_probs(engine, groups, [c.templates[BLOCK_TPL[g[0]]] for g in groups],
+                                      [[c.seqs[k] for k in g] for g in groups], sc)
     assert math.isfinite(worst)
-    print(f"k_qv: largest relative error against the 80-bit evaluation {worst:.3e} "
-          f"(values above {QV_ATOL / QV_RTOL:g}); largest absolute error below that {worst_abs:.3e}")
+    print(f"k_qv, {name}: largest relative error against the 80-bit evaluation {worst:.3e}; "
+          f"largest absolute error below {QV_ATOL / QV_RTOL:g}: {worst_abs:.3e}")
