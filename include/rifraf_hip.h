@@ -21,6 +21,9 @@
  *   rf_pair_align_text <- align / moves_to_aligned_seqs, moves_to_indices and
  *                        band_tolerance over many pairs
  *                        src/align.jl:262-311,322-335,346-353
+ *   rf_pair_errors    <- count_errors and smart_forward_moves!' band doubling
+ *                        over many pairs, without moves
+ *                        src/align.jl:240-250, src/model.jl:643-672
  *   rf_backtrace      <- backtrace + count_errors   src/align.jl:229-245
  *   rf_alignment_proposals <- alignment_proposals / moves_to_proposals
  *                        src/model.jl:458-497
@@ -414,6 +417,38 @@ int rf_pair_align_text(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const in
 /* Summed k_pa_emit time of the last rf_pair_align_text call, milliseconds
  * (0 if it launched none); rf_last_pair_align_ms reports its fills and walks. */
 int rf_last_pair_text_ms(const rf_ctx *ctx, double *emit_ms);
+
+/* Scores, error counts and the band doubling of smart_forward_moves!
+ * (model.jl:643-672) of many pairs with nothing per cell leaving the chip.
+ * count_errors (align.jl:240-250) is the number of alignment columns whose two
+ * characters differ: along the path a match adds s[i] != t[j], an insertion or
+ * a deletion 1, a codon move 3.  The path into a cell is the path into the
+ * predecessor its move names, so the count rides through the fill beside the
+ * score (k_pe / k_pe_gen) and comes out of the last cell with A[end, end]: no
+ * move trace, no walk.  out_score, nerrors, out_bw and out_rounds equal what
+ * rf_pair_align_smart returns with moves = moves_off = nmoves = NULL for the
+ * same arguments: the scores bit for bit, the integers equal.  A pair the
+ * reference raises on gets score NaN, nerrors = -1 and out_bw the bandwidth
+ * that raised; the call still returns 0.  With max_doublings == 0 the call is
+ * rf_pair_align's score and nerrors at bw and threshold may be NULL
+ * (rf_pair_align_text's rule).  Checks, messages, flags (RF_FWD implied,
+ * RF_BWD is RF_ERR_ARG), the 5,114-row limit at max_bw and the return value
+ * are rf_pair_align_smart's.  Every output pointer may be NULL.  The call
+ * touches no slot, no band and not the band arena.  Its device memory is
+ * bounded by RF_OPT_PAIR_CHUNK: the descriptors plus 12 B per pair (score and
+ * count), whatever npairs, the rounds or the cell counts are.  The exception
+ * are pairs whose band is wider than 3,407 rows (two LDS rings, 48 (H + 6) B,
+ * no longer fit 160 KiB): they run inside the same call through
+ * rf_pair_align's trace fill and walk, with the same numbers, and add its
+ * RF_OPT_PAIR_TRACE_MB budget. */
+int rf_pair_errors(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl,
+                   const int32_t *bw, const double *threshold, const uint8_t *fixed,
+                   int32_t max_doublings, int32_t flags, double *out_score, int32_t *nerrors,
+                   int32_t *out_bw, int32_t *out_rounds);
+/* Summed kernel time of the last rf_pair_errors call (all its sets and
+ * rounds; the trace fills and walks of its widest pairs included),
+ * milliseconds.  Leaves rf_last_pair_align_ms' values as they were. */
+int rf_last_pair_errors_ms(const rf_ctx *ctx, double *fill_ms);
 
 /* Backtrace of the A band of each slot (align.jl:229-238), moves in
  * alignment order written at moves[moves_off[k] ...] (capacity n+m each);

@@ -60,6 +60,7 @@ constexpr int RF_TASK_CODED = 1024;
 constexpr int DP_LDS_H = 5114;     // widest band whose four-diagonal ring fits the LDS of k_dp<DPW_NT>
 constexpr int DP_FAST_H = 255;     // widest band of the register kernels (k_dpr<8>, the 64-lane tasks, k_ps<2, 64>)
 constexpr int DP_GEN64_H = 2040;   // widest band of a one-wave LDS ring (k_dp<64>, k_ps_gen<64>: ring < 64 KB)
+constexpr int DP_COUNT_H = 3407;   // widest band whose score ring and int32 count ring fit 160 KiB (k_pe_gen): 48 (H + 6) B
 
 RF_HD constexpr int dpl_pmax(int np, int lpt = 16) { return (lpt * np) | 1; }   // band_P(2*LPT*NP-1)
 // stride classes of the lean DP launches: k_dpr<1 << npi, true, dpr_pm(npi, pmi)>
@@ -355,10 +356,11 @@ RF_HD inline int pa_blocks(int klen) { return (((klen + 1) >> 1) + 15) >> 4; }
 // What one launch set of a pair call produces besides its scores
 struct PairWants {
     bool trace;    // the fills write the move trace (rf_pair_scores: none, and nothing below)
-    bool walk;     // the walk runs: nmoves and nerrors
+    bool walk;     // the walk runs: nmoves and nerrors (with `count`: nerrors goes to the caller)
     bool get_mv;   // the moves go to the caller
     bool emit;     // k_pa_emit runs: aln_len, t2s_len and tolerance, and with
     bool want_txt, want_ix;   // ... these the two texts / the index maps
+    bool count = false;   // rf_pair_errors: the fills carry nerrors (k_pe*); no trace, no walk, nothing else above
     bool want_mv() const { return get_mv || emit; }   // the walk writes the moves
 };
 
@@ -431,7 +433,7 @@ void pair_set_fill(PairSet &s, int64_t cn, bool trace, F task)
 // Scores, then nmoves and nerrors, then the moves; with k_pa_emit its
 // lengths, the two texts (t, then s, mv_total bytes each) and the index maps.
 struct PairLanding {
-    size_t scores, counts;   // bytes: cn doubles at 0; 2 cn int32 behind them
+    size_t scores, counts;   // bytes: cn doubles at 0; 2 cn int32 behind them (cn with PairWants::count: nerrors alone)
     size_t mv_at, len_at, txt_at, ix_at;
     size_t lens;             // bytes: 3 cn int32 (aln_len, t2s_len, tolerance)
     size_t total;            // bytes of the zone
@@ -444,6 +446,10 @@ inline PairLanding pair_landing(int64_t cn, int64_t mv_total, int64_t ix_total, 
     PairLanding L{};
     L.scores = sizeof(double) * (size_t)cn;
     L.total = L.scores;
+    if (w.count) {
+        L.counts = sizeof(int32_t) * (size_t)cn;
+        L.total = L.scores + L.counts;
+    }
     if (!w.trace)
         return L;
     L.counts = sizeof(int32_t) * 2 * (size_t)cn;

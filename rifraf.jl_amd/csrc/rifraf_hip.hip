@@ -17,6 +17,9 @@
 //   k_pa / k_pa_gen / k_pa_walk / k_pa_walk_w  alignments of independent pairs
 //               (rf_pair_align): k_ps / k_ps_gen writing a 4-bit move per
 //               cell, and a walk over the moves  src/align.jl:114-153,229-245
+//   k_pe / k_pe_gen  k_ps / k_ps_gen carrying count_errors of the path into
+//               each cell beside its score (rf_pair_errors): no trace, no walk
+//               src/align.jl:240-250, src/model.jl:643-672
 //   k_pa_emit   gapped texts, index maps and band tolerances from those moves
 //               (rf_pair_align_text)  src/align.jl:262-311,322-335
 //   k_score_ws / k_score_segl / k_score
@@ -1210,7 +1213,8 @@ k_dpr(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ 
 // (kappa-3 with codon moves) stay live.  Same candidates and FP64 sums as
 // k_dpr / k_dp, so the value is the one rf_realign(RF_FWD) writes to
 // out_score, bit for bit.  Each tier is one body (ps_body, ps_gen_body) that
-// both entry points run: k_ps* with TRACE = false, k_pa* with TRACE = true.
+// every entry point runs: k_ps* in mode PS_SCORE, k_pa* in PS_TRACE, k_pe* in
+// PS_COUNT (MODE below; TRACE and COUNT name the two that add something).
 //
 // ps_body<NP, LPT, TRACE> (fast tier): the lean condition of k_dpr -- no
 // codon tables, finite tables, no skew / trim -- and H <= 2*LPT*NP - 1 <=
@@ -1252,6 +1256,21 @@ k_dpr(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ 
 // after every 16th period.  In the general tier the loop over a thread's
 // diagonal pairs is unrolled, so their open words stay in registers.
 //
+// What COUNT adds (k_pe*, rf_pair_errors): count_errors (align.jl:240-245) of
+// the path into each cell, an int32 beside its score.  The path into a cell
+// is the path into the predecessor its move names, so
+//   count[cell] = count[predecessor] + cost(move),
+// cost = s[i] != t[j] for a match, 1 for an insertion or a deletion, 3 for a
+// codon move (what k_pa_walk adds per step), and the final cell's count
+// comes out with A[end, end]: no trace, no walk.  The move is chosen as
+// TRACE chooses it and the score expressions are unchanged, so out[] holds
+// the same bits.  Fast tier: count registers e1 / e2 beside v1 / v2, moved
+// by the same DPP shifts; a masked or out-of-matrix diagonal carries some
+// count that nothing selects (its score is -Inf).  General tier: an int32
+// ring of the same four anti-diagonals behind the score ring, 48 (H + 6) B
+// in all, which fits the LDS up to PE_LDS_H (the host sends wider bands
+// through k_pa_gen and the walk); a pair with an invalid cell gets -1.
+//
 // k_pa_walk (backtrace + count_errors, align.jl:229-245): one lane per pair,
 // from (n, m) to (0, 0), reading trace nibbles in place (a word serves up to
 // 16 consecutive matches: they stay on one diagonal) and the two base strings
@@ -1269,19 +1288,35 @@ constexpr int PA_TRACE_MB = 1024;  // RF_OPT_PAIR_TRACE_MB's default
 // diagonal pairs per thread of the general tier: 2 NT NPP >= pa_hp(widest band of the tier)
 constexpr int PA_NPP64 = (PS_GEN64_H + 1 + 127) / 128;
 constexpr int PA_NPPW = (DPW_LDS_H + 1 + 2 * DPW_NT - 1) / (2 * DPW_NT);
+// The fill modes of ps_body / ps_gen_body: the score alone (k_ps*), with the
+// move trace (k_pa*), with the error count carried per cell (k_pe*)
+constexpr int PS_SCORE = 0, PS_TRACE = 1, PS_COUNT = 2;
+// widest band whose score ring (4 x 8 B) and count ring (4 x 4 B) of H + 6 entries fit the 160 KiB of LDS
+constexpr int PE_LDS_H = 160 * 1024 / 48 - 6;
+static_assert(PE_LDS_H == DP_COUNT_H && 48 * (PE_LDS_H + 6) <= 160 * 1024 && 48 * (PE_LDS_H + 7) > 160 * 1024,
+              "rifraf_dp_plan.h's DP_COUNT_H");
+constexpr int PE_NPPW = (PE_LDS_H + 1 + 2 * DPW_NT - 1) / (2 * DPW_NT);
+#ifndef PS_COUNT_GRP
+#define PS_COUNT_GRP PS_B   // periods unrolled per pass of the lean interior with the count
+#endif
 
 // dpr_step without codon moves, skew / trim and stores (borders of the
 // matrix).  TRACE: the cell's move (strict '>' in reference order) goes into
 // nibble (k >> 1) & 15 of w
-template <int NP, int PAR, int LPT, bool TRACE>
+template <int NP, int PAR, int LPT, int MODE>
 __device__ __forceinline__ void ps_step(const DPTask &T, int q, int k, double (&v1)[NP], double (&v2)[NP],
                                         const RowRec (&row)[NP], const int (&col)[NP], double &fval, int &fset,
-                                        uint64_t (&w)[NP])
+                                        uint64_t (&w)[NP], int (&e1)[NP], int (&e2)[NP], int &fcnt)
 {
+    constexpr bool TRACE = MODE == PS_TRACE, COUNT = MODE == PS_COUNT;
     const double E1 = PAR == 0 ? dpp_f64<TaskLanes<LPT>::FROM_L1>(v1[NP - 1])
                                : dpp_f64<TaskLanes<LPT>::FROM_R1>(v1[0]);
+    int C1 = 0;   // COUNT: the count that moves with E1
+    if constexpr (COUNT)
+        C1 = PAR == 0 ? dpp_i32<TaskLanes<LPT>::FROM_L1>(e1[NP - 1], 0) : dpp_i32<TaskLanes<LPT>::FROM_R1>(e1[0], 0);
     const bool live = k < T.klen;
     double nv[NP];
+    int ne[NP];
 #pragma unroll
     for (int r = 0; r < NP; ++r) {
         const int d = 2 * (q * NP + r) + PAR;
@@ -1306,6 +1341,19 @@ __device__ __forceinline__ void ps_step(const DPTask &T, int q, int k, double (&
             w[r] |= (uint64_t)mv << (4 * ((k >> 1) & 15));
         }
         const bool fin = valid && ii == T.n && jj == T.m;
+        if constexpr (COUNT) {
+            // the count of the chosen predecessor plus the move's cost, chosen as TRACE chooses the move
+            const int c_ins = PAR ? e1[r] : (r > 0 ? e1[r > 0 ? r - 1 : 0] : C1);
+            const int c_del = PAR ? (r < NP - 1 ? e1[r < NP - 1 ? r + 1 : 0] : C1) : e1[r];
+            int c = 0;
+            double b = -RF_INF;
+            if (cm > b) { b = cm; c = e2[r] + (R.sb == col[r] ? 0 : 1); }
+            if (ci > b) { b = ci; c = c_ins + 1; }
+            if (cd > b) { c = c_del + 1; }
+            c = (valid && !org) ? c : 0;
+            fcnt = fin ? c : fcnt;
+            ne[r] = c;
+        }
         fval = fin ? v : fval;
         fset |= fin ? 1 : 0;
         nv[r] = v;
@@ -1314,20 +1362,32 @@ __device__ __forceinline__ void ps_step(const DPTask &T, int q, int k, double (&
     for (int r = 0; r < NP; ++r) {
         v2[r] = v1[r];
         v1[r] = nv[r];
+        if constexpr (COUNT) {
+            e2[r] = e1[r];
+            e1[r] = ne[r];
+        }
     }
 }
 
 // dpl_step without its LDS stores (the lean interior).  TRACE: the move goes
 // into nibble p (a constant once unrolled) of a 4-period accumulator: two
-// compares and selects on the candidates; a masked diagonal (-Inf) carries 0
-template <int NP, int PAR, int LPT, bool TRACE>
+// compares and selects on the candidates; a masked diagonal (-Inf) carries 0.
+// COUNT: the same two compares select the predecessor's count plus the move's
+// cost; a masked diagonal carries some count, which no cell selects (its score is -Inf)
+template <int NP, int PAR, int LPT, int MODE>
 __device__ __forceinline__ void ps_lean_step(double (&v1)[NP], double (&v2)[NP], const RowRec (&row)[NP],
                                              const int (&col)[NP], const double (&lb)[NP], uint32_t (&w)[NP],
-                                             const int p)
+                                             const int p, int (&e1)[NP], int (&e2)[NP])
 {
+    constexpr bool TRACE = MODE == PS_TRACE, COUNT = MODE == PS_COUNT;
     const double E1 = PAR == 0 ? dpp_rot_f64<TaskLanes<LPT>::ROT_L1>(v1[NP - 1])
                                : dpp_rot_f64<TaskLanes<LPT>::ROT_R1>(v1[0]);
+    int C1 = 0;
+    if constexpr (COUNT)
+        C1 = PAR == 0 ? __builtin_amdgcn_mov_dpp(e1[NP - 1], TaskLanes<LPT>::ROT_L1, 0xF, 0xF, false)
+                      : __builtin_amdgcn_mov_dpp(e1[0], TaskLanes<LPT>::ROT_R1, 0xF, 0xF, false);
     double nv[NP];
+    int ne[NP];
 #pragma unroll
     for (int r = 0; r < NP; ++r) {
         const RowRec &R = row[r];
@@ -1343,20 +1403,31 @@ __device__ __forceinline__ void ps_lean_step(double (&v1)[NP], double (&v2)[NP],
             mv = nv[r] == -RF_INF ? 0 : mv;
             w[r] |= (uint32_t)mv << (4 * p);
         }
+        if constexpr (COUNT) {
+            const int c_ins = PAR ? e1[r] : (r > 0 ? e1[r > 0 ? r - 1 : 0] : C1);
+            const int c_del = PAR ? (r < NP - 1 ? e1[r < NP - 1 ? r + 1 : 0] : C1) : e1[r];
+            int c = ci > cm ? c_ins + 1 : e2[r] + (R.sb == col[r] ? 0 : 1);
+            ne[r] = cd > t ? c_del + 1 : c;
+        }
     }
 #pragma unroll
     for (int r = 0; r < NP; ++r) {
         v2[r] = v1[r];
         v1[r] = nv[r];
+        if constexpr (COUNT) {
+            e2[r] = e1[r];
+            e1[r] = ne[r];
+        }
     }
 }
 
-template <int NP, int LPT, bool TRACE>
+template <int NP, int LPT, int MODE>
 __device__ __forceinline__ void ps_body(const DPTask *__restrict__ tasks, int ntasks,
                                         const uint8_t *__restrict__ bases, const double *__restrict__ tabs,
                                         double *__restrict__ out, const double *__restrict__ lut,
-                                        uint64_t *__restrict__ trace)
+                                        uint64_t *__restrict__ trace, int32_t *__restrict__ cnt)
 {
+    constexpr bool TRACE = MODE == PS_TRACE, COUNT = MODE == PS_COUNT;
     // 16 lanes per task, or the whole wave (wave_shr / wave_shl moves: no edge fix, TaskLanes)
     static_assert(LPT == 16 || LPT == 64, "fast-tier tasks are 16 or 64 lanes");
     __shared__ EdgeRec s_edge[64 / LPT][PS_B];
@@ -1378,10 +1449,12 @@ __device__ __forceinline__ void ps_body(const DPTask *__restrict__ tasks, int nt
     RowRec row[NP];
     int col[NP];
     uint64_t w[2][NP];   // TRACE: the open trace words of diagonals 2 (q NP + r) + par
+    int e1[NP], e2[NP];  // COUNT: the error counts of the paths into v1's and v2's cells
 #pragma unroll
     for (int r = 0; r < NP; ++r) {
         v1[r] = -RF_INF;
         v2[r] = -RF_INF;
+        e1[r] = e2[r] = 0;
         if constexpr (TRACE)
             w[0][r] = w[1][r] = 0;
         const int pp = q * NP + r;
@@ -1393,6 +1466,7 @@ __device__ __forceinline__ void ps_body(const DPTask *__restrict__ tasks, int nt
     int cq = load_col(T, false, tbase, 1);                             // enters at kappa = 2
     double fval = 0.0;   // the final cell's score (the lane that computes it)
     int fset = 0;
+    int fcnt = 0;        // COUNT: and its path's error count
     // TRACE: block b of the task's trace, diagonals 2 (q NP + r), + 1 as one 16-B store
     auto flush = [&](int b) {
         uint64_t *trp = trace + T.band;
@@ -1489,7 +1563,8 @@ __device__ __forceinline__ void ps_body(const DPTask *__restrict__ tasks, int nt
             // Periods unrolled per pass of the block: all 16 without the trace.  With it 4 (at
             // 16 the scheduler hoists every period's row / column moves and match selects and
             // runs out of registers); their moves gather in 16 bits and join the trace word once.
-            constexpr int GRP = TRACE ? 4 : PS_B;
+            // COUNT keeps all 16 (registers: DESIGN.md §4 "Error counts carried through the fill").
+            constexpr int GRP = TRACE ? 4 : (COUNT ? PS_COUNT_GRP : PS_B);
             for (int b = 0; b < nblk; ++b) {
                 EdgeRec E = ein[0];
 #pragma unroll 1
@@ -1511,7 +1586,7 @@ __device__ __forceinline__ void ps_body(const DPTask *__restrict__ tasks, int nt
                                 col[r] = col[r - 1];
                             col[0] = from;
                         }
-                        ps_lean_step<NP, 0, LPT, TRACE>(v1, v2, row, col, lb[0], acc[0], j);
+                        ps_lean_step<NP, 0, LPT, MODE>(v1, v2, row, col, lb[0], acc[0], j, e1, e2);
                         {   // odd step: rows advance; lane 15 receives the edge row
                             RowRec e;
                             e.sb = E.sb;
@@ -1526,7 +1601,7 @@ __device__ __forceinline__ void ps_body(const DPTask *__restrict__ tasks, int nt
                                 row[r] = row[r + 1];
                             row[NP - 1] = up;
                         }
-                        ps_lean_step<NP, 1, LPT, TRACE>(v1, v2, row, col, lb[1], acc[1], j);
+                        ps_lean_step<NP, 1, LPT, MODE>(v1, v2, row, col, lb[1], acc[1], j, e1, e2);
                         E = En;
                     }
                     if constexpr (TRACE) {
@@ -1565,7 +1640,7 @@ __device__ __forceinline__ void ps_body(const DPTask *__restrict__ tasks, int nt
         }
         if constexpr (TRACE)
             open_blk = k >> 5;
-        ps_step<NP, 0, LPT, TRACE>(T, q, k, v1, v2, row, col, fval, fset, w[0]);
+        ps_step<NP, 0, LPT, MODE>(T, q, k, v1, v2, row, col, fval, fset, w[0], e1, e2, fcnt);
         if (k + 1 < kmax) {
             // odd step: rows advance; lane 15 receives the prefetched row
             const RowRec up = row_from_above<LPT>(row[0], nq, false);
@@ -1574,7 +1649,7 @@ __device__ __forceinline__ void ps_body(const DPTask *__restrict__ tasks, int nt
                 row[r] = row[r + 1];
             row[NP - 1] = up;
             nq = load_row(T, false, sbase, tb, top + (k + 2) / 2 + 1 - T.c, false);
-            ps_step<NP, 1, LPT, TRACE>(T, q, k + 1, v1, v2, row, col, fval, fset, w[1]);
+            ps_step<NP, 1, LPT, MODE>(T, q, k + 1, v1, v2, row, col, fval, fset, w[1], e1, e2, fcnt);
         }
         if constexpr (TRACE)
             if ((k & 31) == 30) {
@@ -1585,8 +1660,11 @@ __device__ __forceinline__ void ps_body(const DPTask *__restrict__ tasks, int nt
     if constexpr (TRACE)
         if (open_blk >= 0)
             flush(open_blk);
-    if (fset)
+    if (fset) {
         out[T.out_idx] = fval;
+        if constexpr (COUNT)
+            cnt[T.out_idx] = fcnt;
+    }
 }
 
 template <int NP, int LPT = 16>
@@ -1594,7 +1672,7 @@ __global__ void __launch_bounds__(64)
 k_ps(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
      const double *__restrict__ tabs, double *__restrict__ out, const double *__restrict__ lut)
 {
-    ps_body<NP, LPT, false>(tasks, ntasks, bases, tabs, out, lut, nullptr);
+    ps_body<NP, LPT, PS_SCORE>(tasks, ntasks, bases, tabs, out, lut, nullptr, nullptr);
 }
 
 template <int NP, int LPT = 16>
@@ -1603,20 +1681,34 @@ k_pa(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ b
      const double *__restrict__ tabs, double *__restrict__ out, const double *__restrict__ lut,
      uint64_t *__restrict__ trace)
 {
-    ps_body<NP, LPT, true>(tasks, ntasks, bases, tabs, out, lut, trace);
+    ps_body<NP, LPT, PS_TRACE>(tasks, ntasks, bases, tabs, out, lut, trace, nullptr);
 }
 
-template <int NT, int NPP, bool TRACE>
+template <int NP, int LPT = 16>
+__global__ void __launch_bounds__(64)
+k_pe(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+     const double *__restrict__ tabs, double *__restrict__ out, const double *__restrict__ lut,
+     int32_t *__restrict__ cnt)
+{
+    ps_body<NP, LPT, PS_COUNT>(tasks, ntasks, bases, tabs, out, lut, nullptr, cnt);
+}
+
+template <int NT, int NPP, int MODE>
 __device__ __forceinline__ void ps_gen_body(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
                                             const double *__restrict__ tabs, double *__restrict__ out,
-                                            uint64_t *__restrict__ trace, int ring_ld)
+                                            uint64_t *__restrict__ trace, int32_t *__restrict__ cnt, int ring_ld)
 {
+    constexpr bool TRACE = MODE == PS_TRACE, COUNT = MODE == PS_COUNT;
     extern __shared__ __attribute__((aligned(16))) double ps_ring[];
     const int q = threadIdx.x;
     const DPTask T = tasks[blockIdx.x];
     double *ring = ps_ring;
-    for (int e = q; e < 4 * ring_ld; e += NT)
+    int *cring = (int *)(ps_ring + 4 * ring_ld);   // COUNT: the counts of the same four anti-diagonals
+    for (int e = q; e < 4 * ring_ld; e += NT) {
         ring[e] = -RF_INF;
+        if constexpr (COUNT)
+            cring[e] = 0;
+    }
     auto sync = [] {
         if (NT > 64)
             lds_barrier();
@@ -1638,6 +1730,7 @@ __device__ __forceinline__ void ps_gen_body(const DPTask *__restrict__ tasks, co
     bool bad = false;    // "new score is invalid" in a cell of this lane
     double fval = 0.0;   // the final cell (the lane that computes it)
     bool fset = false;
+    int fcnt = 0;        // COUNT: the error count of the final cell's path
     uint64_t w0[NPP], w1[NPP];   // TRACE: open trace words of diagonals 2 (q + u NT), + 1
     if constexpr (TRACE) {
 #pragma unroll
@@ -1654,6 +1747,10 @@ __device__ __forceinline__ void ps_gen_body(const DPTask *__restrict__ tasks, co
         const double *r1 = ring + ((k - 1) & 3) * ring_ld + 3;
         const double *r2 = ring + ((k - 2) & 3) * ring_ld + 3;
         const double *r3 = ring + ((k - 3) & 3) * ring_ld + 3;
+        int *c0 = cring + (k & 3) * ring_ld + 3;
+        const int *c1 = cring + ((k - 1) & 3) * ring_ld + 3;
+        const int *c2 = cring + ((k - 2) & 3) * ring_ld + 3;
+        const int *c3 = cring + ((k - 3) & 3) * ring_ld + 3;
 #pragma unroll UNROLL
         for (int u = 0; u < NPP; ++u) {
             const int d = 2 * (q + u * NT) + par;
@@ -1668,6 +1765,7 @@ __device__ __forceinline__ void ps_gen_body(const DPTask *__restrict__ tasks, co
             const int jj = (k - d) >> 1;
             double v = -RF_INF;
             int mv = 0;   // dead without TRACE
+            int ce = 0;   // COUNT: the count of the chosen predecessor plus the move's cost
             if (jj <= T.m) {
                 const int ii = d + jj - T.c;
                 if (ii >= 0 && ii <= T.n) {
@@ -1703,14 +1801,28 @@ __device__ __forceinline__ void ps_gen_body(const DPTask *__restrict__ tasks, co
                         }
                         bad = bad || best == -RF_INF;   // "new score is invalid"
                         v = best;
+                        if constexpr (COUNT) {
+                            // count_errors (align.jl:240-245) of the path into the cell, as k_pa_walk counts it
+                            switch (mv) {
+                            case 1: ce = c2[d] + (sb != tbb ? 1 : 0); break;
+                            case 2: ce = c1[d - 1] + 1; break;
+                            case 3: ce = c1[d + 1] + 1; break;
+                            case 4: ce = c3[d - 3] + 3; break;
+                            case 5: ce = c3[d + 3] + 3; break;
+                            default: break;
+                            }
+                        }
                     }
                     if (ii == T.n && jj == T.m) {
                         fval = v;
                         fset = true;
+                        fcnt = ce;
                     }
                 }
             }
             r0[d] = v;
+            if constexpr (COUNT)
+                c0[d] = ce;
             if constexpr (TRACE) {
                 const uint64_t nib = (uint64_t)mv << (4 * ((k >> 1) & 15));
                 w0[u] |= par ? 0 : nib;
@@ -1739,8 +1851,12 @@ __device__ __forceinline__ void ps_gen_body(const DPTask *__restrict__ tasks, co
     if (bad)
         ring[0] = 1.0;
     sync();
-    if (fset)
-        out[T.out_idx] = ring[0] != 0.0 ? __builtin_nan("") : fval;
+    if (fset) {
+        const bool raised = ring[0] != 0.0;
+        out[T.out_idx] = raised ? __builtin_nan("") : fval;
+        if constexpr (COUNT)
+            cnt[T.out_idx] = raised ? -1 : fcnt;
+    }
 }
 
 template <int NT>
@@ -1748,7 +1864,7 @@ __global__ void __launch_bounds__(NT)
 k_ps_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
          const double *__restrict__ tabs, double *__restrict__ out, int ring_ld)
 {
-    ps_gen_body<NT, NT == 64 ? PA_NPP64 : PA_NPPW, false>(tasks, bases, tabs, out, nullptr, ring_ld);
+    ps_gen_body<NT, NT == 64 ? PA_NPP64 : PA_NPPW, PS_SCORE>(tasks, bases, tabs, out, nullptr, nullptr, ring_ld);
 }
 
 template <int NT, int NPP>
@@ -1756,7 +1872,15 @@ __global__ void __launch_bounds__(NT)
 k_pa_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
          const double *__restrict__ tabs, double *__restrict__ out, uint64_t *__restrict__ trace, int ring_ld)
 {
-    ps_gen_body<NT, NPP, true>(tasks, bases, tabs, out, trace, ring_ld);
+    ps_gen_body<NT, NPP, PS_TRACE>(tasks, bases, tabs, out, trace, nullptr, ring_ld);
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT)
+k_pe_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
+         const double *__restrict__ tabs, double *__restrict__ out, int32_t *__restrict__ cnt, int ring_ld)
+{
+    ps_gen_body<NT, NT == 64 ? PA_NPP64 : PE_NPPW, PS_COUNT>(tasks, bases, tabs, out, nullptr, cnt, ring_ld);
 }
 
 __global__ void __launch_bounds__(64)
@@ -5586,6 +5710,8 @@ enum Ev : int {
     EV_PAIR_FILL_END,
     EV_PAIR_WALK_END,
     EV_PAIR_EMIT_END,
+    EV_PAIR_ERRORS_BEGIN,   // a launch set of rf_pair_errors: around the counting fills (k_pe*)
+    EV_PAIR_ERRORS_END,
     EV_CAND_SELECT_BEGIN,   // cand_run: k_cand_select, then k_cand_choose
     EV_CAND_CHOOSE_BEGIN,
     EV_CAND_CHOOSE_END,
@@ -5693,6 +5819,7 @@ struct rf_ctx {
     double pair_ms = 0;         // kernels of the last rf_pair_scores
     double pa_fill_ms = 0, pa_walk_ms = 0;   // fills / walks of the last rf_pair_align
     double pa_emit_ms = 0;                   // k_pa_emit of the last rf_pair_align_text
+    double pe_ms = 0;                        // kernels of the last rf_pair_errors
     double cand_select_ms = 0, cand_choose_ms = 0;   // k_cand_select / k_cand_choose of the last candidate call
     hipEvent_t ev_block = nullptr;   // blocking-sync event (RF_OPT_SYNC_BLOCK)
     Opts opt;
@@ -6274,6 +6401,10 @@ int rf_create(int device, rf_ctx **out)
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)k_ps_gen<DPW_NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               160 * 1024);
+    (void)hipFuncSetAttribute((const void *)k_pe_gen<64>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              48 * (PS_GEN64_H + 6));
+    (void)hipFuncSetAttribute((const void *)k_pe_gen<DPW_NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              48 * (PE_LDS_H + 6));
     (void)hipFuncSetAttribute((const void *)k_pa_gen<DPW_NT, PA_NPPW>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               160 * 1024);
     *out = ctx;
@@ -7376,6 +7507,8 @@ int rf_realign_jobs(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const int32
 // rf_pair_scores, which names none); mb: the bandwidth after the last
 // doubling (-1: the call's own).  Both are indices / bandwidths the checks
 // have found non-negative, so a negative value can only mean "not named".
+enum class PairCall { Scores, Align, Errors };   // rf_pair_scores | rf_pair_align* | rf_pair_errors
+
 static std::string band_too_wide(const std::string &fn, int64_t H, int64_t k, int64_t mb = -1)
 {
     return fn + ": band of " + std::to_string(H) + " rows" +
@@ -7385,11 +7518,13 @@ static std::string band_too_wide(const std::string &fn, int64_t H, int64_t k, in
 }
 
 // Argument, flag and per-pair checks.  `fn` names the entry point in the
-// messages; `outs_ok` is its check of its own output pointers; `align` is
-// rf_pair_align (its wording, and its timers are the ones reset).
-static int pair_check(rf_ctx *ctx, const std::string &fn, bool align, bool outs_ok, int64_t npairs,
+// messages; `outs_ok` is its check of its own output pointers; `call` gives
+// the wording (rf_pair_errors takes rf_pair_align's) and the timers that are
+// reset.
+static int pair_check(rf_ctx *ctx, const std::string &fn, PairCall call, bool outs_ok, int64_t npairs,
                       const int32_t *seq, const int32_t *tpl, const int32_t *bw, int32_t flags)
 {
+    const bool align = call != PairCall::Scores;
     if (!(ctx && npairs >= 0 && (npairs == 0 || (seq && tpl && bw)) && outs_ok))
         return fail(ctx, RF_ERR_ARG, fn + ": bad arguments");
     if (flags & RF_BWD)
@@ -7398,7 +7533,9 @@ static int pair_check(rf_ctx *ctx, const std::string &fn, bool align, bool outs_
     if (flags & ~(RF_FWD | RF_SKEW | RF_TRIM))
         return fail(ctx, RF_ERR_ARG, fn + ": unknown flags");
     (void)hipSetDevice(ctx->device);
-    if (align)
+    if (call == PairCall::Errors)
+        ctx->pe_ms = 0;
+    else if (align)
         ctx->pa_fill_ms = ctx->pa_walk_ms = ctx->pa_emit_ms = 0;
     else
         ctx->pair_ms = 0;
@@ -7416,8 +7553,9 @@ static int pair_check(rf_ctx *ctx, const std::string &fn, bool align, bool outs_
 }
 
 // The fill launches of a plan whose tasks are in BUF_PAIR_TASKS: k_pa* into
-// the trace d_tr, k_ps* without one.
-static int pair_fill(rf_ctx *ctx, const PairPlan &pl, double *d_out, uint64_t *d_tr)
+// the trace d_tr, k_pe* with the counts d_cnt (bands up to DP_COUNT_H; never
+// both), k_ps* with neither.
+static int pair_fill(rf_ctx *ctx, const PairPlan &pl, double *d_out, uint64_t *d_tr, int32_t *d_cnt)
 {
     const DPTask *d_tasks = dev<const DPTask>(ctx, BUF_PAIR_TASKS);
     const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
@@ -7427,6 +7565,8 @@ static int pair_fill(rf_ctx *ctx, const PairPlan &pl, double *d_out, uint64_t *d
     using KaFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, const double *, uint64_t *);
     const KsFn ks[4] = {k_ps<1>, k_ps<2>, k_ps<4>, k_ps<2, 64>};
     const KaFn ka[4] = {k_pa<1>, k_pa<2>, k_pa<4>, k_pa<2, 64>};
+    using KeFn = void (*)(const DPTask *, int, const uint8_t *, const double *, double *, const double *, int32_t *);
+    const KeFn ke[4] = {k_pe<1>, k_pe<2>, k_pe<4>, k_pe<2, 64>};
     for (int a = 0; a < 4; ++a)
         if (const int n = (int)pl.cls[a].size()) {
             const int tpw = a == 3 ? 1 : 4;
@@ -7434,6 +7574,9 @@ static int pair_fill(rf_ctx *ctx, const PairPlan &pl, double *d_out, uint64_t *d
             if (d_tr)
                 hipLaunchKernelGGL(ka[a], grid, dim3(64), 0, ctx->stream, d_tasks + pl.at[a], n, d_bases, d_tabs,
                                    d_out, d_lut, d_tr);
+            else if (d_cnt)
+                hipLaunchKernelGGL(ke[a], grid, dim3(64), 0, ctx->stream, d_tasks + pl.at[a], n, d_bases, d_tabs,
+                                   d_out, d_lut, d_cnt);
             else
                 hipLaunchKernelGGL(ks[a], grid, dim3(64), 0, ctx->stream, d_tasks + pl.at[a], n, d_bases, d_tabs,
                                    d_out, d_lut);
@@ -7443,7 +7586,15 @@ static int pair_fill(rf_ctx *ctx, const PairPlan &pl, double *d_out, uint64_t *d
             const int ld = pl.hmax[g] + 6;   // the LDS ring: 4 anti-diagonals of ld doubles
             const size_t lds = 4 * (size_t)ld * 8;
             const DPTask *tk = d_tasks + pl.at[4 + g];
-            if (g == 0 && d_tr)
+            if (d_cnt) {
+                // the count ring behind the score ring: 4 anti-diagonals of ld int32
+                if (g == 0)
+                    hipLaunchKernelGGL(k_pe_gen<64>, dim3(n), dim3(64), lds + lds / 2, ctx->stream, tk, d_bases,
+                                       d_tabs, d_out, d_cnt, ld);
+                else
+                    hipLaunchKernelGGL(k_pe_gen<DPW_NT>, dim3(n), dim3(DPW_NT), lds + lds / 2, ctx->stream, tk,
+                                       d_bases, d_tabs, d_out, d_cnt, ld);
+            } else if (g == 0 && d_tr)
                 hipLaunchKernelGGL((k_pa_gen<64, PA_NPP64>), dim3(n), dim3(64), lds, ctx->stream, tk, d_bases,
                                    d_tabs, d_out, d_tr, ld);
             else if (g == 0)
@@ -7504,6 +7655,7 @@ struct PairIo {
     const int64_t *moves_off;
     int32_t *nmoves, *nerrors;
     const PairText *tx;   // may be NULL
+    bool errors = false;  // rf_pair_errors: counts carried by the fills, kernel time to its own timer
     int64_t at(int64_t i) const { return idx ? idx[i] : i; }
 };
 // sees a pair's k, score, nmoves and nerrors; says whether its moves and texts go to the caller
@@ -7520,16 +7672,15 @@ static int pair_stage(rf_ctx *ctx, const PairSet &s, const PairLanding &L, const
     if (w.trace)
         if (int e = ensure_buf(ctx, b[BUF_PAIR_TRACE], (size_t)std::max<int64_t>(s.tr_at, 2) * 8))
             return e;
-    if (w.walk) {
-        if (w.want_mv()) {
-            if (int e = ensure_buf(ctx, b[BUF_PAIR_MOVES], L.mv_dev))
-                return e;
-            if (int e = upload(ctx, b[BUF_PAIR_MOVE_OFF], s.mvoff))
-                return e;
-        }
-        if (int e = ensure_buf(ctx, b[BUF_PAIR_COUNTS], L.counts))
+    if (w.walk && w.want_mv()) {
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_MOVES], L.mv_dev))
+            return e;
+        if (int e = upload(ctx, b[BUF_PAIR_MOVE_OFF], s.mvoff))
             return e;
     }
+    if (w.walk || w.count)
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_COUNTS], L.counts))
+            return e;
     if (w.want_txt) {
         if (int e = ensure_buf(ctx, b[BUF_PAIR_TEXT_T], L.mv_dev))
             return e;
@@ -7549,7 +7700,9 @@ static int pair_stage(rf_ctx *ctx, const PairSet &s, const PairLanding &L, const
 }
 
 // Step 2: the fills, then with a trace the walk (k_pa_walk_w or k_pa_walk by
-// pair_walk_wave) and k_pa_emit over the moves the walk left
+// pair_walk_wave) and k_pa_emit over the moves the walk left.  With
+// PairWants::count the fills are the set's only kernels, between marks of
+// their own.
 static int pair_launch(rf_ctx *ctx, const PairSet &s, const PairWants &w)
 {
     const int64_t cn = s.cn;
@@ -7560,10 +7713,10 @@ static int pair_launch(rf_ctx *ctx, const PairSet &s, const PairWants &w)
     int8_t *d_mv = w.want_mv() ? dev<int8_t>(ctx, BUF_PAIR_MOVES) : nullptr;
     const int64_t *d_mvoff = dev<const int64_t>(ctx, BUF_PAIR_MOVE_OFF);
     int32_t *d_cnt = dev<int32_t>(ctx, BUF_PAIR_COUNTS);
-    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_FILL_BEGIN], ctx->stream));
-    if (int e = pair_fill(ctx, s.pl, d_out, d_tr))
+    HIPCHK(ctx, hipEventRecord(ctx->ev[w.count ? EV_PAIR_ERRORS_BEGIN : EV_PAIR_FILL_BEGIN], ctx->stream));
+    if (int e = pair_fill(ctx, s.pl, d_out, d_tr, w.count ? d_cnt : nullptr))
         return e;
-    HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_FILL_END], ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[w.count ? EV_PAIR_ERRORS_END : EV_PAIR_FILL_END], ctx->stream));
     if (!w.trace)
         return 0;
     if (w.walk) {
@@ -7597,7 +7750,7 @@ static int pair_download(rf_ctx *ctx, const PairSet &s, const PairLanding &L, co
     const size_t mv = (size_t)s.mv_total;
     auto get = [&](size_t at, Buf b, size_t bytes) { return land(ctx, at, ctx->scratch[b].p, bytes); };
     HIPCHK(ctx, get(0, BUF_PAIR_SCORES, L.scores));
-    if (w.walk)
+    if (w.walk || w.count)
         HIPCHK(ctx, get(L.scores, BUF_PAIR_COUNTS, L.counts));
     if (w.walk && w.get_mv && mv > 0)
         HIPCHK(ctx, get(L.mv_at, BUF_PAIR_MOVES, mv));
@@ -7630,11 +7783,13 @@ static void pair_collect(rf_ctx *ctx, const PairIo &io, int64_t p0, const PairSe
             io.out_score[k] = sc[i];
         if (!w.walk)
             continue;
+        // the walk's counts are nmoves, then nerrors; the counting fills leave nerrors alone
+        const int32_t nmv = w.count ? -1 : cnt[i], nerr = w.count ? cnt[i] : cnt[cn + i];
         if (io.nmoves)
-            io.nmoves[k] = cnt[i];
+            io.nmoves[k] = nmv;
         if (io.nerrors)
-            io.nerrors[k] = cnt[cn + i];
-        if (ended && !ended(k, sc[i], cnt[i], cnt[cn + i]))
+            io.nerrors[k] = nerr;
+        if (ended && !ended(k, sc[i], nmv, nerr))
             continue;
         if (w.get_mv && cnt[i] > 0) {   // the walk leaves the moves at the end of the pair's n + m slot
             const int64_t slot = (i + 1 < cn ? s.mvoff[(size_t)i + 1] : s.mv_total) - s.mvoff[(size_t)i];
@@ -7657,6 +7812,14 @@ static void pair_collect(rf_ctx *ctx, const PairIo &io, int64_t p0, const PairSe
             std::memcpy(tx->t2s + tx->t2s_off[k], h + L.ix_at + sizeof(int32_t) * (size_t)s.ixoff[(size_t)i],
                         sizeof(int32_t) * (size_t)il);
     }
+    if (w.count) {
+        ctx->pe_ms += mark_ms(ctx, EV_PAIR_ERRORS_BEGIN, EV_PAIR_ERRORS_END);
+        return;
+    }
+    if (io.errors) {   // its pairs above DP_COUNT_H: the trace fill and the walk
+        ctx->pe_ms += mark_ms(ctx, EV_PAIR_FILL_BEGIN, EV_PAIR_WALK_END);
+        return;
+    }
     if (!w.trace) {
         ctx->pair_ms += mark_ms(ctx, EV_PAIR_FILL_BEGIN, EV_PAIR_FILL_END);
         return;
@@ -7667,30 +7830,24 @@ static void pair_collect(rf_ctx *ctx, const PairIo &io, int64_t p0, const PairSe
         ctx->pa_emit_ms += mark_ms(ctx, EV_PAIR_WALK_END, EV_PAIR_EMIT_END);
 }
 
-// The body of every pair call (one round of rf_pair_align_smart): the pairs of
-// `io` in launch sets of at most RF_OPT_PAIR_CHUNK pairs and, with `trace`,
-// RF_OPT_PAIR_TRACE_MB of trace (pair_set_end), so one set's buffers
-// (BUF_PAIR_*) are all the device memory a call needs, whatever its size.
-// Within a set the pairs are sorted into width classes, longest first.
-// Without `trace` (rf_pair_scores) the fills are k_ps*, score-only, and
-// nothing follows them.  `walk`: run the walk (counts, and moves where asked
-// for); with io.tx, k_pa_emit then runs over the moves, which are downloaded
-// only if io.moves asks for them.  `ended` (may be empty) sees a pair's score
+// The launch sets of a pair call: the pairs of `io` in sets of at most
+// RF_OPT_PAIR_CHUNK pairs and, with w.trace, RF_OPT_PAIR_TRACE_MB of trace
+// (pair_set_end), so one set's buffers (BUF_PAIR_*) are all the device memory
+// a call needs, whatever its size.  Within a set the pairs are sorted into
+// width classes, longest first.  `ended` (may be empty) sees a pair's score
 // and counts and says whether its moves and k_pa_emit's products go to the
 // caller; without it every pair's do.
-static int pair_run(rf_ctx *ctx, const PairIo &io, bool trace, bool walk, const PairEnded &ended)
+static int pair_sets(rf_ctx *ctx, const PairIo &io, const PairWants &w, const PairEnded &ended)
 {
     const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
     const int64_t budget = (int64_t)std::max(ctx->opt.pair_trace_mb, 1) << 20;   // bytes of trace per set
-    const bool emit = walk && io.tx && io.tx->any();
-    const PairWants w{trace, walk, io.moves != nullptr, emit, emit && io.tx->aln_t, emit && io.tx->t2s};
     PairSet s;
     for (int64_t p0 = 0; p0 < io.nidx; p0 += s.cn) {
-        const int64_t p1 = pair_set_end(p0, io.nidx, chunk, trace, budget, [&](int64_t i) {
+        const int64_t p1 = pair_set_end(p0, io.nidx, chunk, w.trace, budget, [&](int64_t i) {
             const int64_t k = io.at(i);
             return PairDims{ctx->seqs[io.seq[k]].n, ctx->tpls[io.tpl[k]].m, io.bw[k]};
         });
-        pair_set_fill(s, p1 - p0, trace, [&](int64_t i, bool *finite) {
+        pair_set_fill(s, p1 - p0, w.trace, [&](int64_t i, bool *finite) {
             const int64_t k = io.at(p0 + i);
             const SeqObj &S = ctx->seqs[io.seq[k]];
             *finite = S.finite;
@@ -7708,12 +7865,49 @@ static int pair_run(rf_ctx *ctx, const PairIo &io, bool trace, bool walk, const 
     return 0;
 }
 
+// The body of every pair call (one round of rf_pair_align_smart).  Without
+// `trace` (rf_pair_scores) the fills are k_ps*, score-only, and nothing
+// follows them.  `walk`: run the walk (counts, and moves where asked for);
+// with io.tx, k_pa_emit then runs over the moves, which are downloaded only
+// if io.moves asks for them.
+//
+// With io.errors (rf_pair_errors) the pairs whose band is within DP_COUNT_H
+// run first, in sets of their own, through the counting fills (k_pe*): no
+// trace, no walk, sets by the chunk alone.  The pairs above it follow through
+// the trace fill and the walk.
+static int pair_run(rf_ctx *ctx, const PairIo &io, bool trace, bool walk, const PairEnded &ended)
+{
+    if (!io.errors) {
+        const bool emit = walk && io.tx && io.tx->any();
+        const PairWants w{trace, walk, io.moves != nullptr, emit, emit && io.tx->aln_t, emit && io.tx->t2s};
+        return pair_sets(ctx, io, w, ended);
+    }
+    std::vector<int64_t> part[2];   // the pairs that carry their count | that take the trace
+    for (int64_t i = 0; i < io.nidx; ++i) {
+        const int64_t k = io.at(i);
+        const int H = band_rows(ctx->seqs[io.seq[k]].n + 1, ctx->tpls[io.tpl[k]].m + 1, io.bw[k]);
+        part[H > DP_COUNT_H].push_back(k);
+    }
+    for (int g = 0; g < 2; ++g) {
+        if (part[g].empty())
+            continue;
+        PairIo sub = io;
+        sub.nidx = (int64_t)part[g].size();
+        sub.idx = part[g].data();
+        PairWants w{g == 1, walk, false, false, false, false};
+        w.count = g == 0;
+        if (int e = pair_sets(ctx, sub, w, ended))
+            return e;
+    }
+    return 0;
+}
+
 // Score-only forward pass of independent pairs (k_ps / k_ps_gen).  Reads the
 // sequence and template arenas only: no slot, no band, no band bookkeeping.
 int rf_pair_scores(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
                    int32_t flags, double *out)
 {
-    if (int e = pair_check(ctx, "rf_pair_scores", false, npairs == 0 || out, npairs, seq, tpl, bw, flags))
+    if (int e = pair_check(ctx, "rf_pair_scores", PairCall::Scores, npairs == 0 || out, npairs, seq, tpl, bw, flags))
         return e;
     const PairIo io{npairs, nullptr, seq, tpl, bw, fill_flags(flags), out, nullptr, nullptr, nullptr, nullptr, nullptr};
     return pair_run(ctx, io, false, false, nullptr);
@@ -7726,7 +7920,7 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
                   int32_t flags, double *out_score, int8_t *moves, const int64_t *moves_off, int32_t *nmoves,
                   int32_t *nerrors)
 {
-    if (int e = pair_check(ctx, "rf_pair_align", true, !moves == !moves_off, npairs, seq, tpl, bw, flags))
+    if (int e = pair_check(ctx, "rf_pair_align", PairCall::Align, !moves == !moves_off, npairs, seq, tpl, bw, flags))
         return e;
     const PairIo io{npairs, nullptr, seq, tpl, bw, fill_flags(flags),
                     out_score, moves, moves_off, nmoves, nerrors, nullptr};
@@ -7739,15 +7933,17 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
 // `fn` names the entry point (rf_pair_align_smart, rf_pair_align_text); `tx`
 // (may be NULL) is rf_pair_align_text's outputs, which also lets threshold be
 // NULL when max_doublings is 0: no pair then gets past its first fill.
+// `errors`: rf_pair_errors, whose rounds take their counts from the fills
+// (pair_run with io.errors) and which has rf_pair_align_text's threshold rule.
 static int pair_smart_run(rf_ctx *ctx, const std::string &fn, bool outs_ok, int64_t npairs, const int32_t *seq,
                           const int32_t *tpl, const int32_t *bw, const double *threshold, const uint8_t *fixed,
                           int32_t max_doublings, int32_t flags, double *out_score, int8_t *moves,
                           const int64_t *moves_off, int32_t *nmoves, int32_t *nerrors, int32_t *out_bw,
-                          int32_t *out_rounds, const PairText *tx)
+                          int32_t *out_rounds, const PairText *tx, bool errors = false)
 {
-    if (int e = pair_check(ctx, fn, true, outs_ok, npairs, seq, tpl, bw, flags))
+    if (int e = pair_check(ctx, fn, errors ? PairCall::Errors : PairCall::Align, outs_ok, npairs, seq, tpl, bw, flags))
         return e;
-    if (npairs > 0 && !threshold && !(tx && max_doublings == 0))
+    if (npairs > 0 && !threshold && !((tx || errors) && max_doublings == 0))
         return fail(ctx, RF_ERR_ARG, fn + ": threshold is NULL");
     if (max_doublings < 0 || max_doublings > 5)
         return fail(ctx, RF_ERR_ARG, fn + ": max_doublings must be 0..5");
@@ -7797,7 +7993,7 @@ static int pair_smart_run(rf_ctx *ctx, const std::string &fn, bool outs_ok, int6
         for (int64_t k : pending)
             walk = walk || !stops_at_fill(k);
         const PairIo io{(int64_t)pending.size(), pending.data(), seq, tpl, cur.data(), fill_flags(flags), out_score,
-                        moves, moves_off, nmoves, nerrors, tx};
+                        moves, moves_off, nmoves, nerrors, tx, errors};
         if (int e = pair_run(ctx, io, true, walk, ended))
             return e;
         next.clear();
@@ -7842,6 +8038,26 @@ int rf_pair_align_text(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const in
     const PairText tx{aln_t, aln_s, aln_off, aln_len, t2s, t2s_off, t2s_len, tolerance};
     return pair_smart_run(ctx, "rf_pair_align_text", outs_ok, npairs, seq, tpl, bw, threshold, fixed, max_doublings,
                           flags, out_score, nullptr, nullptr, nullptr, nerrors, out_bw, out_rounds, &tx);
+}
+
+// rf_pair_align_smart without moves, the error count carried through the
+// fill beside the score (k_pe / k_pe_gen): no trace, no walk.  Pairs whose
+// band is wider than DP_COUNT_H take rf_pair_align_smart's path inside the
+// same rounds.
+int rf_pair_errors(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
+                   const double *threshold, const uint8_t *fixed, int32_t max_doublings, int32_t flags,
+                   double *out_score, int32_t *nerrors, int32_t *out_bw, int32_t *out_rounds)
+{
+    return pair_smart_run(ctx, "rf_pair_errors", true, npairs, seq, tpl, bw, threshold, fixed, max_doublings, flags,
+                          out_score, nullptr, nullptr, nullptr, nerrors, out_bw, out_rounds, nullptr, true);
+}
+
+int rf_last_pair_errors_ms(const rf_ctx *ctx, double *fill_ms)
+{
+    if (!ctx || !fill_ms)
+        return RF_ERR_ARG;
+    *fill_ms = ctx->pe_ms;
+    return 0;
 }
 
 int rf_last_pair_text_ms(const rf_ctx *ctx, double *emit_ms)

@@ -33,14 +33,15 @@ def __getattr__(name):
         from . import model
         return getattr(model, name)
     if name in ("align", "align_moves", "forward", "backward", "forward_moves", "edit_distance",
-                "moves_to_aligned_seqs", "moves_to_indices", "band_tolerance"):
+                "moves_to_aligned_seqs", "moves_to_indices", "band_tolerance", "forward_errors"):
         from . import align
         return getattr(align, name)
     if name in ("cross_scores", "choose_references"):
         from . import assign
         return getattr(assign, name)
     if name in ("align_moves_many", "align_many", "smart_align_moves_many", "smart_align_many", "edit_distances",
-                "correct_shifts_many", "align_indices_many", "band_tolerances"):
+                "correct_shifts_many", "align_indices_many", "band_tolerances", "count_errors_many",
+                "smart_bandwidths_many"):
         from . import pairalign
         return getattr(pairalign, name)
     if name in ("sample_sequences", "sample_mixture", "sample_from_template", "sample_reference",

@@ -66,6 +66,9 @@ _SIGNATURES = {
     "rf_pair_align_text": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                    c_int32] + [c_void_p] * 12),
     "rf_last_pair_text_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rf_pair_errors": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                               c_int32] + [c_void_p] * 4),
+    "rf_last_pair_errors_ms": (c_int, [c_void_p, POINTER(c_double)]),
     "rf_backtrace": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rf_score": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_void_p]),

@@ -111,6 +111,64 @@ def edit_distance(t, s, scratch=None):
     return count_errors(t, seq, scratch=scratch)
 
 
+def forward_errors(t, s: RifrafSequence, bandwidth=None, trim=False, skew_matches=False):
+    """(A[end, end], count_errors of the backtrace) of forward_moves!
+    (align.jl:114-141, cell rule :50-112) without a move array: a host
+    restatement, column by column, of what the engine's counting fills
+    (rf_pair_errors) carry per cell.  The path into a cell is the path into
+    the predecessor its move names -- the first strictly greater candidate in
+    the order match, insert, delete, codon insert, codon delete -- so its
+    error count (align.jl:240-245) is the predecessor's plus the move's: a
+    match adds s[i] != t[j], an insertion or a deletion 1, a codon move 3.
+    Only the last four columns are kept.  A cell the reference raises on
+    ("new score is invalid") -> (nan, -1)."""
+    t = DNASeq(t)
+    n, m = len(s), len(t)
+    bw = int(s.bandwidth if bandwidth is None else bandwidth)
+    if bw < 1:
+        raise ValueError("bandwidth must be positive")
+    if n < 1:
+        raise ValueError("forward_errors: empty sequence")
+    h_off, v_off = max(m - n, 0), max(n - m, 0)
+    seq = [int(b) for b in s.seq]
+    tpl = [int(b) for b in t]
+    match, mism, ins, dele = (x.tolist() for x in (s.match_scores, s.mismatch_scores, s.ins_scores, s.del_scores))
+    cins, cdel = s.codon_ins_scores.tolist(), s.codon_del_scores.tolist()
+    ninf = -math.inf
+    # column j - k is cols[k - 1]: (scores, counts) over rows 0..n, -inf outside the band
+    cols = [([ninf] * (n + 1), [0] * (n + 1)) for _ in range(3)]
+    for j in range(m + 1):
+        sc, ct = [ninf] * (n + 1), [0] * (n + 1)
+        (p1, c1), (p3, c3) = cols[0], cols[2]
+        for i in range(max(0, j - h_off - bw), min(j + v_off + bw, n) + 1):   # row_range, bandedarrays.jl:133-137
+            if i == 0 and j == 0:
+                sc[0] = 0.0
+                continue
+            sb = seq[i - 1] if i > 0 else -1
+            tb = tpl[j - 1] if j > 0 else -1
+            ks = max(i - 1, 0)
+            ms = match[ks] if sb == tb else mism[ks]
+            if skew_matches and sb != tb:
+                ms *= 0.99
+            isc = 0.0 if trim and (j == 0 or j == m) else ins[ks]
+            best, cnt = ninf, 0
+            if i > 0 and j > 0 and p1[i - 1] + ms > best:
+                best, cnt = p1[i - 1] + ms, c1[i - 1] + (1 if sb != tb else 0)
+            if i > 0 and sc[i - 1] + isc > best:
+                best, cnt = sc[i - 1] + isc, ct[i - 1] + 1
+            if j > 0 and p1[i] + dele[i] > best:
+                best, cnt = p1[i] + dele[i], c1[i] + 1
+            if cins and i >= 3 and sc[i - 3] + cins[i - 3] > best:
+                best, cnt = sc[i - 3] + cins[i - 3], ct[i - 3] + 3
+            if cdel and j >= 3 and p3[i] + cdel[i] > best:
+                best, cnt = p3[i] + cdel[i], c3[i] + 3
+            if best == ninf:
+                return math.nan, -1
+            sc[i], ct[i] = best, cnt
+        cols = [(sc, ct), cols[0], cols[1]]
+    return cols[0][0][n], cols[0][1][n]
+
+
 # ---------------------------------------------------------------------
 # host bookkeeping over move lists
 # ---------------------------------------------------------------------

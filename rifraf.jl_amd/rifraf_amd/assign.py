@@ -18,7 +18,7 @@ from .types import DNASeq
 
 def cross_scores(seqs, templates, bandwidth=None, engine=None, first_seq=0, first_tpl=0,
                  skew_matches=False, trim=False, bandwidth_pvalue=None, return_bandwidths=False,
-                 max_doublings=5):
+                 max_doublings=5, carry_counts=False):
     """(R, T) matrix of A[end, end] of every RifrafSequence against every
     template, in one engine call.  The sequences are uploaded as ids
     [first_seq, first_seq + R) and the templates as [first_tpl, first_tpl +
@@ -26,8 +26,10 @@ def cross_scores(seqs, templates, bandwidth=None, engine=None, first_seq=0, firs
     scores every cell at that bandwidth (rf_pair_scores); a value starts
     there and doubles the band of each cell as smart_forward_moves!
     (model.jl:643-672) does (rf_pair_align_smart, no moves kept), without
-    changing the sequences.  return_bandwidths: -> (scores, (R, T) int32
-    bandwidths the cells were scored at)."""
+    changing the sequences.  carry_counts: with a bandwidth_pvalue, the error
+    counts that decide the doubling ride through the fills (rf_pair_errors:
+    no move trace, no walk); the results are the same.  return_bandwidths:
+    -> (scores, (R, T) int32 bandwidths the cells were scored at)."""
     from .align import default_engine
     from .engine import RF_SKEW, RF_TRIM
     e = engine or default_engine()
@@ -57,8 +59,12 @@ def cross_scores(seqs, templates, bandwidth=None, engine=None, first_seq=0, firs
         r, j = (int(x[0]) for x in np.nonzero(rows > MAX_BAND_ROWS))
         raise RifrafError(f"sequence {r}, template {j}: band of {int(rows[r, j])} rows at its largest bandwidth is "
                           f"wider than the {MAX_BAND_ROWS} the engine aligns without bands")
-    sc, _, _, out_bw, _ = e.pair_align_smart(si, ti, bws, thr[:, None], fixed=fixed[:, None],
-                                             max_doublings=max_doublings, flags=flags, want_moves=False)
+    if carry_counts:
+        sc, _, out_bw, _ = e.pair_errors(si, ti, bws, thr[:, None], fixed=fixed[:, None],
+                                         max_doublings=max_doublings, flags=flags)
+    else:
+        sc, _, _, out_bw, _ = e.pair_align_smart(si, ti, bws, thr[:, None], fixed=fixed[:, None],
+                                                 max_doublings=max_doublings, flags=flags, want_moves=False)
     sc, out_bw = sc.reshape(R, T), out_bw.reshape(R, T)
     return (sc, out_bw) if return_bandwidths else sc
 
@@ -79,7 +85,7 @@ def first_maximum(totals) -> int:
 
 
 def choose_references(clusters, references, scores=None, bandwidth=9, phred_cap=None, engine=None,
-                      bandwidth_pvalue=None):
+                      bandwidth_pvalue=None, carry_counts=False):
     """The reference of each cluster.  clusters: (dnaseqs, phreds) per
     cluster; references: bare base sequences.  Every read (with its Phred
     tables, capped at phred_cap if given) is aligned to every reference as
@@ -87,7 +93,7 @@ def choose_references(clusters, references, scores=None, bandwidth=9, phred_cap=
     reference j and the first maximum wins.  bandwidth_pvalue: as in
     cross_scores (None: every cell at `bandwidth`; a value: band doubling
     from there, so a read against a reference it fits badly is not
-    under-scored).  -> [(index, totals)]."""
+    under-scored); carry_counts: as in cross_scores.  -> [(index, totals)]."""
     if scores is None:
         scores = Scores.from_errors(ErrorModel(1.0, 2.0, 2.0))
     out = []
@@ -96,7 +102,7 @@ def choose_references(clusters, references, scores=None, bandwidth=9, phred_cap=
             phreds = [cap_phreds(p, phred_cap) for p in phreds]
         seqs = [RifrafSequence(s, np.asarray(p, np.int8), bandwidth, scores) for s, p in zip(dnaseqs, phreds)]
         totals = fold_totals(cross_scores(seqs, references, bandwidth=bandwidth, engine=engine,
-                                           bandwidth_pvalue=bandwidth_pvalue))
+                                           bandwidth_pvalue=bandwidth_pvalue, carry_counts=carry_counts))
         out.append((first_maximum(totals), totals))
     return out
 

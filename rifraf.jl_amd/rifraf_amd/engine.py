@@ -553,6 +553,43 @@ class Engine:
             r.tolerance = None
         return scores[:n], r
 
+    def pair_errors(self, seqs, tpls, bws, thresholds=None, fixed=None, max_doublings: int = 0, flags=0):
+        """rf_pair_errors: score, count_errors (align.jl:240-250) and
+        smart_forward_moves!' band doubling (model.jl:643-672) per pair, the
+        count carried through the fill beside the score: no move trace, no
+        walk.  Arguments broadcast as pair_align_smart's; thresholds may be
+        None with max_doublings=0 (pair_align's score and nerrors at bws).
+        Returns (scores, nerrors, bandwidths, rounds) over the flattened
+        pairs, equal to pair_align_smart(..., want_moves=False)'s: a pair the
+        reference raises on has score NaN and nerrors -1."""
+        arrs = [np.asarray(seqs), np.asarray(tpls), np.asarray(bws)]
+        if thresholds is not None:
+            arrs.append(np.asarray(thresholds, np.float64))
+        if fixed is not None:
+            arrs.append(np.asarray(fixed))
+        arrs = np.broadcast_arrays(*arrs)
+        seqs = np.ascontiguousarray(arrs[0].reshape(-1), np.int32)
+        tpls = np.ascontiguousarray(arrs[1].reshape(-1), np.int32)
+        bws = np.ascontiguousarray(arrs[2].reshape(-1), np.int32)
+        thr = np.ascontiguousarray(arrs[3].reshape(-1), np.float64) if thresholds is not None else None
+        fx = np.ascontiguousarray(arrs[-1].reshape(-1) != 0, np.uint8) if fixed is not None else None
+        n = seqs.shape[0]
+        scores = np.empty(max(n, 1))
+        nerr = np.empty(max(n, 1), np.int32)
+        out_bw = np.empty(max(n, 1), np.int32)
+        rounds = np.empty(max(n, 1), np.int32)
+        self._check(self.lib.rf_pair_errors(self.ctx, n, ptr(seqs), ptr(tpls), ptr(bws), ptr(thr), ptr(fx),
+                                            int(max_doublings), int(flags), ptr(scores), ptr(nerr), ptr(out_bw),
+                                            ptr(rounds)))
+        return scores[:n], nerr[:n], out_bw[:n], rounds[:n]
+
+    def last_pair_errors_ms(self) -> float:
+        """Kernel ms of the last pair_errors call (all its launch sets and
+        rounds); last_pair_align_ms keeps its values."""
+        v = c_double()
+        self._check(self.lib.rf_last_pair_errors_ms(self.ctx, byref(v)))
+        return v.value
+
     def last_pair_text_ms(self) -> float:
         """k_pa_emit ms of the last pair_align_text call (all its launch sets
         and rounds); last_pair_align_ms reports its fills and walks."""

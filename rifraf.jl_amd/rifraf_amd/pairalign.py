@@ -1,5 +1,5 @@
 """Alignments of many pairs in one engine call (rf_pair_align,
-rf_pair_align_text).
+rf_pair_align_text), and their error counts alone (rf_pair_errors).
 
 The pairwise half of the reference's API over lists: align_moves / align
 (src/align.jl:337-353), edit_distance (:253-260) and the loop of
@@ -56,19 +56,13 @@ def max_bandwidths(bws, fixed, slen, tlen, max_doublings):
     return np.where(np.asarray(fixed, bool), bws, grown)
 
 
-def _run(e, seqs, templates, si, ti, bws, flags, want_moves, smart=None, text=None):
-    """One rf_pair_align call over pairs (si[k], ti[k]); sequences and
-    templates are uploaded as ids 0.. of the engine.  smart = (thresholds,
-    fixed, max_doublings): one rf_pair_align_smart call, and the band that
-    must fit is the one at the largest bandwidth a pair can reach.  text =
-    (want_text, want_indices, want_tolerance): one rf_pair_align_text call
-    instead (len(si) > 0) -> (scores, engine.PairText)."""
-    if len(si) == 0:
-        empty = (np.empty(0), ([] if want_moves else None), np.empty(0, np.int32))
-        return empty if smart is None else empty + (np.empty(0, np.int32), np.empty(0, np.int32))
+def _upload(e, seqs, templates, si, ti, bws, smart):
+    """Checks the band every pair (si[k], ti[k]) needs -- with smart =
+    (thresholds, fixed, max_doublings) the one at the largest bandwidth it can
+    reach -- and uploads sequences and templates as ids 0.. of the engine.
+    -> (sequence lengths, template lengths)."""
     slen = np.array([len(s) for s in seqs], np.int64)
     tlen = np.array([len(t) for t in templates], np.int64)
-    bws = np.broadcast_to(np.asarray(bws, np.int64), si.shape)
     top = bws if smart is None else max_bandwidths(bws, smart[1], slen[si], tlen[ti], smart[2])
     rows = 2 * top + np.abs(slen[si] - tlen[ti]) + 1
     wide = np.nonzero(rows > MAX_BAND_ROWS)[0]
@@ -79,6 +73,21 @@ def _run(e, seqs, templates, si, ti, bws, flags, want_moves, smart=None, text=No
                           f"{at} is wider than the {MAX_BAND_ROWS} the engine aligns without bands")
     e.set_sequences(0, seqs)
     e.set_templates(0, templates)
+    return slen, tlen
+
+
+def _run(e, seqs, templates, si, ti, bws, flags, want_moves, smart=None, text=None):
+    """One rf_pair_align call over pairs (si[k], ti[k]); sequences and
+    templates are uploaded as ids 0.. of the engine.  smart = (thresholds,
+    fixed, max_doublings): one rf_pair_align_smart call, and the band that
+    must fit is the one at the largest bandwidth a pair can reach.  text =
+    (want_text, want_indices, want_tolerance): one rf_pair_align_text call
+    instead (len(si) > 0) -> (scores, engine.PairText)."""
+    if len(si) == 0:
+        empty = (np.empty(0), ([] if want_moves else None), np.empty(0, np.int32))
+        return empty if smart is None else empty + (np.empty(0, np.int32), np.empty(0, np.int32))
+    bws = np.broadcast_to(np.asarray(bws, np.int64), si.shape)
+    slen, tlen = _upload(e, seqs, templates, si, ti, bws, smart)
     if text is not None:
         thr, fixed, md = smart if smart is not None else (None, None, 0)
         return e.pair_align_text(si, ti, bws, thr, fixed=fixed, max_doublings=md, flags=flags, want_text=text[0],
@@ -185,6 +194,53 @@ def smart_align_moves_many(seqs, templates, pairs=None, pvalue=BANDWIDTH_PVALUE,
     _, moves, _, out_bw, _ = _run(_engine(engine), seqs, templates, si, ti, bws, flags, True,
                                   smart=(thr, fixed, max_doublings))
     return moves, out_bw
+
+
+def _count_inputs(seqs, templates, pairs, bandwidth):
+    """The uploaded lists, the pair indices and the starting bandwidths of a
+    counting call, built as smart_align_moves_many builds them."""
+    seqs = list(seqs)
+    templates = [DNASeq(t) for t in templates]
+    si, ti = _pairs(pairs, len(seqs), len(templates))
+    if bandwidth is None:
+        bws = np.array([s.bandwidth for s in seqs], np.int64)[si]
+    else:
+        bws = np.full(si.shape, int(bandwidth), np.int64)
+    return seqs, templates, si, ti, bws
+
+
+def _errors(e, seqs, templates, si, ti, bws, flags, smart):
+    """One rf_pair_errors call over pairs (si[k], ti[k]).  smart: None or (thresholds, fixed, max_doublings).
+    -> (scores, nerrors, bandwidths)."""
+    if len(si) == 0:
+        return np.empty(0), np.empty(0, np.int32), np.empty(0, np.int32)
+    _upload(e, seqs, templates, si, ti, bws, smart)
+    thr, fixed, md = smart if smart is not None else (None, None, 0)
+    sc, nerr, out_bw, _ = e.pair_errors(si, ti, bws, thr, fixed=fixed, max_doublings=md, flags=flags)
+    return sc, nerr, out_bw
+
+
+def count_errors_many(seqs, templates, pairs=None, bandwidth=None, skew_matches=True, engine=None):
+    """count_errors(templates[j], seqs[i]) (align.jl:247-250: the skewed
+    alignment's count) for every (i, j) of `pairs`, in one engine call that
+    keeps no moves (rf_pair_errors).  Arguments as align_moves_many's.
+    -> int32 array; -1 for a pair the reference raises on."""
+    seqs, templates, si, ti, bws = _count_inputs(seqs, templates, pairs, bandwidth)
+    flags = RF_SKEW if skew_matches else 0
+    return _errors(_engine(engine), seqs, templates, si, ti, bws, flags, None)[1]
+
+
+def smart_bandwidths_many(seqs, templates, pairs=None, pvalue=BANDWIDTH_PVALUE, max_doublings=5, bandwidth=None,
+                          engine=None):
+    """The bandwidth smart_forward_moves! (model.jl:643-672) ends at for every
+    pair, with the error count and the score of its last fill, in one engine
+    call that keeps no moves (rf_pair_errors): the numbers of
+    smart_align_moves_many for the same arguments.  The RifrafSequences are
+    not changed.  -> (int32 bandwidths, int32 nerrors, scores)."""
+    seqs, templates, si, ti, bws = _count_inputs(seqs, templates, pairs, bandwidth)
+    thr, fixed = smart_inputs(seqs, si, pvalue)
+    sc, nerr, out_bw = _errors(_engine(engine), seqs, templates, si, ti, bws, 0, (thr, fixed, max_doublings))
+    return out_bw, nerr, sc
 
 
 def smart_align_many(seqs, templates, pairs=None, pvalue=BANDWIDTH_PVALUE, max_doublings=5, bandwidth=None,
@@ -294,4 +350,5 @@ def correct_shifts_many(consensuses, references, log_p=-1.0, bandwidth=-1, score
 
 
 __all__ = ["align_moves_many", "align_many", "smart_align_moves_many", "smart_align_many", "align_indices_many",
-           "band_tolerances", "edit_distances", "correct_shifts_many", "MAX_BAND_ROWS"]
+           "band_tolerances", "edit_distances", "correct_shifts_many", "count_errors_many", "smart_bandwidths_many",
+           "MAX_BAND_ROWS"]
