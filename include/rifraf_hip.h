@@ -24,6 +24,10 @@
  *   rf_pair_errors    <- count_errors and smart_forward_moves!' band doubling
  *                        over many pairs, without moves
  *                        src/align.jl:240-250, src/model.jl:643-672
+ *   rf_pair_shifts    <- single_indel_proposals, has_single_indels and
+ *                        correct_shifts (apply_proposals, are_ambiguous) over
+ *                        many pairs  src/model.jl:532-562,1303-1316,
+ *                        src/proposals.jl:41-102, scripts/correct_shifts.jl:61-68
  *   rf_backtrace      <- backtrace + count_errors   src/align.jl:229-245
  *   rf_alignment_proposals <- alignment_proposals / moves_to_proposals
  *                        src/model.jl:458-497
@@ -449,6 +453,62 @@ int rf_pair_errors(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_
  * rounds; the trace fills and walks of its widest pairs included),
  * milliseconds.  Leaves rf_last_pair_align_ms' values as they were. */
 int rf_last_pair_errors_ms(const rf_ctx *ctx, double *fill_ms);
+
+/* rf_pair_align that hands back frameshift correction instead of the moves,
+ * computed on the device from the walk's output (k_pa_fix).  The sequence is
+ * the reference, the template the consensus; i and j are the sequence and
+ * template positions after a move.
+ *   proposals   single_indel_proposals (model.jl:538-562) in move order: an
+ *               insert gives Insertion(j, s[i-1]), a delete Deletion(j); kind
+ *               1 / 2, 1-based pos (Insertion at 0 allowed) and base at
+ *               prop_kind / prop_pos / prop_base[prop_off[k] ...].  The pair's
+ *               capacity is prop_off[k+1] - prop_off[k] (npairs + 1 offsets):
+ *               the first that many records are written, nprops[k] is the true
+ *               count (rf_candidates' rule).
+ *   fixed       correct_shifts (model.jl:1303-1316), i.e. apply_proposals
+ *               (proposals.jl:80-102) of those proposals to the template:
+ *               base codes 0..3 at fixed[fixed_off[k] ...] (capacity n + m),
+ *               fixed_len[k] of them.  A set apply_proposals refuses
+ *               (are_ambiguous, proposals.jl:41-56: two insertions at one
+ *               position) gets fixed_len = -2 and no bytes; its proposals and
+ *               tallies are reported.
+ *   tally       5 int32 per pair: its moves of each code 1..5 (match, insert,
+ *               delete, codon insert, codon delete).
+ * The caller passes RF_SKEW for correct_shifts and single_indel_proposals and
+ * 0 for has_single_indels (model.jl:532-536: tally[5k+1] + tally[5k+2] > 0).
+ * Every output pointer may be NULL; fixed needs fixed_off, the three record
+ * arrays are NULL together and need prop_off (else RF_ERR_ARG; a refused call
+ * changes nothing).  If fixed, fixed_len, nprops, the records and tally are all
+ * NULL the kernel is not launched and the call is rf_pair_align's score.
+ * Checks, messages, flags (RF_FWD implied, RF_BWD is RF_ERR_ARG), the
+ * 5,114-row limit and the return value are rf_pair_align's.  A pair the
+ * reference raises on (score NaN), or whose walk fails, gets fixed_len =
+ * nprops = -1, tallies of -1 and none of its bytes or records; the call still
+ * returns 0.  The moves are not downloaded.  The call touches no slot, no band
+ * and not the band arena; its device memory is bounded by RF_OPT_PAIR_CHUNK /
+ * RF_OPT_PAIR_TRACE_MB (per launch set: rf_pair_align's, n + m bytes of
+ * corrected template and at most 5 (n + m) bytes of records per pair). */
+int rf_pair_shifts(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl,
+                   const int32_t *bw, int32_t flags, double *out_score,
+                   uint8_t *fixed, const int64_t *fixed_off, int32_t *fixed_len,
+                   int32_t *nprops, const int64_t *prop_off, uint8_t *prop_kind,
+                   int32_t *prop_pos, uint8_t *prop_base, int32_t *tally);
+/* Summed k_pa_fix time of the last rf_pair_shifts call, milliseconds (0 if it
+ * launched none); rf_last_pair_align_ms reports its fills and walks. */
+int rf_last_pair_shifts_ms(const rf_ctx *ctx, double *fix_ms);
+/* rf_pair_shifts' products from given moves, on the host alone (no context,
+ * no GPU; csrc/rifraf_shift_fix.h): pair k has nmoves[k] moves at
+ * moves[moves_off[k] ...], the sequence sbases[s_off[k] .. s_off[k+1]) and the
+ * template tbases[t_off[k] .. t_off[k+1]) (npairs + 1 offsets each).  A pair
+ * with nmoves < 0 gets the -1 outputs.  Returns 0, or RF_ERR_ARG (nothing
+ * written) for a missing array, a move code outside 1..5, moves that leave
+ * either string, or record offsets that decrease. */
+int rf_host_shift_fix(int64_t npairs, const int8_t *moves, const int64_t *moves_off,
+                      const int32_t *nmoves, const uint8_t *sbases, const int64_t *s_off,
+                      const uint8_t *tbases, const int64_t *t_off,
+                      uint8_t *fixed, const int64_t *fixed_off, int32_t *fixed_len,
+                      int32_t *nprops, const int64_t *prop_off, uint8_t *prop_kind,
+                      int32_t *prop_pos, uint8_t *prop_base, int32_t *tally);
 
 /* Backtrace of the A band of each slot (align.jl:229-238), moves in
  * alignment order written at moves[moves_off[k] ...] (capacity n+m each);

@@ -361,7 +361,9 @@ struct PairWants {
     bool emit;     // k_pa_emit runs: aln_len, t2s_len and tolerance, and with
     bool want_txt, want_ix;   // ... these the two texts / the index maps
     bool count = false;   // rf_pair_errors: the fills carry nerrors (k_pe*); no trace, no walk, nothing else above
-    bool want_mv() const { return get_mv || emit; }   // the walk writes the moves
+    bool fix = false;     // k_pa_fix runs: fixed_len, nprops and the tallies, and with
+    bool want_fixed = false, want_rec = false;   // ... these the corrected templates / the proposal records
+    bool want_mv() const { return get_mv || emit || fix; }   // the walk writes the moves
 };
 
 struct PairDims {
@@ -397,7 +399,23 @@ struct PairSet {
     PairPlan pl;
     std::vector<int64_t> mvoff, ixoff;   // per pair, in set order
     int64_t tr_at = 0, mv_total = 0, ix_total = 0;   // the totals: trace words, move bytes, map entries
+    // k_pa_fix's proposal records (pair_set_records): cn + 1 offsets, the last the total
+    std::vector<int64_t> proff;
+    int64_t pr_total = 0;
 };
+
+// The device capacity of each pair's proposal records: cap(i) is what the
+// caller gave pair i, and no pair has more proposals than its n + m moves.
+template <class F>
+void pair_set_records(PairSet &s, F cap)
+{
+    s.proff.assign((size_t)s.cn + 1, 0);
+    for (int64_t i = 0; i < s.cn; ++i) {
+        const int64_t slot = (i + 1 < s.cn ? s.mvoff[(size_t)i + 1] : s.mv_total) - s.mvoff[(size_t)i];
+        s.proff[(size_t)i + 1] = s.proff[(size_t)i] + std::max<int64_t>(std::min(cap(i), slot), 0);
+    }
+    s.pr_total = s.proff[(size_t)s.cn];
+}
 
 // Fills `s` with the cn pairs of a set.  task(i, &finite): the DPTask of the
 // set's pair i (out_idx i; no band, P or pad yet) and whether its tables are
@@ -409,7 +427,8 @@ void pair_set_fill(PairSet &s, int64_t cn, bool trace, F task)
     s.pl.clear();
     s.mvoff.assign(trace ? (size_t)cn : 0, 0);
     s.ixoff.assign(trace ? (size_t)cn : 0, 0);
-    s.tr_at = s.mv_total = s.ix_total = 0;
+    s.tr_at = s.mv_total = s.ix_total = s.pr_total = 0;
+    s.proff.clear();
     for (int64_t i = 0; i < cn; ++i) {
         bool finite = false;
         DPTask t = task(i, &finite);
@@ -438,9 +457,15 @@ struct PairLanding {
     size_t lens;             // bytes: 3 cn int32 (aln_len, t2s_len, tolerance)
     size_t total;            // bytes of the zone
     size_t mv_dev, ix_dev;   // device bytes of the moves (and of each text) and of the index maps
+    // k_pa_fix: its seven int32 per pair, the corrected templates (mv_total
+    // bytes), the records' kind | base << 4 bytes (pr_total) and positions
+    size_t fix_at, fixed_at, kb_at, pos_at;
+    size_t fixes;            // bytes: 7 cn int32 (fixed_len, nprops, the five tallies)
+    size_t kb_dev, pos_dev;  // device bytes of the two record arrays
 };
 
-inline PairLanding pair_landing(int64_t cn, int64_t mv_total, int64_t ix_total, const PairWants &w)
+inline PairLanding pair_landing(int64_t cn, int64_t mv_total, int64_t ix_total, const PairWants &w,
+                                int64_t pr_total = 0)
 {
     const auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     PairLanding L{};
@@ -461,6 +486,16 @@ inline PairLanding pair_landing(int64_t cn, int64_t mv_total, int64_t ix_total, 
     L.total = L.ix_at + (w.want_ix ? sizeof(int32_t) * (size_t)ix_total : 0);
     L.mv_dev = (size_t)std::max<int64_t>(mv_total, 16);
     L.ix_dev = sizeof(int32_t) * (size_t)std::max<int64_t>(ix_total, 4);
+    if (w.fix) {
+        L.fixes = sizeof(int32_t) * 7 * (size_t)cn;
+        L.fix_at = up16(L.total);
+        L.fixed_at = up16(L.fix_at + L.fixes);
+        L.kb_at = up16(L.fixed_at + (w.want_fixed ? (size_t)mv_total : 0));
+        L.pos_at = up16(L.kb_at + (w.want_rec ? (size_t)pr_total : 0));
+        L.total = L.pos_at + (w.want_rec ? sizeof(int32_t) * (size_t)pr_total : 0);
+        L.kb_dev = (size_t)std::max<int64_t>(pr_total, 16);
+        L.pos_dev = sizeof(int32_t) * (size_t)std::max<int64_t>(pr_total, 4);
+    }
     return L;
 }
 

@@ -22,6 +22,9 @@
 //               src/align.jl:240-250, src/model.jl:643-672
 //   k_pa_emit   gapped texts, index maps and band tolerances from those moves
 //               (rf_pair_align_text)  src/align.jl:262-311,322-335
+//   k_pa_fix    frameshift correction from those moves (rf_pair_shifts): the
+//               single-indel proposals, the corrected template, ambiguity
+//               src/model.jl:538-562,1303-1316, src/proposals.jl:41-102
 //   k_score_ws / k_score_segl / k_score
 //               dense per-position proposal scoring of every batch read,
 //               left-folded over the batch in batch order
@@ -66,6 +69,7 @@
 #include "rifraf_score_plan.h"
 #include "rifraf_seq_upload.h"
 #include "rifraf_candidates.h"
+#include "rifraf_shift_fix.h"
 
 #define RF_INF (__builtin_inf())
 
@@ -2142,6 +2146,127 @@ k_pa_emit(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restric
         lens[oi] = bo;
         lens[(size_t)ntasks + oi] = bk;
         lens[2 * (size_t)ntasks + oi] = tol;
+    }
+}
+
+// k_pa_fix (rf_pair_shifts): correct_shifts (model.jl:1303-1316) from a
+// pair's moves, on the moves the walk left in device memory.  The sequence s
+// (rows) is the reference, the template t the consensus.  Shape and scan are
+// k_pa_emit's: one wave per pair, the lanes take 64 consecutive moves in
+// alignment order, and (di, dj), the bases the move adds to the corrected
+// template and whether it proposes go through one inclusive wave scan packed
+// in bytes (a chunk sums to at most 3 * 64 per field) on top of the running
+// totals.  The per-move rules are rifraf_shift_fix.h's, which the host
+// restatement (rf_host_shift_fix) shares.  With i, j after its move:
+//   - single_indel_proposals (model.jl:538-562): an insert (2) is
+//     Insertion(j, s[i - 1]), a delete (3) is Deletion(j), in move order; the
+//     other moves propose nothing.  The first `capacity` records of a pair are
+//     stored, nprops is the true count.
+//   - apply_proposals(t, proposals) (proposals.jl:80-102) is the
+//     concatenation, per move, of: match t[j - 1]; insert s[i - 1]; delete and
+//     codon insert nothing; codon delete t[j - 3 .. j - 1].  Why: j never
+//     decreases along the moves and Deletion(p) is made by the move that
+//     brings j to p, Insertion(p, b) by a later move at j = p, so move order
+//     is already the order apply_proposals sorts to (by pos, deletions first).
+//     It copies t[next .. pos - 1], then a deletion skips t[pos]; an insertion
+//     at pos > 0 without a deletion there emits t[pos], b; after a deletion at
+//     pos, or at pos = 0, it emits b alone; next = pos + 1, and the tail
+//     follows.  So every template base is emitted exactly once, in order,
+//     unless a Deletion names it, and b comes right behind the bases up to
+//     t[pos].  Per move that is the same text: each template position belongs
+//     to exactly one j-advancing move (a match or a codon delete emits it, a
+//     delete drops it), and an insert emits s[i - 1] when the bases up to t[j]
+//     are out (or dropped) -- before the first base at j = 0, after t[j] if it
+//     was kept, in its place if the move before deleted it.  A move adds at
+//     most di + dj bases, so the length is at most n + m.
+//   - are_ambiguous (proposals.jl:41-56): the deletions' positions are
+//     distinct (each takes a new j), so the set is ambiguous exactly when two
+//     inserts share a j, i.e. an insert whose previous insert has the same j
+//     (no move between them advanced j; a codon insert does not).  A lane
+//     finds the insert before it by a ballot, or in the j of the last insert
+//     of the chunks before (last_ins).  fixed_len is then -2; the proposals
+//     and tallies are reported all the same.
+// out: fixed_len, nprops and the counts of the move codes 1..5, ntasks of
+// each; a pair the walk gave up (-1) gets -1 in all seven and no bytes or
+// records.  fixed and the records (rec_kb = kind | base << 4, rec_pos) may be
+// off (NULL); rec_off holds ntasks + 1 offsets.  No LDS, no atomics.
+__global__ void __launch_bounds__(64 * PAW_NW)
+k_pa_fix(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+         const int8_t *__restrict__ moves, const int64_t *__restrict__ moves_off,
+         const int32_t *__restrict__ nmoves, uint8_t *__restrict__ fixed, uint8_t *__restrict__ rec_kb,
+         int32_t *__restrict__ rec_pos, const int64_t *__restrict__ rec_off, int32_t *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int t = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * PAW_NW + (threadIdx.x >> 6)));
+    if (t >= ntasks)
+        return;
+    const DPTask &T = tasks[t];
+    const int n = T.n, m = T.m, oi = T.out_idx;
+    const int cnt = nmoves[oi];
+    if (cnt < 0) {
+        if (lane < 2 + SF_TALLIES)
+            out[(size_t)lane * ntasks + oi] = -1;
+        return;
+    }
+    const uint8_t *s = bases + T.sb;
+    const uint8_t *tt = bases + T.tb;
+    const int64_t slot = moves_off[oi];
+    const int8_t *mvs = moves + slot + (n + m - cnt);   // end-aligned by the walk
+    uint8_t *fx = fixed ? fixed + slot : nullptr;
+    const int64_t r0 = rec_kb ? rec_off[oi] : 0;
+    const int cap = rec_kb ? (int)(rec_off[oi + 1] - r0) : 0;
+    int bi = 0, bj = 0, bo = 0, bk = 0;   // i, j, corrected bases and proposals of the chunks before
+    int last_ins = -1;                    // j of the last insert of the chunks before
+    bool amb = false;
+    int tl[SF_TALLIES] = {0, 0, 0, 0, 0};
+    for (int x0 = 0; x0 < cnt; x0 += 64) {
+        const bool on = x0 + lane < cnt;
+        const int mv = on ? mvs[x0 + lane] : 0;
+        const int w = sf_width(mv), pr = sf_proposes(mv) ? 1 : 0;
+        int sc = sf_di(mv) | (sf_dj(mv) << 8) | (w << 16) | (pr << 24);
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(sc, d, 64);
+            sc += lane >= d ? up : 0;
+        }
+        const int i = bi + (sc & 255), j = bj + ((sc >> 8) & 255);
+        const int o = bo + ((sc >> 16) & 255) - w, k = bk + ((sc >> 24) & 255) - pr;
+        if (fx) {
+            if (mv == 1)
+                fx[o] = tt[j - 1];
+            else if (mv == 2)
+                fx[o] = s[i - 1];
+            else if (mv == 5) {
+#pragma unroll
+                for (int u = 0; u < 3; ++u)
+                    fx[o + u] = tt[j - 3 + u];
+            }
+        }
+        if (rec_kb && pr && k < cap) {
+            rec_kb[r0 + k] = (uint8_t)(mv == 2 ? SF_INS | (s[i - 1] << 4) : SF_DEL);
+            rec_pos[r0 + k] = j;
+        }
+        const uint64_t insm = __ballot(mv == 2);
+        const uint64_t below = insm & ((1ull << lane) - 1);
+        const int jp = __shfl(j, below ? 63 - __builtin_clzll(below) : lane, 64);
+        amb = amb || __ballot(mv == 2 && j == (below ? jp : last_ins)) != 0;
+        if (insm)
+            last_ins = __builtin_amdgcn_readlane(j, __builtin_amdgcn_readfirstlane(63 - __builtin_clzll(insm)));
+#pragma unroll
+        for (int c = 0; c < SF_TALLIES; ++c)
+            tl[c] += __popcll(__ballot(mv == c + 1));
+        const int tot = __builtin_amdgcn_readlane(sc, 63);
+        bi += tot & 255;
+        bj += (tot >> 8) & 255;
+        bo += (tot >> 16) & 255;
+        bk += (tot >> 24) & 255;
+    }
+    if (lane == 0) {
+        out[oi] = amb ? -2 : bo;
+        out[(size_t)ntasks + oi] = bk;
+#pragma unroll
+        for (int c = 0; c < SF_TALLIES; ++c)
+            out[(size_t)(2 + c) * ntasks + oi] = tl[c];
     }
 }
 
@@ -5676,6 +5801,14 @@ enum Buf : int {
     BUF_PAIR_INDEX,
     BUF_PAIR_INDEX_OFF,
     BUF_PAIR_LENGTHS,
+    // k_pa_fix's products for one launch set: the corrected templates, the
+    // proposal records (kind | base << 4, pos) with their offsets, and
+    // fixed_len / nprops / the five tallies
+    BUF_PAIR_FIXED,
+    BUF_PAIR_PROP_KB,
+    BUF_PAIR_PROP_POS,
+    BUF_PAIR_PROP_OFF,
+    BUF_PAIR_FIX_OUT,
     // The candidate calls (cand_run, which waits for the stream after its
     // downloads).  The proposal mask of rf_candidates, (m + 1) x 9 bytes per
     // group at dplan's dense_off: the caller's rows of source 4, marked on top
@@ -5710,6 +5843,7 @@ enum Ev : int {
     EV_PAIR_FILL_END,
     EV_PAIR_WALK_END,
     EV_PAIR_EMIT_END,
+    EV_PAIR_FIX_END,      // ... or k_pa_fix, from EV_PAIR_WALK_END
     EV_PAIR_ERRORS_BEGIN,   // a launch set of rf_pair_errors: around the counting fills (k_pe*)
     EV_PAIR_ERRORS_END,
     EV_CAND_SELECT_BEGIN,   // cand_run: k_cand_select, then k_cand_choose
@@ -5819,6 +5953,7 @@ struct rf_ctx {
     double pair_ms = 0;         // kernels of the last rf_pair_scores
     double pa_fill_ms = 0, pa_walk_ms = 0;   // fills / walks of the last rf_pair_align
     double pa_emit_ms = 0;                   // k_pa_emit of the last rf_pair_align_text
+    double pa_fix_ms = 0;                    // k_pa_fix of the last rf_pair_shifts
     double pe_ms = 0;                        // kernels of the last rf_pair_errors
     double cand_select_ms = 0, cand_choose_ms = 0;   // k_cand_select / k_cand_choose of the last candidate call
     hipEvent_t ev_block = nullptr;   // blocking-sync event (RF_OPT_SYNC_BLOCK)
@@ -7536,7 +7671,7 @@ static int pair_check(rf_ctx *ctx, const std::string &fn, PairCall call, bool ou
     if (call == PairCall::Errors)
         ctx->pe_ms = 0;
     else if (align)
-        ctx->pa_fill_ms = ctx->pa_walk_ms = ctx->pa_emit_ms = 0;
+        ctx->pa_fill_ms = ctx->pa_walk_ms = ctx->pa_emit_ms = ctx->pa_fix_ms = 0;
     else
         ctx->pair_ms = 0;
     for (int64_t k = 0; k < npairs; ++k) {
@@ -7643,6 +7778,18 @@ struct PairText {   // rf_pair_align_text's outputs, each NULL or indexed by the
     bool any() const { return aln_t || aln_len || t2s || t2s_len || tolerance; }
 };
 
+struct PairFix {   // rf_pair_shifts' outputs, each NULL or indexed by the pair's own k
+    uint8_t *fixed;
+    const int64_t *fixed_off;
+    int32_t *fixed_len, *nprops;
+    const int64_t *prop_off;
+    uint8_t *prop_kind;
+    int32_t *prop_pos;
+    uint8_t *prop_base;
+    int32_t *tally;
+    bool any() const { return fixed || fixed_len || nprops || prop_kind || tally; }
+};
+
 // The pairs of one pair_run and where their results go.  List position i is
 // pair at(i); seq, tpl, bw and every output are indexed by the pair's own k.
 struct PairIo {
@@ -7656,6 +7803,7 @@ struct PairIo {
     int32_t *nmoves, *nerrors;
     const PairText *tx;   // may be NULL
     bool errors = false;  // rf_pair_errors: counts carried by the fills, kernel time to its own timer
+    const PairFix *fx = nullptr;   // rf_pair_shifts: k_pa_fix's products
     int64_t at(int64_t i) const { return idx ? idx[i] : i; }
 };
 // sees a pair's k, score, nmoves and nerrors; says whether its moves and texts go to the caller
@@ -7696,11 +7844,25 @@ static int pair_stage(rf_ctx *ctx, const PairSet &s, const PairLanding &L, const
     if (w.emit)
         if (int e = ensure_buf(ctx, b[BUF_PAIR_LENGTHS], L.lens))
             return e;
+    if (w.fix)
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_FIX_OUT], L.fixes))
+            return e;
+    if (w.want_fixed)
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_FIXED], L.mv_dev))
+            return e;
+    if (w.want_rec) {
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_PROP_KB], L.kb_dev))
+            return e;
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_PROP_POS], L.pos_dev))
+            return e;
+        if (int e = upload(ctx, b[BUF_PAIR_PROP_OFF], s.proff))
+            return e;
+    }
     return ensure_landing(ctx, L.total);
 }
 
 // Step 2: the fills, then with a trace the walk (k_pa_walk_w or k_pa_walk by
-// pair_walk_wave) and k_pa_emit over the moves the walk left.  With
+// pair_walk_wave) and k_pa_emit or k_pa_fix over the moves the walk left.  With
 // PairWants::count the fills are the set's only kernels, between marks of
 // their own.
 static int pair_launch(rf_ctx *ctx, const PairSet &s, const PairWants &w)
@@ -7741,6 +7903,16 @@ static int pair_launch(rf_ctx *ctx, const PairSet &s, const PairWants &w)
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_EMIT_END], ctx->stream));
     }
+    if (w.fix) {   // never with emit: its time runs from EV_PAIR_WALK_END
+        hipLaunchKernelGGL(k_pa_fix, dim3((unsigned)((cn + PAW_NW - 1) / PAW_NW)), dim3(64 * PAW_NW), 0,
+                           ctx->stream, d_tasks, (int)cn, d_bases, (const int8_t *)d_mv, d_mvoff,
+                           (const int32_t *)d_cnt, w.want_fixed ? dev<uint8_t>(ctx, BUF_PAIR_FIXED) : nullptr,
+                           w.want_rec ? dev<uint8_t>(ctx, BUF_PAIR_PROP_KB) : nullptr,
+                           w.want_rec ? dev<int32_t>(ctx, BUF_PAIR_PROP_POS) : nullptr,
+                           dev<const int64_t>(ctx, BUF_PAIR_PROP_OFF), dev<int32_t>(ctx, BUF_PAIR_FIX_OUT));
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(ctx->ev[EV_PAIR_FIX_END], ctx->stream));
+    }
     return 0;
 }
 
@@ -7762,6 +7934,14 @@ static int pair_download(rf_ctx *ctx, const PairSet &s, const PairLanding &L, co
     }
     if (w.want_ix && s.ix_total > 0)
         HIPCHK(ctx, get(L.ix_at, BUF_PAIR_INDEX, sizeof(int32_t) * (size_t)s.ix_total));
+    if (w.fix)
+        HIPCHK(ctx, get(L.fix_at, BUF_PAIR_FIX_OUT, L.fixes));
+    if (w.want_fixed && mv > 0)
+        HIPCHK(ctx, get(L.fixed_at, BUF_PAIR_FIXED, mv));
+    if (w.want_rec && s.pr_total > 0) {
+        HIPCHK(ctx, get(L.kb_at, BUF_PAIR_PROP_KB, (size_t)s.pr_total));
+        HIPCHK(ctx, get(L.pos_at, BUF_PAIR_PROP_POS, sizeof(int32_t) * (size_t)s.pr_total));
+    }
     HIPCHK(ctx, stream_wait(ctx));
     return 0;
 }
@@ -7776,6 +7956,7 @@ static void pair_collect(rf_ctx *ctx, const PairIo &io, int64_t p0, const PairSe
     const double *sc = landed<double>(ctx);
     const int32_t *cnt = landed<int32_t>(ctx, L.scores);
     const int32_t *len = landed<int32_t>(ctx, L.len_at);   // aln_len, t2s_len, tolerance: cn of each
+    const int32_t *fix = landed<int32_t>(ctx, L.fix_at);   // fixed_len, nprops, the five tallies: cn of each
     const PairText *tx = io.tx;
     for (int64_t i = 0; i < cn; ++i) {
         const int64_t k = io.at(p0 + i);
@@ -7794,6 +7975,28 @@ static void pair_collect(rf_ctx *ctx, const PairIo &io, int64_t p0, const PairSe
         if (w.get_mv && cnt[i] > 0) {   // the walk leaves the moves at the end of the pair's n + m slot
             const int64_t slot = (i + 1 < cn ? s.mvoff[(size_t)i + 1] : s.mv_total) - s.mvoff[(size_t)i];
             std::memcpy(io.moves + io.moves_off[k], h + L.mv_at + s.mvoff[(size_t)i] + slot - cnt[i], (size_t)cnt[i]);
+        }
+        if (w.fix) {   // k_pa_fix writes the corrected template from the start of the slot
+            const PairFix *fx = io.fx;
+            const int32_t fl = fix[i], np = fix[cn + i];
+            if (fx->fixed_len)
+                fx->fixed_len[k] = fl;
+            if (fx->nprops)
+                fx->nprops[k] = np;
+            for (int c = 0; fx->tally && c < SF_TALLIES; ++c)
+                fx->tally[k * SF_TALLIES + c] = fix[(2 + c) * cn + i];
+            if (w.want_fixed && fl > 0)
+                std::memcpy(fx->fixed + fx->fixed_off[k], h + L.fixed_at + s.mvoff[(size_t)i], (size_t)fl);
+            if (w.want_rec) {   // the first `capacity` records; a failed pair (-1) has none
+                const int64_t r0 = s.proff[(size_t)i], nr = std::min<int64_t>(np, s.proff[(size_t)i + 1] - r0);
+                const uint8_t *kb = (const uint8_t *)h + L.kb_at + r0;
+                const int32_t *pos = (const int32_t *)(h + L.pos_at) + r0;
+                for (int64_t r = 0; r < nr; ++r) {
+                    fx->prop_kind[fx->prop_off[k] + r] = kb[r] & 15;
+                    fx->prop_base[fx->prop_off[k] + r] = kb[r] >> 4;
+                    fx->prop_pos[fx->prop_off[k] + r] = pos[r];
+                }
+            }
         }
         if (!w.emit)
             continue;
@@ -7828,6 +8031,8 @@ static void pair_collect(rf_ctx *ctx, const PairIo &io, int64_t p0, const PairSe
     ctx->pa_walk_ms += mark_ms(ctx, EV_PAIR_FILL_END, EV_PAIR_WALK_END);
     if (w.emit)
         ctx->pa_emit_ms += mark_ms(ctx, EV_PAIR_WALK_END, EV_PAIR_EMIT_END);
+    if (w.fix)
+        ctx->pa_fix_ms += mark_ms(ctx, EV_PAIR_WALK_END, EV_PAIR_FIX_END);
 }
 
 // The launch sets of a pair call: the pairs of `io` in sets of at most
@@ -7853,7 +8058,12 @@ static int pair_sets(rf_ctx *ctx, const PairIo &io, const PairWants &w, const Pa
             *finite = S.finite;
             return pair_task(S, ctx->tpls[io.tpl[k]], io.bw[k], io.fl, (int32_t)i);
         });
-        const PairLanding L = pair_landing(s.cn, s.mv_total, s.ix_total, w);
+        if (w.want_rec)
+            pair_set_records(s, [&](int64_t i) {
+                const int64_t k = io.at(p0 + i);
+                return io.fx->prop_off[k + 1] - io.fx->prop_off[k];
+            });
+        const PairLanding L = pair_landing(s.cn, s.mv_total, s.ix_total, w, s.pr_total);
         if (int e = pair_stage(ctx, s, L, w))
             return e;
         if (int e = pair_launch(ctx, s, w))
@@ -7868,8 +8078,8 @@ static int pair_sets(rf_ctx *ctx, const PairIo &io, const PairWants &w, const Pa
 // The body of every pair call (one round of rf_pair_align_smart).  Without
 // `trace` (rf_pair_scores) the fills are k_ps*, score-only, and nothing
 // follows them.  `walk`: run the walk (counts, and moves where asked for);
-// with io.tx, k_pa_emit then runs over the moves, which are downloaded only
-// if io.moves asks for them.
+// with io.tx, k_pa_emit then runs over the moves (with io.fx, k_pa_fix),
+// which are downloaded only if io.moves asks for them.
 //
 // With io.errors (rf_pair_errors) the pairs whose band is within DP_COUNT_H
 // run first, in sets of their own, through the counting fills (k_pe*): no
@@ -7879,7 +8089,10 @@ static int pair_run(rf_ctx *ctx, const PairIo &io, bool trace, bool walk, const 
 {
     if (!io.errors) {
         const bool emit = walk && io.tx && io.tx->any();
-        const PairWants w{trace, walk, io.moves != nullptr, emit, emit && io.tx->aln_t, emit && io.tx->t2s};
+        PairWants w{trace, walk, io.moves != nullptr, emit, emit && io.tx->aln_t, emit && io.tx->t2s};
+        w.fix = walk && io.fx && io.fx->any();
+        w.want_fixed = w.fix && io.fx->fixed;
+        w.want_rec = w.fix && io.fx->prop_kind;
         return pair_sets(ctx, io, w, ended);
     }
     std::vector<int64_t> part[2];   // the pairs that carry their count | that take the trace
@@ -7925,6 +8138,44 @@ int rf_pair_align(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t
     const PairIo io{npairs, nullptr, seq, tpl, bw, fill_flags(flags),
                     out_score, moves, moves_off, nmoves, nerrors, nullptr};
     return pair_run(ctx, io, true, moves || nmoves || nerrors, nullptr);
+}
+
+// rf_pair_align whose products are k_pa_fix's: single_indel_proposals
+// (model.jl:538-562) and correct_shifts (model.jl:1303-1316) of each pair.
+// The moves stay on the device.
+int rf_pair_shifts(rf_ctx *ctx, int64_t npairs, const int32_t *seq, const int32_t *tpl, const int32_t *bw,
+                   int32_t flags, double *out_score, uint8_t *fixed, const int64_t *fixed_off, int32_t *fixed_len,
+                   int32_t *nprops, const int64_t *prop_off, uint8_t *prop_kind, int32_t *prop_pos,
+                   uint8_t *prop_base, int32_t *tally)
+{
+    const int nrec = (prop_kind != nullptr) + (prop_pos != nullptr) + (prop_base != nullptr);
+    bool outs_ok = (!fixed || fixed_off) && (nrec == 0 || (nrec == 3 && prop_off));
+    for (int64_t k = 0; outs_ok && nrec == 3 && k < npairs; ++k)
+        outs_ok = prop_off[k] >= 0 && prop_off[k + 1] >= prop_off[k];
+    if (int e = pair_check(ctx, "rf_pair_shifts", PairCall::Align, outs_ok, npairs, seq, tpl, bw, flags))
+        return e;
+    const PairFix fx{fixed, fixed_off, fixed_len, nprops, prop_off, prop_kind, prop_pos, prop_base, tally};
+    PairIo io{npairs, nullptr, seq, tpl, bw, fill_flags(flags), out_score, nullptr, nullptr, nullptr, nullptr, nullptr};
+    io.fx = &fx;
+    return pair_run(ctx, io, true, fx.any(), nullptr);
+}
+
+int rf_last_pair_shifts_ms(const rf_ctx *ctx, double *fix_ms)
+{
+    if (!ctx || !fix_ms)
+        return RF_ERR_ARG;
+    *fix_ms = ctx->pa_fix_ms;
+    return 0;
+}
+
+int rf_host_shift_fix(int64_t npairs, const int8_t *moves, const int64_t *moves_off, const int32_t *nmoves,
+                      const uint8_t *sbases, const int64_t *s_off, const uint8_t *tbases, const int64_t *t_off,
+                      uint8_t *fixed, const int64_t *fixed_off, int32_t *fixed_len, int32_t *nprops,
+                      const int64_t *prop_off, uint8_t *prop_kind, int32_t *prop_pos, uint8_t *prop_base,
+                      int32_t *tally)
+{
+    return host_shift_fix(npairs, moves, moves_off, nmoves, sbases, s_off, tbases, t_off, fixed, fixed_off,
+                          fixed_len, nprops, prop_off, prop_kind, prop_pos, prop_base, tally);
 }
 
 // smart_forward_moves! (model.jl:643-672) of independent pairs: rounds of

@@ -25,7 +25,7 @@ def __getattr__(name):
     if name in ("Engine", "RifrafError"):
         from . import engine
         return getattr(engine, name)
-    if name in ("host_candidates", "CAND_SOURCES"):
+    if name in ("host_candidates", "CAND_SOURCES", "host_shift_fix", "PairShifts"):
         from . import _lib
         return getattr(_lib, name)
     if name in ("rifraf", "RifrafParams", "RifrafResult", "RifrafState", "correct_shifts",
@@ -41,7 +41,7 @@ def __getattr__(name):
         return getattr(assign, name)
     if name in ("align_moves_many", "align_many", "smart_align_moves_many", "smart_align_many", "edit_distances",
                 "correct_shifts_many", "align_indices_many", "band_tolerances", "count_errors_many",
-                "smart_bandwidths_many"):
+                "smart_bandwidths_many", "single_indel_proposals_many", "has_single_indels_many"):
         from . import pairalign
         return getattr(pairalign, name)
     if name in ("sample_sequences", "sample_mixture", "sample_from_template", "sample_reference",

@@ -69,6 +69,9 @@ _SIGNATURES = {
     "rf_pair_errors": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                c_int32] + [c_void_p] * 4),
     "rf_last_pair_errors_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rf_pair_shifts": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32] + [c_void_p] * 10),
+    "rf_last_pair_shifts_ms": (c_int, [c_void_p, POINTER(c_double)]),
+    "rf_host_shift_fix": (c_int, [c_int64] + [c_void_p] * 16),
     "rf_backtrace": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rf_score": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_void_p]),
@@ -386,6 +389,90 @@ def host_candidates(cons, tables, scores, sources, min_dist, masks=None, cand_ca
     if rc != 0:
         raise ValueError(f"rf_host_candidates: bad arguments ({rc})")
     return io.results(with_counts)
+
+
+class PairShifts:
+    """The outputs of rf_pair_shifts and rf_host_shift_fix over n pairs:
+    fixed_len, nprops and tally ((n, 5): the moves of each code 1..5), the
+    corrected templates' bytes `fixed` at fixed_off, and the proposal records
+    prop_kind / prop_pos / prop_base at prop_off.  fixed_caps: n + m of each
+    pair (None: no corrected templates); prop_caps: the records each pair has
+    room for (None: no records).  A failed pair has fixed_len = nprops = -1
+    and tallies of -1, an ambiguous one fixed_len = -2."""
+    __slots__ = ("n", "fixed", "fixed_off", "fixed_len", "nprops", "prop_off", "prop_kind", "prop_pos", "prop_base",
+                 "tally")
+
+    def __init__(self, n, fixed_caps=None, prop_caps=None):
+        self.n = n
+        self.fixed_len = np.full(max(n, 1), -1, np.int32)[:n]
+        self.nprops = np.full(max(n, 1), -1, np.int32)[:n]
+        self.tally = np.full((max(n, 1), 5), -1, np.int32)[:n]
+        self.fixed = self.fixed_off = self.prop_off = self.prop_kind = self.prop_pos = self.prop_base = None
+        if fixed_caps is not None:
+            self.fixed_off = self._offsets(fixed_caps)
+            self.fixed = np.full(max(int(self.fixed_off[-1]), 1), 255, np.uint8)
+        if prop_caps is not None:
+            self.prop_off = self._offsets(prop_caps)
+            k = max(int(self.prop_off[-1]), 1)
+            self.prop_kind, self.prop_pos = np.full(k, 255, np.uint8), np.full(k, -1, np.int32)
+            self.prop_base = np.full(k, 255, np.uint8)
+
+    def _offsets(self, caps):
+        off = np.zeros(self.n + 1, np.int64)
+        np.cumsum(np.broadcast_to(np.asarray(caps, np.int64).reshape(-1), (self.n,)), out=off[1:])
+        return off
+
+    def args(self):
+        """The nine output arguments from `fixed` on, in the order of the C calls."""
+        return [ptr(a) for a in (self.fixed, self.fixed_off, self.fixed_len, self.nprops, self.prop_off,
+                                 self.prop_kind, self.prop_pos, self.prop_base, self.tally)]
+
+    def fixed_seq(self, k):
+        """The corrected template of pair k (uint8 base codes); None for a failed or an ambiguous pair."""
+        ln = int(self.fixed_len[k])
+        if ln < 0:
+            return None
+        o = int(self.fixed_off[k])
+        return self.fixed[o:o + ln].copy()
+
+    def proposals(self, k):
+        """The records of pair k as Insertion / Deletion proposals (the first
+        `capacity` of them); None for a failed pair."""
+        from .proposals import Proposal
+        if self.nprops[k] < 0:
+            return None
+        a = int(self.prop_off[k])
+        n = min(int(self.nprops[k]), int(self.prop_off[k + 1]) - a)
+        return [Proposal(int(self.prop_kind[i]), int(self.prop_pos[i]), int(self.prop_base[i])) for i in range(a, a + n)]
+
+    def has_single_indels(self):
+        """has_single_indels (model.jl:532-536) per pair: an insert or a delete among its moves (failed pairs: False)."""
+        return (self.tally[:, 1] + self.tally[:, 2]) > 0
+
+
+def host_shift_fix(moves, seqs, tpls, want_fixed=True, want_proposals=True, prop_cap=None):
+    """rf_host_shift_fix: rf_pair_shifts' products from given moves on the
+    host alone (no context, no GPU).  moves: one int8 array per pair in
+    alignment order, None for a failed pair; seqs / tpls: the pairs' base
+    arrays (the sequence is the reference, the template the consensus).
+    prop_cap: records per pair, a number or one per pair (None: n + m).
+    Returns a PairShifts."""
+    n = len(moves)
+    seqs = [np.asarray(s, np.uint8) for s in seqs]
+    tpls = [np.asarray(t, np.uint8) for t in tpls]
+    if len(seqs) != n or len(tpls) != n:
+        raise ValueError("host_shift_fix: one sequence and one template per move list")
+    nm = np.array([len(s) + len(t) for s, t in zip(seqs, tpls)], np.int64)
+    r = PairShifts(n, nm if want_fixed else None, (nm if prop_cap is None else prop_cap) if want_proposals else None)
+    cat = lambda xs, t: np.ascontiguousarray(np.concatenate([np.asarray(x, t) for x in xs] + [np.zeros(1, t)]), t)   # noqa: E731
+    off = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)   # noqa: E731
+    mvs = [np.zeros(0, np.int8) if mv is None else mv for mv in moves]
+    nmoves = np.ascontiguousarray([-1 if mv is None else len(mv) for mv in moves] + [0], np.int32)
+    rc = load().rf_host_shift_fix(n, ptr(cat(mvs, np.int8)), ptr(off(mvs)), ptr(nmoves), ptr(cat(seqs, np.uint8)),
+                                  ptr(off(seqs)), ptr(cat(tpls, np.uint8)), ptr(off(tpls)), *r.args())
+    if rc != 0:
+        raise ValueError(f"rf_host_shift_fix: bad arguments ({rc})")
+    return r
 
 
 def ptr(a: np.ndarray | None):

@@ -583,6 +583,54 @@ class Engine:
                                             ptr(rounds)))
         return scores[:n], nerr[:n], out_bw[:n], rounds[:n]
 
+    def pair_shifts(self, seqs, tpls, bws, flags=0, want_fixed: bool = True, want_proposals: bool = False,
+                    prop_cap=None, caps=None):
+        """rf_pair_shifts: pair_align whose products are made on the device
+        from the moves, which stay there: single_indel_proposals
+        (model.jl:538-562), the corrected template of correct_shifts
+        (:1303-1316) and the tallies of the move codes.  The sequence is the
+        reference, the template the consensus; pass RF_SKEW for
+        correct_shifts and single_indel_proposals, 0 for has_single_indels.
+        seqs / tpls / bws broadcast as in pair_align.  caps: n + m of each
+        pair, the capacity of its corrected template and (unless prop_cap
+        says otherwise) of its records; prop_cap: records per pair, a number
+        or one per pair.  Pass caps whenever the lengths are at hand: without
+        them and with want_fixed, or want_proposals without prop_cap, the
+        whole call runs twice, first for the lengths alone.
+        Returns (scores, _lib.PairShifts)."""
+        seqs, tpls, bws = np.broadcast_arrays(np.asarray(seqs), np.asarray(tpls), np.asarray(bws))
+        seqs = np.ascontiguousarray(seqs.reshape(-1), np.int32)
+        tpls = np.ascontiguousarray(tpls.reshape(-1), np.int32)
+        bws = np.ascontiguousarray(bws.reshape(-1), np.int32)
+        n = seqs.shape[0]
+        scores = np.empty(max(n, 1))
+
+        def call(sc, r):
+            self._check(self.lib.rf_pair_shifts(self.ctx, n, ptr(seqs), ptr(tpls), ptr(bws), int(flags), ptr(sc),
+                                                *r.args()))
+
+        fixed_caps = caps if want_fixed else None
+        prop_caps = (caps if prop_cap is None else prop_cap) if want_proposals else None
+        if (want_fixed and fixed_caps is None) or (want_proposals and prop_caps is None):
+            # the engine knows the lengths, this object does not: a first
+            # call for the lengths alone sizes the buffers exactly
+            first = _lib.PairShifts(n)
+            call(None, first)
+            if want_fixed and fixed_caps is None:
+                fixed_caps = np.maximum(first.fixed_len, 0)
+            if want_proposals and prop_caps is None:
+                prop_caps = np.maximum(first.nprops, 0)
+        r = _lib.PairShifts(n, fixed_caps, prop_caps)
+        call(scores, r)
+        return scores[:n], r
+
+    def last_pair_shifts_ms(self) -> float:
+        """k_pa_fix ms of the last pair_shifts call (all its launch sets);
+        last_pair_align_ms reports its fills and walks."""
+        v = c_double()
+        self._check(self.lib.rf_last_pair_shifts_ms(self.ctx, byref(v)))
+        return v.value
+
     def last_pair_errors_ms(self) -> float:
         """Kernel ms of the last pair_errors call (all its launch sets and
         rounds); last_pair_align_ms keeps its values."""

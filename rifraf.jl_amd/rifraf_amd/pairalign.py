@@ -11,6 +11,8 @@ Where only the gapped texts, the index maps (moves_to_indices, :322-335) or
 the band tolerances (:262-284) are wanted, the engine makes them from the
 moves on the device (Engine.pair_align_text) and the moves are not downloaded;
 an engine without that call gets the moves and align.py's per-move loops.
+The same holds for frameshift correction (rf_pair_shifts, Engine.pair_shifts):
+correct_shifts_many, single_indel_proposals_many and has_single_indels_many.
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ from .align import band_tolerance, moves_to_aligned_seqs, moves_to_indices
 from .engine import RF_SKEW, RF_TRIM, RifrafError
 from .errormodel import ErrorModel, Scores
 from .poisson import cquantile_poisson_many
-from .proposals import Deletion, Insertion, apply_proposals
+from .proposals import AmbiguousProposalsError, Deletion, Insertion, apply_proposals
 from .rifrafsequences import RifrafSequence
 from .types import DNASeq
 
@@ -319,36 +321,148 @@ def _single_indels(moves, refseq):
     return out
 
 
-def correct_shifts_many(consensuses, references, log_p=-1.0, bandwidth=-1, scores=None, engine=None):
-    """correct_shifts (model.jl:1303-1316) of every consensus against its
-    reference -- one reference for all, or one per consensus -- as the loop
-    of scripts/correct_shifts.jl:61-68 does, in one engine call: the skewed
-    codon alignment of single_indel_proposals (the reference is the
-    sequence, the consensus the template), then apply_proposals."""
-    scores = scores or Scores.from_errors(ErrorModel(10.0, 1e-5, 1e-5, 1.0, 1.0))
+def _shift_lists(fn, consensuses, references):
+    """The consensuses and their references -- one for all (a list of one),
+    or one per consensus -- as base arrays."""
     consensuses = [DNASeq(c) for c in consensuses]
     if isinstance(references, str) or (isinstance(references, np.ndarray) and references.ndim == 1):
         references = [references]
     references = [DNASeq(r) for r in references]
+    if len(references) != 1 and len(references) != len(consensuses):
+        raise ValueError(f"{fn}: one reference, or one per consensus")
+    return consensuses, references
+
+
+def _shift_moves(e, consensuses, references, log_p, bandwidth, scores):
+    """The skewed codon alignment of every consensus (template) against its
+    reference (sequence) through pair_align: one RifrafSequence per pair,
+    and the moves come to the host.  -> (sequences, moves), None for a
+    failed pair's."""
     if len(references) == 1:
         references = references * len(consensuses)
-    if len(references) != len(consensuses):
-        raise ValueError("correct_shifts_many: one reference, or one per consensus")
     rs = []
     for c, r in zip(consensuses, references):
         bw = bandwidth if bandwidth >= 0 else int(math.ceil(min(len(c), len(r)) * 0.1))
         rs.append(RifrafSequence(r, np.full(len(r), log_p), bw, scores))
     k = np.arange(len(consensuses), dtype=np.int64)
     bws = np.array([s.bandwidth for s in rs], np.int64)
-    _, moves, _ = _run(_engine(engine), rs, consensuses, k, k, bws, RF_SKEW, True)
-    out = []
-    for i, (c, s, mv) in enumerate(zip(consensuses, rs, moves)):
-        if mv is None:
+    _, moves, _ = _run(e, rs, consensuses, k, k, bws, RF_SKEW, True)
+    return rs, moves
+
+
+def _moves_or_raise(i, mv):
+    if mv is None:
+        raise RifrafError(f"pair {i}: new score is invalid")
+    return mv
+
+
+def _shifts(e, consensuses, seqs, si, bws, flags, want_fixed, want_proposals):
+    """One rf_pair_shifts call over the pairs (sequence seqs[si[k]], template
+    consensuses[k]); a sequence that many pairs share is uploaded once.
+    -> _lib.PairShifts."""
+    ti = np.arange(len(consensuses), dtype=np.int64)
+    slen, tlen = _upload(e, seqs, consensuses, si, ti, bws, None)
+    _, r = e.pair_shifts(si, ti, bws, flags, want_fixed=want_fixed, want_proposals=want_proposals,
+                         caps=slen[si] + tlen[ti])
+    return r
+
+
+def _shift_sequences(consensuses, references, log_p, bandwidth, scores):
+    """correct_shifts' sequences and bandwidths for rf_pair_shifts: the
+    bandwidth of a pair travels beside it, so one reference is one sequence
+    however many consensuses it meets.  -> (sequences, si, bws)."""
+    n = len(consensuses)
+    si = np.zeros(n, np.int64) if len(references) == 1 else np.arange(n, dtype=np.int64)
+    bws = np.array([bandwidth if bandwidth >= 0 else int(math.ceil(min(len(c), len(references[int(i)])) * 0.1))
+                    for c, i in zip(consensuses, si)], np.int64)
+    # a RifrafSequence wants a bandwidth of its own; the call does not read it
+    own = [int(bws.min())] if len(references) == 1 else bws.tolist()
+    rs = [RifrafSequence(r, np.full(len(r), log_p), int(b), scores) for r, b in zip(references, own)]
+    return rs, si, bws
+
+
+def _raise_failed(r, ambiguous):
+    """correct_shifts_many's exception for the first pair in order that has one."""
+    bad = (r.fixed_len == -1) | (r.nprops == -1)
+    if ambiguous:
+        bad = bad | (r.fixed_len == -2)
+    if bad.any():
+        i = int(np.argmax(bad))
+        if r.nprops[i] == -1:
             raise RifrafError(f"pair {i}: new score is invalid")
-        out.append(apply_proposals(c, _single_indels(mv, s.seq)))
-    return out
+        raise AmbiguousProposalsError()
+
+
+def correct_shifts_many(consensuses, references, log_p=-1.0, bandwidth=-1, scores=None, engine=None):
+    """correct_shifts (model.jl:1303-1316) of every consensus against its
+    reference -- one reference for all, or one per consensus -- as the loop
+    of scripts/correct_shifts.jl:61-68 does, in one engine call: the skewed
+    codon alignment of single_indel_proposals (the reference is the
+    sequence, the consensus the template), then apply_proposals.  The engine
+    makes the corrected consensuses from the moves on the device
+    (Engine.pair_shifts) and the moves are not downloaded; an engine without
+    that call gets the moves and the per-move loop."""
+    scores = scores or Scores.from_errors(ErrorModel(10.0, 1e-5, 1e-5, 1.0, 1.0))
+    consensuses, references = _shift_lists("correct_shifts_many", consensuses, references)
+    e = _engine(engine)
+    if not consensuses:
+        return []
+    if not hasattr(e, "pair_shifts"):
+        rs, moves = _shift_moves(e, consensuses, references, log_p, bandwidth, scores)
+        return [apply_proposals(c, _single_indels(_moves_or_raise(i, mv), s.seq))
+                for i, (c, s, mv) in enumerate(zip(consensuses, rs, moves))]
+    rs, si, bws = _shift_sequences(consensuses, references, log_p, bandwidth, scores)
+    r = _shifts(e, consensuses, rs, si, bws, RF_SKEW, True, False)
+    _raise_failed(r, True)
+    return [r.fixed_seq(k) for k in range(r.n)]
+
+
+def single_indel_proposals_many(consensuses, references, log_p=-1.0, bandwidth=-1, scores=None, engine=None):
+    """single_indel_proposals (model.jl:538-562) of every consensus against
+    its reference: the Insertion / Deletion proposals that correct_shifts_many
+    applies, in move order, from the same alignment and with the same
+    arguments.  One engine call.  -> list of proposal lists."""
+    scores = scores or Scores.from_errors(ErrorModel(10.0, 1e-5, 1e-5, 1.0, 1.0))
+    consensuses, references = _shift_lists("single_indel_proposals_many", consensuses, references)
+    e = _engine(engine)
+    if not consensuses:
+        return []
+    if not hasattr(e, "pair_shifts"):
+        rs, moves = _shift_moves(e, consensuses, references, log_p, bandwidth, scores)
+        return [_single_indels(_moves_or_raise(i, mv), s.seq) for i, (s, mv) in enumerate(zip(rs, moves))]
+    rs, si, bws = _shift_sequences(consensuses, references, log_p, bandwidth, scores)
+    r = _shifts(e, consensuses, rs, si, bws, RF_SKEW, False, True)
+    _raise_failed(r, False)
+    return [r.proposals(k) for k in range(r.n)]
+
+
+def has_single_indels_many(consensuses, refseqs, bandwidth=None, engine=None):
+    """has_single_indels (model.jl:532-536) of every consensus against its
+    reference, a RifrafSequence -- one for all, or one per consensus: does
+    the unskewed alignment (model.jl:534) hold a single insertion or
+    deletion?  bandwidth=None uses each reference's own.  One engine call.
+    -> bool array."""
+    consensuses = [DNASeq(c) for c in consensuses]
+    refseqs = [refseqs] if isinstance(refseqs, RifrafSequence) else list(refseqs)
+    if len(refseqs) != 1 and len(refseqs) != len(consensuses):
+        raise ValueError("has_single_indels_many: one reference, or one per consensus")
+    n = len(consensuses)
+    if n == 0:
+        return np.zeros(0, bool)
+    si = np.zeros(n, np.int64) if len(refseqs) == 1 else np.arange(n, dtype=np.int64)
+    if bandwidth is None:
+        bws = np.array([s.bandwidth for s in refseqs], np.int64)[si]
+    else:
+        bws = np.full(n, int(bandwidth), np.int64)
+    e = _engine(engine)
+    if not hasattr(e, "pair_shifts"):
+        _, moves, _ = _run(e, refseqs, consensuses, si, np.arange(n, dtype=np.int64), bws, 0, True)
+        return np.array([bool(((_moves_or_raise(i, mv) == 2) | (mv == 3)).any()) for i, mv in enumerate(moves)], bool)
+    r = _shifts(e, consensuses, refseqs, si, bws, 0, False, False)
+    _raise_failed(r, False)
+    return r.has_single_indels()
 
 
 __all__ = ["align_moves_many", "align_many", "smart_align_moves_many", "smart_align_many", "align_indices_many",
-           "band_tolerances", "edit_distances", "correct_shifts_many", "count_errors_many", "smart_bandwidths_many",
-           "MAX_BAND_ROWS"]
+           "band_tolerances", "edit_distances", "correct_shifts_many", "single_indel_proposals_many",
+           "has_single_indels_many", "count_errors_many", "smart_bandwidths_many", "MAX_BAND_ROWS"]
