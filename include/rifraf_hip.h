@@ -908,6 +908,20 @@ int rf_host_score_plan(int32_t nreads, const int32_t *n, const int32_t *m, const
                        const int32_t *opt_key, const int32_t *opt_val, int32_t per_seq, int32_t empty_ok,
                        int32_t *pick, int32_t *split, int32_t item_cap, int32_t *items, int32_t *nitems,
                        int64_t *dense_off, int64_t *split_off);
+/* The reads-per-workgroup rule of a scorer launch on the host alone: no
+ * context, no GPU (csrc/rifraf_score_plan.h score_chunks).  A launch of
+ * kernel family `kernel` (RF_SCK_*) in split mode (split != 0) or fused mode
+ * over nitems work items of groups of at most max_reads reads, at
+ * RF_OPT_SCORE_WGS = score_wgs and RF_OPT_SEG_WGS = seg_wgs (an option below
+ * 1 counts as 1).  Outputs: *rchunk, the consecutive reads of a group one
+ * workgroup takes, and *grid_y.  Fused: 1 and 1.  Split, RF_SCK_GENERAL: 1
+ * and max_reads.  Split, RF_SCK_SEG: rchunk = ceil(nitems * max_reads /
+ * seg_wgs), RF_SCK_WS: rchunk = max(1, floor(nitems * max_reads /
+ * score_wgs)), and grid_y = ceil(max_reads / rchunk) in both; rchunk may
+ * exceed max_reads (grid_y is then 1).  The product is taken in 64 bits.
+ * RF_ERR_ARG: an unknown family, nitems or max_reads below 1, a NULL output. */
+int rf_host_score_chunks(int32_t kernel, int32_t split, int32_t nitems, int32_t max_reads, int32_t score_wgs,
+                         int32_t seg_wgs, int32_t *rchunk, int32_t *grid_y);
 
 /* The row codes of rf_set_sequences on the host alone: no context, no GPU
  * (csrc/rifraf_seq_upload.h, DESIGN.md §4 "Sequence uploads").  nseq sequences

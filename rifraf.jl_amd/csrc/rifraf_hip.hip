@@ -6364,29 +6364,20 @@ unsigned launch_scorer(rf_ctx *ctx, const ScorePick &pk, unsigned nitems, unsign
     const double *d_bands = (const double *)ctx->band_arena.d;
     int sm = split ? 1 : 0;
     dim3 grid(nitems, gy);
+    // split: gy is the launch's max_reads (score_chunks, csrc/rifraf_score_plan.h)
+    const ScoreChunks ch = score_chunks(pk.family(), sm != 0, nitems, gy, ctx->opt.score_wgs, ctx->opt.seg_wgs);
+    if (sm)
+        grid.y = ch.grid_y;
     if (pk.seg) {
-        int rchunk = 1;
-        if (split) {
-            const int64_t tgt = std::max(ctx->opt.seg_wgs, 1);
-            rchunk = (int)std::max<int64_t>(1, ((int64_t)nitems * gy + tgt - 1) / tgt);
-            grid.y = (gy + rchunk - 1) / rchunk;
-        }
         hipLaunchKernelGGL(k_score_segl<32>, grid, dim3(64), 0, ctx->stream, items, groups, reads, d_bases, d_tabs,
-                           d_bands, dense, split, sm, rchunk);
+                           d_bands, dense, split, sm, ch.rchunk);
     } else if (!pk.lean) {
         hipLaunchKernelGGL(k_score, grid, dim3(128), 2 * pk.lds * 8, ctx->stream, items, groups, reads,
                            d_bases, d_tabs, d_bands, dense, split, sm, pk.lds);
     } else {
-        // split: enough reads per workgroup for the loaders' prefetch to
-        // overlap the chains, still >= 2,048 workgroups (one per CU at a time)
-        int rchunk = 1;
-        if (split) {
-            rchunk = (int)std::max<int64_t>(1, ((int64_t)nitems * gy) / std::max(ctx->opt.score_wgs, 1));
-            grid.y = (gy + rchunk - 1) / rchunk;
-        }
         hipLaunchKernelGGL((k_score_ws<WS_NPF, 256>), grid, dim3(512), pk.lds * 8, ctx->stream, items,
                            groups, reads, d_bases, d_tabs, d_bands, dense, split, sm, pk.lds,
-                           WS_CODES ? (const double *)ctx->codes.lut.p : nullptr, rchunk);
+                           WS_CODES ? (const double *)ctx->codes.lut.p : nullptr, ch.rchunk);
     }
     return grid.y;
 }
@@ -8906,6 +8897,17 @@ int rf_host_score_plan(int32_t nreads, const int32_t *n, const int32_t *m, const
     std::copy(P.gstart.begin(), P.gstart.end(), dense_off);
     for (int32_t g = 0; g < ngroups; ++g)
         split_off[g] = P.groups[g].split_off;
+    return 0;
+}
+
+int rf_host_score_chunks(int32_t kernel, int32_t split, int32_t nitems, int32_t max_reads, int32_t score_wgs,
+                         int32_t seg_wgs, int32_t *rchunk, int32_t *grid_y)
+{
+    if (kernel < RF_SCK_GENERAL || kernel > RF_SCK_WS || nitems < 1 || max_reads < 1 || !rchunk || !grid_y)
+        return RF_ERR_ARG;
+    const ScoreChunks ch = score_chunks(kernel, split != 0, nitems, max_reads, score_wgs, seg_wgs);
+    *rchunk = ch.rchunk;
+    *grid_y = (int32_t)ch.grid_y;
     return 0;
 }
 

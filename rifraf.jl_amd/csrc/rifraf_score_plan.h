@@ -139,6 +139,39 @@ inline bool score_split(int64_t nitems, int max_reads, int score_mode, bool per_
     return score_mode != 1 && nitems < 2048 && max_reads > 1;
 }
 
+// Reads per workgroup and grid.y of a scorer launch over nitems items of
+// groups of at most max_reads reads.  Fused mode folds every read of a group
+// in one workgroup (grid.y 1); the general scorer in split mode takes one read
+// per workgroup.  The segment scorer and k_score_ws in split mode take rchunk
+// consecutive reads of a group per workgroup: the segment scorer the fewest
+// that keep the launch within seg_wgs workgroups (RF_OPT_SEG_WGS, a ceiling),
+// k_score_ws the most that still leave score_wgs workgroups
+// (RF_OPT_SCORE_WGS, a floor): enough reads per workgroup for the loaders'
+// prefetch to overlap the chains, still one workgroup per CU at a time several
+// times over.  An option below 1 counts as 1.
+struct ScoreChunks {
+    int rchunk = 1;
+    unsigned grid_y = 1;
+};
+
+inline ScoreChunks score_chunks(int family, bool split, int64_t nitems, int64_t max_reads, int score_wgs, int seg_wgs)
+{
+    ScoreChunks c;
+    if (!split)
+        return c;
+    c.grid_y = (unsigned)max_reads;
+    if (family == RF_SCK_SEG) {
+        const int64_t tgt = std::max(seg_wgs, 1);
+        c.rchunk = (int)std::max<int64_t>(1, (nitems * max_reads + tgt - 1) / tgt);
+    } else if (family == RF_SCK_WS) {
+        c.rchunk = (int)std::max<int64_t>(1, (nitems * max_reads) / std::max(score_wgs, 1));
+    } else {
+        return c;
+    }
+    c.grid_y = (unsigned)((max_reads + c.rchunk - 1) / c.rchunk);
+    return c;
+}
+
 // What the planner reads of one batch read and of one group
 struct ScoreReadIn {
     int64_t A, B, sb, tab;   // bytes: the A and B bands', the sequence's bases' and tables' offsets

@@ -92,6 +92,7 @@ _SIGNATURES = {
     "rf_host_score_plan": (c_int, [c_int32] + [c_void_p] * 5 + [c_int32, c_void_p, c_int32, c_void_p, c_void_p,
                                    c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, POINTER(c_int32),
                                    c_void_p, c_void_p]),
+    "rf_host_score_chunks": (c_int, [c_int32] * 6 + [POINTER(c_int32), POINTER(c_int32)]),
     "rf_last_score_launch": (c_int, [c_void_p, c_void_p]),
     "rf_host_row_codes": (c_int, [c_int32] + [c_void_p] * 6 + [c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 6),
     "rf_host_upload_chunks": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p,
@@ -241,6 +242,19 @@ def host_score_plan(n, m, bw, read_off, stride=None, finite=None, per_seq=False,
         raise ValueError(f"rf_host_score_plan: bad arguments ({rc})")
     return ScorePlan(SCORE_KERNELS[pick[0]], int(pick[1]), int(pick[2]), bool(split[0]), bool(split[1]),
                      [tuple(int(x) for x in it) for it in items[:ni.value]], dense_off.tolist(), split_off[:ng].tolist())
+
+
+def host_score_chunks(kernel, split, nitems, max_reads, score_wgs=2048, seg_wgs=262144):
+    """rf_host_score_chunks: (rchunk, grid_y) of a scorer launch of family
+    `kernel` (a SCORE_KERNELS name) over nitems items of groups of at most
+    max_reads reads, on the host alone (no context, no GPU); the options
+    default as the engine's."""
+    rchunk, grid_y = c_int32(), c_int32()
+    rc = load().rf_host_score_chunks(SCORE_KERNELS.index(kernel), int(bool(split)), int(nitems), int(max_reads),
+                                     int(score_wgs), int(seg_wgs), ctypes.byref(rchunk), ctypes.byref(grid_y))
+    if rc != 0:
+        raise ValueError(f"rf_host_score_chunks: bad arguments ({rc})")
+    return rchunk.value, grid_y.value
 
 
 RF_CODES = 65536   # entries of the row codes' dictionary, per kind
