@@ -49,6 +49,57 @@ def dense_slot(kind, base):
     return np.where(kind == SUB, base, np.where(kind == DEL, 4, 5 + base))
 
 
+def tie_template(m, rng, max_run=4):
+    """A template of m bases in homopolymer runs of 1..max_run over two
+    letters.  -> (bases, run lengths, the letter of each run)."""
+    a, b = rng.choice(4, 2, replace=False)
+    runs = []
+    while sum(runs) < m:
+        runs.append(min(int(rng.integers(1, max_run + 1)), m - sum(runs)))
+    letters = [a if k % 2 == 0 else b for k in range(len(runs))]
+    t = np.concatenate([np.full(r, c, np.uint8) for r, c in zip(runs, letters)])
+    return t, runs, letters
+
+
+def tie_read(runs, letters, n, rng, edits=0, spread=8):
+    """A read of n bases made from a template's runs by shortening /
+    lengthening runs one base at a time until it has n bases (for n == m one
+    run is shortened and another lengthened); then `edits` times one run is
+    shortened by 1..3 bases (as far as it has them) and another run lengthened
+    by as many, at most `spread` runs away, so that the alignment leaves the
+    diagonal by at most three and comes back soon: a lengthening by two puts two
+    inserts at one template position, one by three is a codon."""
+    m = sum(runs)
+    rr = list(runs)
+    if n == m and len(rr) > 1:
+        k = int(rng.integers(0, len(rr)))
+        rr[k] -= 1
+        rr[(k + 1) % len(rr)] += 1
+    while sum(rr) > n:
+        k = int(rng.choice([i for i, r in enumerate(rr) if r > 0]))
+        rr[k] -= 1
+    while sum(rr) < n:
+        rr[int(rng.integers(0, len(rr)))] += 1
+    for _ in range(edits):
+        k = int(rng.choice([i for i, r in enumerate(rr) if r > 0]))
+        d = min(int(rng.integers(1, 4)), rr[k])
+        rr[k] -= d
+        rr[min(max(k + int(rng.integers(-spread, spread + 1)), 0), len(rr) - 1)] += d
+    s = np.concatenate([np.full(r, c, np.uint8) for r, c in zip(rr, letters)])
+    assert len(s) == n
+    return s
+
+
+def tie_pair(m, n, rng, max_run=4, edits=0, spread=8):
+    """A template of homopolymer runs over two letters, and a read made from
+    it by shortening / lengthening runs until it has n bases (for n == m one
+    run is shortened and another lengthened): at a constant error_log_p the
+    moves of the alignment tie all along the edited runs."""
+    t, runs, letters = tie_template(m, rng, max_run)
+    assert len(t) == m
+    return t, tie_read(runs, letters, n, rng, edits, spread)
+
+
 def assert_score_launch(engine, kernel=None, mode=None):
     """The engine's last scoring call ran the scorer `kernel` ("general",
     "seg", "ws") in `mode` ("fused", "split"); None: not checked.  The
@@ -62,4 +113,4 @@ def assert_score_launch(engine, kernel=None, mode=None):
 
 
 __all__ = ["make_read", "inband_mask", "all_proposals_arrays", "dense_slot", "random_seq",
-           "SEQ_SCORES", "REF_SCORES", "assert_score_launch"]
+           "SEQ_SCORES", "REF_SCORES", "assert_score_launch", "tie_template", "tie_read", "tie_pair"]

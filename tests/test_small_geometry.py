@@ -37,6 +37,7 @@ import pytest
 
 import oracle
 from _util import REF_SCORES, SEQ_SCORES, all_proposals_arrays, dense_slot, inband_mask, make_read, random_seq
+from _util import tie_pair as _tie_pair
 from rifraf_amd import RifrafSequence
 from rifraf_amd.align import moves_to_proposals_np
 from rifraf_amd.engine import RF_BAND_A, RF_BAND_B, RF_BWD, RF_FWD, RF_SKEW, RF_TRIM
@@ -54,31 +55,6 @@ CODON = ("ref", "ref0", "tie_ref")
 NONCODON = ("seq", "seq0", "tie_seq")
 TIE_LP = -1.0
 GAP = 4
-
-
-def _tie_pair(m, n, rng):
-    """A template of homopolymer runs over two letters, and a read made from
-    it by shortening / lengthening runs until it has n bases (for n == m one
-    run is shortened and another lengthened)."""
-    a, b = rng.choice(4, 2, replace=False)
-    runs = []
-    while sum(runs) < m:
-        runs.append(min(int(rng.integers(1, 5)), m - sum(runs)))
-    letters = [a if k % 2 == 0 else b for k in range(len(runs))]
-    t = np.concatenate([np.full(r, c, np.uint8) for r, c in zip(runs, letters)])
-    rr = list(runs)
-    if n == m and len(rr) > 1:
-        k = int(rng.integers(0, len(rr)))
-        rr[k] -= 1
-        rr[(k + 1) % len(rr)] += 1
-    while sum(rr) > n:
-        k = int(rng.choice([i for i, r in enumerate(rr) if r > 0]))
-        rr[k] -= 1
-    while sum(rr) < n:
-        rr[int(rng.integers(0, len(rr)))] += 1
-    s = np.concatenate([np.full(r, c, np.uint8) for r, c in zip(rr, letters)])
-    assert len(t) == m and len(s) == n
-    return t, s
 
 
 def _random_reads(rng, scores, zeros):
