@@ -875,6 +875,23 @@ int rf_host_dp_plan(int32_t njobs, const int32_t *n, const int32_t *m, const int
 /* The launch records of the context's last successful rf_realign /
  * rf_realign_jobs, in issue order; RF_ERR_ARG when there are more than cap. */
 int rf_last_dp_launches(const rf_ctx *ctx, int32_t cap, int32_t *launches, int32_t *nlaunches);
+/* Where the context's regions lie in its bump-allocated arenas, for the tests
+ * that place bands and tables at offsets beyond 32 bits and have to prove it
+ * (DESIGN.md §4 "High arena offsets").  Reads only: no state changes.
+ * slot >= 0: band[0] = byte offset and band[1] = capacity in bytes of band
+ * `which` (RF_BAND_A / RF_BAND_B) of that slot in the band arena.  seq >= 0:
+ * the same pair for the sequence's table region (tables and row codes, in the
+ * table arena) in tabs[2] and for its bases (in the byte arena) in bases[2].
+ * slot or seq = -1 asks for nothing of that kind, and its pointers may be
+ * NULL; both -1 is RF_ERR_ARG.  A slot that is unknown or whose band holds no
+ * region (never filled, or dropped by rf_release_bands), another `which`, and
+ * an id without a completed upload are RF_ERR_ARG, with nothing written.
+ * Offsets hold until the next call that allocates (an upload, a fill of a new
+ * or larger band, rf_reserve, rf_release_bands).  An added call: the ABI
+ * version stays 1, which changes only when a declared call or struct does.
+ * Engine-internal; no reference counterpart. */
+int rf_region_offsets(const rf_ctx *ctx, int32_t slot, int32_t which, int32_t seq, int64_t *band, int64_t *tabs,
+                      int64_t *bases);
 
 /* The scoring planner made observable (DESIGN.md §4 "Scoring planner"), for
  * the same reason: the three scorers, fused and split mode and both item

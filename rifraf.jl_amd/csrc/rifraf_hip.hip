@@ -7551,6 +7551,39 @@ int rf_last_dp_launches(const rf_ctx *ctx, int32_t cap, int32_t *launches, int32
     return 0;
 }
 
+int rf_region_offsets(const rf_ctx *ctx, int32_t slot, int32_t which, int32_t seq, int64_t *band, int64_t *tabs,
+                      int64_t *bases)
+{
+    if (!ctx || (slot < 0 && seq < 0))
+        return RF_ERR_ARG;
+    // every refusal comes before the first write
+    const Band *b = nullptr;
+    if (slot >= 0) {
+        if (!band || slot >= (int32_t)ctx->slots.size() || (which != RF_BAND_A && which != RF_BAND_B))
+            return RF_ERR_ARG;
+        b = which == RF_BAND_A ? &ctx->slots[slot].a : &ctx->slots[slot].b;
+        if (b->r.off < 0)
+            return RF_ERR_ARG;
+    }
+    const SeqObj *S = nullptr;
+    if (seq >= 0) {
+        if (!tabs || !bases || seq >= (int32_t)ctx->seqs.size() || !ctx->seqs[seq].valid)
+            return RF_ERR_ARG;
+        S = &ctx->seqs[seq];
+    }
+    if (b) {
+        band[0] = b->r.off;
+        band[1] = b->r.cap;
+    }
+    if (S) {
+        tabs[0] = S->tabs.off;
+        tabs[1] = S->tabs.cap;
+        bases[0] = S->bases.off;
+        bases[1] = S->bases.cap;
+    }
+    return 0;
+}
+
 int rf_host_dp_plan(int32_t njobs, const int32_t *n, const int32_t *m, const int32_t *bw, const int32_t *flags,
                     const int32_t *ncins, const int32_t *ncdel, const uint8_t *finite, const int32_t *stride_a,
                     const int32_t *stride_b, int32_t nopt, const int32_t *opt_key, const int32_t *opt_val,

@@ -89,6 +89,7 @@ _SIGNATURES = {
     "rf_host_dp_plan": (c_int, [c_int32] + [c_void_p] * 9 + [c_int32] + [c_void_p] * 6 + [POINTER(c_int32), c_int32,
                                 c_void_p, POINTER(c_int32)]),
     "rf_last_dp_launches": (c_int, [c_void_p, c_int32, c_void_p, POINTER(c_int32)]),
+    "rf_region_offsets": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "rf_host_score_plan": (c_int, [c_int32] + [c_void_p] * 5 + [c_int32, c_void_p, c_int32, c_void_p, c_void_p,
                                    c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, POINTER(c_int32),
                                    c_void_p, c_void_p]),

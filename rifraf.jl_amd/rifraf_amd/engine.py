@@ -882,6 +882,30 @@ class Engine:
         self._check(self.lib.rf_last_dp_launches(self.ctx, _lib.DP_LAUNCH_CAP, ptr(rec), byref(n)))
         return _lib.dp_launch_records(rec, n.value)
 
+    def band_region(self, slot: int, which: int = RF_BAND_A):
+        """rf_region_offsets of a band: (byte offset, capacity in bytes) of
+        the slot's A or B band in the band arena.  Raises RifrafError for a
+        slot without such a band."""
+        out = np.zeros(2, np.int64)
+        self._check_arg(self.lib.rf_region_offsets(self.ctx, int(slot), int(which), -1, ptr(out), None, None),
+                        "rf_region_offsets: no such band")
+        return int(out[0]), int(out[1])
+
+    def seq_regions(self, seq: int):
+        """rf_region_offsets of a sequence: ((offset, capacity) of its tables
+        and row codes in the table arena, (offset, capacity) of its bases in
+        the byte arena), in bytes.  Raises RifrafError for an unknown id."""
+        tabs, bases = np.zeros(2, np.int64), np.zeros(2, np.int64)
+        self._check_arg(self.lib.rf_region_offsets(self.ctx, -1, 0, int(seq), None, ptr(tabs), ptr(bases)),
+                        "rf_region_offsets: no such sequence")
+        return (int(tabs[0]), int(tabs[1])), (int(bases[0]), int(bases[1]))
+
+    @staticmethod
+    def _check_arg(rc: int, msg: str):
+        # the read-only record calls take a const context and leave no message
+        if rc != 0:
+            raise RifrafError(f"{msg} ({rc})")
+
     def last_score_launch(self):
         """The scorer launch of the last successful scoring call (a
         _lib.ScoreLaunch: kernel family, split mode, work items, grid.y)."""

@@ -39,6 +39,22 @@ def test_binding_signatures_cover_header():
     assert lib.rf_abi_version() == _lib.RF_ABI_VERSION
 
 
+def test_region_offsets_is_declared_and_bound():
+    """rf_region_offsets: an added, read-only call (the ABI version stays 1),
+    bound with its seven arguments and wrapped by two Engine methods."""
+    text = open(HEADER).read()
+    assert re.search(r"^int rf_region_offsets\(const rf_ctx \*ctx, int32_t slot, int32_t which, int32_t seq, "
+                     r"int64_t \*band, int64_t \*tabs,\s*int64_t \*bases\);", text, re.M)
+    assert re.search(r"#define RF_ABI_VERSION 1\b", text)
+    from rifraf_amd import _lib
+    from rifraf_amd.engine import Engine
+    assert len(_lib._SIGNATURES["rf_region_offsets"][1]) == 7
+    assert callable(Engine.band_region) and callable(Engine.seq_regions)
+    lib = _lib.load()
+    buf = (ctypes.c_int64 * 2)()
+    assert lib.rf_region_offsets(None, 0, 0, -1, buf, None, None) == -1     # RF_ERR_ARG without a context
+
+
 def test_no_device_is_loud():
     import torch
     if torch.cuda.is_available():
