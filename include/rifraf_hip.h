@@ -182,6 +182,41 @@ const char *rf_last_error(const rf_ctx *ctx);
                                    host filter and sort.  Same candidates, chosen lists
                                    and runs under both values (DESIGN.md §4 "Candidate
                                    selection" has the measurement behind the default)  */
+#define RF_OPT_PAIR_WIDE   36   /* the wide tier of the pair calls (rf_pair_scores,
+                                   rf_pair_align, rf_pair_align_smart, rf_pair_align_text,
+                                   rf_pair_errors, rf_pair_shifts): 0 (default): a band
+                                   of more than 5,114 rows is RF_ERR_ARG, as ever.  1: such
+                                   a pair runs in the wide tier (k_ps_wide / k_pa_wide /
+                                   k_pe_wide: the same cell recurrence with its four
+                                   anti-diagonals in device memory, one workgroup per
+                                   pair at a time), every other pair as before.  v >= 2:
+                                   also every pair whose band has at least v rows,
+                                   whichever tier it would take (for tests of the
+                                   tier at small shapes).  Same bits, moves and counts
+                                   as the other tiers.  With the option on, rf_pair_errors
+                                   counts its wide pairs in the fill (k_pe_wide); bands of
+                                   3,408 to 5,114 rows keep the trace route.  The
+                                   limits with the option on, checked before anything
+                                   runs (RF_ERR_ARG): a band of at most
+                                   RF_PAIR_WIDE_MAX_H rows, H + 2 m below 2^31 (the
+                                   int32 fields of a task), and for the calls that
+                                   keep a move trace fewer than 2^31 trace words per
+                                   pair (ceil(ceil((H + 2 m) / 2) / 16) blocks of H
+                                   rounded up to even: the lane walk's 32-bit index;
+                                   16 GiB of trace).  A trace or ring the device cannot
+                                   hold is RF_ERR_HIP from the allocation, as for
+                                   every buffer, and changes nothing               */
+#define RF_PAIR_WIDE_MAX_H (1 << 24)
+#define RF_OPT_PAIR_RING_MB 37  /* device bytes of the wide tier's rings per launch
+                                   set, MB (default 256).  A workgroup's ring is
+                                   4 (H + 6) doubles for the widest wide pair of the
+                                   set (12 instead of 8 bytes per entry in
+                                   rf_pair_errors); as many workgroups run as the
+                                   budget holds rings, at least one (0: exactly
+                                   one) and at most one per pair, and loop over the
+                                   pairs, longest first.  The ring memory is at most
+                                   max(budget, one ring), whatever npairs is
+                                   (rf_host_pair_wide_plan)                        */
 /* Keys 3, 5-8, 14 and 20 selected scorer variants measured slower and removed
    in round 3 (k_score_lean, the 128-lane k_score_ws, k_score_seg /
    k_score_segc, 16-diagonal k_score_segl, the unspecialised k_score_w2);
@@ -314,7 +349,8 @@ int rf_realign_jobs(rf_ctx *ctx, int32_t njobs, const int32_t *slot,
  * not fit the device and that nobody reads.  flags: 0 or RF_SKEW / RF_TRIM;
  * RF_FWD is implied and accepted, RF_BWD is RF_ERR_ARG.  Unknown ids, bw < 1
  * and a band of more than 5,114 rows (2 bw + |n - m| + 1: what the widest
- * pass holds in LDS) are RF_ERR_ARG.  Sequences come from any of the three
+ * pass holds in LDS) are RF_ERR_ARG; RF_OPT_PAIR_WIDE lifts the band limit for
+ * every pair call.  Sequences come from any of the three
  * upload calls, templates from rf_set_templates(_ids).  A pair the reference
  * raises on ("new score is invalid", align.jl:105-110) gets NaN and the call
  * still returns 0 (rf_score_dense's convention).  The call touches no slot,
@@ -939,6 +975,20 @@ int rf_host_score_plan(int32_t nreads, const int32_t *n, const int32_t *m, const
  * RF_ERR_ARG: an unknown family, nitems or max_reads below 1, a NULL output. */
 int rf_host_score_chunks(int32_t kernel, int32_t split, int32_t nitems, int32_t max_reads, int32_t score_wgs,
                          int32_t seg_wgs, int32_t *rchunk, int32_t *grid_y);
+
+/* The launch of a set's wide pair class (RF_OPT_PAIR_WIDE) on the host alone:
+ * no context, no GPU (csrc/rifraf_dp_plan.h pair_wide_plan).  H: the band rows
+ * of the class's npairs pairs; mode: 0 the score alone (rf_pair_scores), 1 with
+ * the move trace (rf_pair_align and its kin), 2 with the error count
+ * (rf_pair_errors); budget: bytes of ring (RF_OPT_PAIR_RING_MB << 20).
+ * Outputs, from 64-bit arithmetic: *ring_ld = max(H) + 6, the entries of one
+ * anti-diagonal; *nwg = the workgroups, max(1, min(npairs, budget / one)) for
+ * one = 4 ring_ld 8 bytes (mode 2: 4 ring_ld 12, the int32 counts behind the
+ * doubles); *ring_bytes = nwg * one, what BUF_PAIR_RING holds.  RF_ERR_ARG:
+ * npairs < 1, an H below 1 or above RF_PAIR_WIDE_MAX_H, an unknown mode, a
+ * negative budget, a NULL pointer. */
+int rf_host_pair_wide_plan(int64_t npairs, const int32_t *H, int32_t mode, int64_t budget, int64_t *nwg,
+                           int64_t *ring_ld, int64_t *ring_bytes);
 
 /* The row codes of rf_set_sequences on the host alone: no context, no GPU
  * (csrc/rifraf_seq_upload.h, DESIGN.md §4 "Sequence uploads").  nseq sequences

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <limits>
 #include <vector>
 
 #include "../../include/rifraf_hip.h"
@@ -312,26 +313,61 @@ inline DpPlan dp_plan(const std::vector<DPTask> &in, const std::vector<uint8_t> 
     return P;
 }
 
-// The tasks of one launch set in their six width classes, like rf_realign's:
+// The wide tier of the pair calls (RF_OPT_PAIR_WIDE; k_ps_wide, k_pa_wide,
+// k_pe_wide in rifraf_hip.hip): bands past DP_LDS_H, the four-anti-diagonal
+// ring in device memory.  A pair is wide when its band has at least
+// pair_wide_from(option) rows: never (0), from DP_LDS_H + 1 (1), or from v
+// rows (v >= 2, the tests' knob; DP_LDS_H + 1 at the latest).
+constexpr int PW_MAX_H = RF_PAIR_WIDE_MAX_H;   // widest band of the wide tier
+constexpr int PW_RING_MB = 256;                // RF_OPT_PAIR_RING_MB's default
+inline int pair_wide_from(int opt)
+{
+    return opt <= 0 ? std::numeric_limits<int>::max() : opt == 1 ? DP_LDS_H + 1 : std::min(opt, DP_LDS_H + 1);
+}
+
+// The launch of a set's wide class: npairs pairs (>= 1), the widest of hmax
+// rows, in fill mode `count` (the int32 count ring behind the score ring) or
+// not, within `budget` bytes of ring.  One workgroup holds a ring of 4 ring_ld
+// doubles (and as many int32), ring_ld = hmax + 6; as many workgroups run as
+// the budget holds rings, at least one and at most npairs, and loop over the
+// pairs.  So the ring takes at most max(budget, one ring) bytes whatever
+// npairs is.  Everything in int64.
+struct PairWidePlan {
+    int64_t nwg, ring_ld, ring_bytes;
+};
+inline PairWidePlan pair_wide_plan(int64_t npairs, int64_t hmax, bool count, int64_t budget)
+{
+    PairWidePlan p;
+    p.ring_ld = hmax + 6;
+    const int64_t one = 4 * p.ring_ld * (count ? 12 : 8);
+    p.nwg = std::max<int64_t>(1, std::min(npairs, budget / one));
+    p.ring_bytes = p.nwg * one;
+    return p;
+}
+
+// The tasks of one launch set in their seven width classes, like rf_realign's:
 // 0-2: H <= 31, 63, 127 as 16-lane tasks of 1, 2, 4 band-row pairs per lane;
 // 3: H <= DP_FAST_H as 64-lane tasks of 2 (k_dpr's wide class: 8 pairs per
 // lane in 16 lanes leave one wave per SIMD); 4, 5: the general tier in one
-// wave (H <= DP_GEN64_H) or DPW_NT threads.
+// wave (H <= DP_GEN64_H) or DPW_NT threads; 6: the wide tier, every pair of
+// at least wide_from rows whatever class it would else take.
 struct PairPlan {
-    std::vector<DPTask> cls[6], all;   // all: the classes in order, each longest first
-    size_t at[7];                      // class a is all[at[a] .. at[a + 1])
-    int hmax[2];                       // widest band of classes 4 and 5
+    std::vector<DPTask> cls[7], all;   // all: the classes in order, each longest first
+    size_t at[8];                      // class a is all[at[a] .. at[a + 1])
+    int hmax[3];                       // widest band of classes 4, 5 and 6
+    int wide_from = std::numeric_limits<int>::max();   // pair_wide_from(RF_OPT_PAIR_WIDE); clear() keeps it
 
     void clear()
     {
         for (auto &c : cls)
             c.clear();
-        hmax[0] = hmax[1] = 0;
+        hmax[0] = hmax[1] = hmax[2] = 0;
     }
     void add(const DPTask &t, bool finite)
     {
         // fast tier: k_dpr's lean condition, bands that live in registers
-        const int a = dp_lean(t, finite) && t.H <= DP_FAST_H ? dp_npi(t.H) : (t.H <= DP_GEN64_H ? 4 : 5);
+        const int a = t.H >= wide_from ? 6
+                      : dp_lean(t, finite) && t.H <= DP_FAST_H ? dp_npi(t.H) : (t.H <= DP_GEN64_H ? 4 : 5);
         cls[a].push_back(t);
         if (a >= 4)
             hmax[a - 4] = std::max(hmax[a - 4], t.H);
@@ -339,12 +375,12 @@ struct PairPlan {
     void finish()
     {
         all.clear();
-        for (int a = 0; a < 6; ++a) {
+        for (int a = 0; a < 7; ++a) {
             std::stable_sort(cls[a].begin(), cls[a].end(), [](const DPTask &x, const DPTask &y) { return x.klen > y.klen; });
             at[a] = all.size();
             all.insert(all.end(), cls[a].begin(), cls[a].end());
         }
-        at[6] = all.size();
+        at[7] = all.size();
     }
 };
 

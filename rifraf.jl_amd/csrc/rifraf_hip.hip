@@ -20,6 +20,8 @@
 //   k_pe / k_pe_gen  k_ps / k_ps_gen carrying count_errors of the path into
 //               each cell beside its score (rf_pair_errors): no trace, no walk
 //               src/align.jl:240-250, src/model.jl:643-672
+//   k_ps_wide / k_pa_wide / k_pe_wide  the three for bands past DPW_LDS_H
+//               (RF_OPT_PAIR_WIDE): the ring of anti-diagonals in device memory
 //   k_pa_emit   gapped texts, index maps and band tolerances from those moves
 //               (rf_pair_align_text)  src/align.jl:262-311,322-335
 //   k_pa_fix    frameshift correction from those moves (rf_pair_shifts): the
@@ -1885,6 +1887,177 @@ k_pe_gen(const DPTask *__restrict__ tasks, const uint8_t *__restrict__ bases,
          const double *__restrict__ tabs, double *__restrict__ out, int32_t *__restrict__ cnt, int ring_ld)
 {
     ps_gen_body<NT, NT == 64 ? PA_NPP64 : PE_NPPW, PS_COUNT>(tasks, bases, tabs, out, nullptr, cnt, ring_ld);
+}
+
+// ps_wide_body<MODE> (wide tier, RF_OPT_PAIR_WIDE): ps_gen_body's recurrence
+// for bands past DPW_LDS_H -- the same candidates in the same order, the same
+// strict '>' and FP64 sums, so the same bits, moves and counts -- with the
+// ring of four anti-diagonals in device memory, as k_dp<W, true, NT> keeps
+// it: one workgroup of DPW_NT threads per pair, thread q the diagonal pairs
+// q, q + DPW_NT, ... in a rolled loop (no bound on H but PW_MAX_H), a full
+// __syncthreads() per anti-diagonal (it orders the workgroup's global
+// stores).  The launch has nwg workgroups (pair_wide_plan: what the ring
+// budget holds) and workgroup b takes the pairs b, b + nwg, ... of the class,
+// which is sorted longest first; its ring is 4 ring_ld doubles at
+// gring + 4 ring_ld b and, with COUNT, as many int32 behind the nwg score
+// rings.  Before each pair the workgroup writes the 4 (H + 6) entries that the
+// pair reads -- -Inf and count 0 -- so nothing of the pair before is seen.
+// TRACE: a thread owns more diagonals than registers hold open words, so the
+// pair's trace is zeroed first (every word of every block is stored, cells
+// outside the DP as TRACE_NONE) and each cell ORs its nibble into its word in
+// place; a word belongs to one thread.  The pair's "new score is invalid" flag
+// is a word of LDS, the kernel's only LDS.
+// gfx950 (-Rpass-analysis=kernel-resource-usage): DESIGN.md §4 "Wide tier".
+template <int MODE>
+__device__ __forceinline__ void ps_wide_body(const DPTask *__restrict__ tasks, int ntasks,
+                                             const uint8_t *__restrict__ bases, const double *__restrict__ tabs,
+                                             double *__restrict__ out, uint64_t *trace, int32_t *__restrict__ cnt,
+                                             double *gring, int ring_ld)
+{
+    constexpr bool TRACE = MODE == PS_TRACE, COUNT = MODE == PS_COUNT;
+    constexpr int NT = DPW_NT;
+    __shared__ int raised;
+    const int q = threadIdx.x;
+    double *ring = gring + (size_t)blockIdx.x * 4 * ring_ld;
+    int *cring = (int *)(gring + (size_t)gridDim.x * 4 * ring_ld) + (size_t)blockIdx.x * 4 * ring_ld;
+    for (int t = blockIdx.x; t < ntasks; t += gridDim.x) {
+        const DPTask T = tasks[t];
+        const int ld = T.H + 6;   // <= ring_ld
+        for (int e = q; e < 4 * ld; e += NT) {
+            ring[e] = -RF_INF;
+            if constexpr (COUNT)
+                cring[e] = 0;
+        }
+        // the pair's trace from the thread's first diagonal on (a pointer in vector registers)
+        uint64_t *tr = TRACE ? trace + T.band + 2 * q : nullptr;
+        if constexpr (TRACE) {
+            // fewer than 2^31 words: the host refuses a longer trace (pair_band_fault)
+            const unsigned words = (unsigned)T.pad * (unsigned)T.P;
+            for (unsigned e = q; e < words; e += NT)
+                tr[(int)e - 2 * q] = 0;
+        }
+        if (q == 0)
+            raised = 0;
+        __syncthreads();
+        const uint8_t *sbase = bases + T.sb;
+        const uint8_t *tbase = bases + T.tb;
+        const double *tb = tabs + T.tab;
+        // the tables by offset from tb and the ring rows by offset from ring / cring:
+        // one scalar register each where a pointer takes two
+        const size_t nn = (size_t)T.n;
+        bool bad = false;    // "new score is invalid" in a cell of this thread
+        double fval = 0.0;   // the final cell (the thread that computes it)
+        bool fset = false;
+        int fcnt = 0;        // COUNT: the error count of the final cell's path
+
+        for (int k = 0; k < T.klen; ++k) {
+            const int par = k & 1;
+            const int o0 = (k & 3) * ld + 3, o1 = ((k - 1) & 3) * ld + 3;
+            const int o2 = ((k - 2) & 3) * ld + 3, o3 = ((k - 3) & 3) * ld + 3;
+            for (int pp = q;; pp += NT) {
+                const int d = 2 * pp + par;
+                if (d >= T.H || d > k)
+                    break;
+                const int jj = (k - d) >> 1;
+                double v = -RF_INF;
+                int mv = 0;   // dead in PS_SCORE
+                int ce = 0;   // COUNT: the count of the chosen predecessor plus the move's cost
+                const int ii = d + jj - T.c;
+                if (jj <= T.m && ii >= 0 && ii <= T.n) {
+                    if (ii == 0 && jj == 0) {
+                        v = 0.0;
+                    } else {
+                        // align.jl:64-76 score lookups
+                        const int sb = ii >= 1 ? sbase[ii - 1] : 4;
+                        const int tbb = jj >= 1 ? tbase[jj - 1] : 4;
+                        const int ks = max(ii - 1, 0);
+                        double ms = tb[(sb == tbb ? 0 : nn) + ks];
+                        double is = tb[2 * nn + ks];
+                        const double ds = tb[3 * nn + ii];
+                        if ((T.flags & 2) && sb != tbb)
+                            ms *= 0.99;
+                        if ((T.flags & 4) && (jj == 0 || jj == T.m))
+                            is = 0.0;
+                        // align.jl:77-104, strict '>' in reference order
+                        double best = -RF_INF, s;
+                        s = ring[o2 + d] + ms;
+                        if (s > best) { best = s; mv = 1; }
+                        s = ring[o1 + d - 1] + is;
+                        if (s > best) { best = s; mv = 2; }
+                        s = ring[o1 + d + 1] + ds;
+                        if (s > best) { best = s; mv = 3; }
+                        if (T.ncins > 0 && ii >= 3) {
+                            s = ring[o3 + d - 3] + tb[4 * nn + 1 + (ii - 3)];
+                            if (s > best) { best = s; mv = 4; }
+                        }
+                        if (T.ncdel > 0 && jj >= 3) {
+                            s = ring[o3 + d + 3] + tb[4 * nn + 1 + T.ncins + ii];
+                            if (s > best) { best = s; mv = 5; }
+                        }
+                        bad = bad || best == -RF_INF;   // "new score is invalid"
+                        v = best;
+                        if constexpr (COUNT) {
+                            // count_errors (align.jl:240-245) of the path into the cell, as k_pa_walk counts it
+                            switch (mv) {
+                            case 1: ce = cring[o2 + d] + (sb != tbb ? 1 : 0); break;
+                            case 2: ce = cring[o1 + d - 1] + 1; break;
+                            case 3: ce = cring[o1 + d + 1] + 1; break;
+                            case 4: ce = cring[o3 + d - 3] + 3; break;
+                            case 5: ce = cring[o3 + d + 3] + 3; break;
+                            default: break;
+                            }
+                        }
+                    }
+                    if (ii == T.n && jj == T.m) {
+                        fval = v;
+                        fset = true;
+                        fcnt = ce;
+                    }
+                }
+                ring[o0 + d] = v;
+                if constexpr (COUNT)
+                    cring[o0 + d] = ce;
+                if constexpr (TRACE)
+                    if (mv != 0)
+                        tr[(k >> 5) * T.P + (d - 2 * q)] |= (uint64_t)mv << (4 * ((k >> 1) & 15));
+            }
+            __syncthreads();
+        }
+        // NaN for a pair the reference raises on; the flag is reset before the next pair
+        if (bad)
+            raised = 1;
+        __syncthreads();
+        if (fset) {
+            const bool nan = raised != 0;
+            const int oi = tasks[t].out_idx;
+            out[oi] = nan ? __builtin_nan("") : fval;
+            if constexpr (COUNT)
+                cnt[oi] = nan ? -1 : fcnt;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(DPW_NT)
+k_ps_wide(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+          const double *__restrict__ tabs, double *__restrict__ out, double *gring, int ring_ld)
+{
+    ps_wide_body<PS_SCORE>(tasks, ntasks, bases, tabs, out, nullptr, nullptr, gring, ring_ld);
+}
+
+__global__ void __launch_bounds__(DPW_NT)
+k_pa_wide(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+          const double *__restrict__ tabs, double *__restrict__ out, uint64_t *trace, double *gring, int ring_ld)
+{
+    ps_wide_body<PS_TRACE>(tasks, ntasks, bases, tabs, out, trace, nullptr, gring, ring_ld);
+}
+
+__global__ void __launch_bounds__(DPW_NT)
+k_pe_wide(const DPTask *__restrict__ tasks, int ntasks, const uint8_t *__restrict__ bases,
+          const double *__restrict__ tabs, double *__restrict__ out, int32_t *__restrict__ cnt, double *gring,
+          int ring_ld)
+{
+    ps_wide_body<PS_COUNT>(tasks, ntasks, bases, tabs, out, nullptr, cnt, gring, ring_ld);
 }
 
 __global__ void __launch_bounds__(64)
@@ -5821,6 +5994,9 @@ enum Buf : int {
     BUF_CAND_OUT,
     BUF_CAND_TABLE,    // rf_candidates_table: the caller's table
     BUF_CAND_CONS,     // rf_candidates_table: the caller's consensus bases
+    // the wide pair class of one launch set (RF_OPT_PAIR_WIDE): its workgroups'
+    // rings of four anti-diagonals, the scores and behind them k_pe_wide's counts
+    BUF_PAIR_RING,
     BUF_COUNT
 };
 
@@ -5905,6 +6081,8 @@ struct Opts : DpOpts, ScoreOpts {
     int pair_trace_mb = PA_TRACE_MB;   // RF_OPT_PAIR_TRACE_MB: MB of move trace per launch set of rf_pair_align
     int pair_walk = 0;                 // RF_OPT_PAIR_WALK: 0 auto, 1 k_pa_walk (lane per pair), 2 k_pa_walk_w (wave per pair)
     int cand_device = 0;    // RF_OPT_CAND_DEVICE: 1 = the native driver selects and chooses candidates with rf_candidates
+    int pair_wide = 0;      // RF_OPT_PAIR_WIDE: 0 bands past DPW_LDS_H refused, 1 in the wide tier, v >= 2 also every band of >= v rows
+    int pair_ring_mb = PW_RING_MB;   // RF_OPT_PAIR_RING_MB: MB of the wide tier's rings per launch set (0: one workgroup)
 };
 
 }  // namespace
@@ -6605,6 +6783,8 @@ static int *opt_slot(rf_ctx *ctx, int32_t key)
     case RF_OPT_PAIR_TRACE_MB: return &o.pair_trace_mb;
     case RF_OPT_PAIR_WALK: return &o.pair_walk;
     case RF_OPT_CAND_DEVICE: return &o.cand_device;
+    case RF_OPT_PAIR_WIDE: return &o.pair_wide;
+    case RF_OPT_PAIR_RING_MB: return &o.pair_ring_mb;
     default: return dp_opt(o, key);   // the DP launch planner's
     }
 }
@@ -7676,6 +7856,28 @@ static std::string band_too_wide(const std::string &fn, int64_t H, int64_t k, in
            std::to_string(DPW_LDS_H) + (k >= 0 ? " a bandless" : " a score-only") + " pass holds in LDS";
 }
 
+// The band check of one pair: H rows (at bandwidth mb where that is not the
+// call's own) against template length m.  Without RF_OPT_PAIR_WIDE the LDS
+// limit; with it the wide tier's limits (include/rifraf_hip.h).  Empty: fits.
+static std::string pair_band_fault(const rf_ctx *ctx, const std::string &fn, PairCall call, int64_t H, int64_t m,
+                                   int64_t k, int64_t mb = -1)
+{
+    const bool align = call != PairCall::Scores;
+    if (H <= DPW_LDS_H)
+        return {};
+    if (ctx->opt.pair_wide <= 0)
+        return band_too_wide(fn, H, align ? k : -1, mb);
+    const std::string who = fn + ": band of " + std::to_string(H) + " rows (pair " + std::to_string(k) + ")";
+    if (H > PW_MAX_H)
+        return who + " is wider than the " + std::to_string(PW_MAX_H) + " the wide tier takes";
+    if (H + 2 * m > INT32_MAX)
+        return who + ": H + 2 m does not fit 32 bits";
+    // the lane walk indexes a pair's trace words with 32 bits
+    if (call == PairCall::Align && (int64_t)pa_blocks((int)(H + 2 * m)) * pa_hp((int)H) > INT32_MAX)
+        return who + ": its move trace has 2^31 words or more";
+    return {};
+}
+
 // Argument, flag and per-pair checks.  `fn` names the entry point in the
 // messages; `outs_ok` is its check of its own output pointers; `call` gives
 // the wording (rf_pair_errors takes rf_pair_align's) and the timers that are
@@ -7705,10 +7907,18 @@ static int pair_check(rf_ctx *ctx, const std::string &fn, PairCall call, bool ou
         if (bw[k] < 1)
             return fail(ctx, RF_ERR_ARG, "bandwidth must be positive");
         const int64_t H = 2 * (int64_t)bw[k] + std::abs((int64_t)ctx->seqs[seq[k]].n - ctx->tpls[tpl[k]].m) + 1;
-        if (H > DPW_LDS_H)
-            return fail(ctx, RF_ERR_ARG, band_too_wide(fn, H, align ? k : -1));
+        const std::string why = pair_band_fault(ctx, fn, call, H, ctx->tpls[tpl[k]].m, k);
+        if (!why.empty())
+            return fail(ctx, RF_ERR_ARG, why);
     }
     return 0;
+}
+
+// The wide class of a plan under the context's ring budget (RF_OPT_PAIR_RING_MB)
+static PairWidePlan pair_wide_ring(const rf_ctx *ctx, const PairPlan &pl, bool count)
+{
+    return pair_wide_plan((int64_t)pl.cls[6].size(), pl.hmax[2], count,
+                          (int64_t)std::max(ctx->opt.pair_ring_mb, 0) << 20);
 }
 
 // The fill launches of a plan whose tasks are in BUF_PAIR_TASKS: k_pa* into
@@ -7765,7 +7975,41 @@ static int pair_fill(rf_ctx *ctx, const PairPlan &pl, double *d_out, uint64_t *d
                 hipLaunchKernelGGL(k_ps_gen<DPW_NT>, dim3(n), dim3(DPW_NT), lds, ctx->stream, tk, d_bases, d_tabs,
                                    d_out, ld);
         }
+    if (const int n = (int)pl.cls[6].size()) {
+        // the wide tier: the workgroups the ring budget holds loop over the class (BUF_PAIR_RING: pair_stage)
+        const PairWidePlan wp = pair_wide_ring(ctx, pl, d_cnt != nullptr);
+        const DPTask *tk = d_tasks + pl.at[6];
+        double *d_ring = dev<double>(ctx, BUF_PAIR_RING);
+        const dim3 grid((unsigned)wp.nwg);
+        if (d_tr)
+            hipLaunchKernelGGL(k_pa_wide, grid, dim3(DPW_NT), 0, ctx->stream, tk, n, d_bases, d_tabs, d_out, d_tr,
+                               d_ring, (int)wp.ring_ld);
+        else if (d_cnt)
+            hipLaunchKernelGGL(k_pe_wide, grid, dim3(DPW_NT), 0, ctx->stream, tk, n, d_bases, d_tabs, d_out, d_cnt,
+                               d_ring, (int)wp.ring_ld);
+        else
+            hipLaunchKernelGGL(k_ps_wide, grid, dim3(DPW_NT), 0, ctx->stream, tk, n, d_bases, d_tabs, d_out, d_ring,
+                               (int)wp.ring_ld);
+    }
     HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+int rf_host_pair_wide_plan(int64_t npairs, const int32_t *H, int32_t mode, int64_t budget, int64_t *nwg,
+                           int64_t *ring_ld, int64_t *ring_bytes)
+{
+    if (npairs < 1 || !H || mode < PS_SCORE || mode > PS_COUNT || budget < 0 || !nwg || !ring_ld || !ring_bytes)
+        return RF_ERR_ARG;
+    int32_t hmax = 0;
+    for (int64_t k = 0; k < npairs; ++k) {
+        if (H[k] < 1 || H[k] > PW_MAX_H)
+            return RF_ERR_ARG;
+        hmax = std::max(hmax, H[k]);
+    }
+    const PairWidePlan p = pair_wide_plan(npairs, hmax, mode == PS_COUNT, budget);
+    *nwg = p.nwg;
+    *ring_ld = p.ring_ld;
+    *ring_bytes = p.ring_bytes;
     return 0;
 }
 
@@ -7852,6 +8096,9 @@ static int pair_stage(rf_ctx *ctx, const PairSet &s, const PairLanding &L, const
     }
     if (w.walk || w.count)
         if (int e = ensure_buf(ctx, b[BUF_PAIR_COUNTS], L.counts))
+            return e;
+    if (!s.pl.cls[6].empty())
+        if (int e = ensure_buf(ctx, b[BUF_PAIR_RING], (size_t)pair_wide_ring(ctx, s.pl, w.count).ring_bytes))
             return e;
     if (w.want_txt) {
         if (int e = ensure_buf(ctx, b[BUF_PAIR_TEXT_T], L.mv_dev))
@@ -8071,6 +8318,7 @@ static int pair_sets(rf_ctx *ctx, const PairIo &io, const PairWants &w, const Pa
     const int64_t chunk = std::max(ctx->opt.pair_chunk, 1);
     const int64_t budget = (int64_t)std::max(ctx->opt.pair_trace_mb, 1) << 20;   // bytes of trace per set
     PairSet s;
+    s.pl.wide_from = pair_wide_from(ctx->opt.pair_wide);
     for (int64_t p0 = 0; p0 < io.nidx; p0 += s.cn) {
         const int64_t p1 = pair_set_end(p0, io.nidx, chunk, w.trace, budget, [&](int64_t i) {
             const int64_t k = io.at(i);
@@ -8106,7 +8354,7 @@ static int pair_sets(rf_ctx *ctx, const PairIo &io, const PairWants &w, const Pa
 // which are downloaded only if io.moves asks for them.
 //
 // With io.errors (rf_pair_errors) the pairs whose band is within DP_COUNT_H
-// run first, in sets of their own, through the counting fills (k_pe*): no
+// (and the wide tier's, RF_OPT_PAIR_WIDE) run first, in sets of their own, through the counting fills (k_pe*): no
 // trace, no walk, sets by the chunk alone.  The pairs above it follow through
 // the trace fill and the walk.
 static int pair_run(rf_ctx *ctx, const PairIo &io, bool trace, bool walk, const PairEnded &ended)
@@ -8123,7 +8371,8 @@ static int pair_run(rf_ctx *ctx, const PairIo &io, bool trace, bool walk, const 
     for (int64_t i = 0; i < io.nidx; ++i) {
         const int64_t k = io.at(i);
         const int H = band_rows(ctx->seqs[io.seq[k]].n + 1, ctx->tpls[io.tpl[k]].m + 1, io.bw[k]);
-        part[H > DP_COUNT_H].push_back(k);
+        // a wide pair (RF_OPT_PAIR_WIDE) carries its count in k_pe_wide, whatever its width
+        part[H > DP_COUNT_H && H < pair_wide_from(ctx->opt.pair_wide)].push_back(k);
     }
     for (int g = 0; g < 2; ++g) {
         if (part[g].empty())
@@ -8228,8 +8477,9 @@ static int pair_smart_run(rf_ctx *ctx, const std::string &fn, bool outs_ok, int6
         // model.jl:648-651
         const int64_t mb = (fixed && fixed[k]) ? bw[k] : std::min({(int64_t)bw[k] << max_doublings, m, n});
         const int64_t H = 2 * mb + std::abs(n - m) + 1;
-        if (H > DPW_LDS_H)
-            return fail(ctx, RF_ERR_ARG, band_too_wide(fn, H, k, mb));
+        const std::string why = pair_band_fault(ctx, fn, errors ? PairCall::Errors : PairCall::Align, H, m, k, mb);
+        if (!why.empty())
+            return fail(ctx, RF_ERR_ARG, why);
         cur[(size_t)k] = bw[k];
         maxbw[(size_t)k] = (int32_t)mb;
     }

@@ -41,7 +41,8 @@ def __getattr__(name):
         return getattr(assign, name)
     if name in ("align_moves_many", "align_many", "smart_align_moves_many", "smart_align_many", "edit_distances",
                 "correct_shifts_many", "align_indices_many", "band_tolerances", "count_errors_many",
-                "smart_bandwidths_many", "single_indel_proposals_many", "has_single_indels_many"):
+                "smart_bandwidths_many", "single_indel_proposals_many", "has_single_indels_many",
+                "calibrate_phreds_many"):
         from . import pairalign
         return getattr(pairalign, name)
     if name in ("sample_sequences", "sample_mixture", "sample_from_template", "sample_reference",

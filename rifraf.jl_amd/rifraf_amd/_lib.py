@@ -94,6 +94,7 @@ _SIGNATURES = {
                                    c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, POINTER(c_int32),
                                    c_void_p, c_void_p]),
     "rf_host_score_chunks": (c_int, [c_int32] * 6 + [POINTER(c_int32), POINTER(c_int32)]),
+    "rf_host_pair_wide_plan": (c_int, [c_int64, c_void_p, c_int32, c_int64] + [POINTER(c_int64)] * 3),
     "rf_last_score_launch": (c_int, [c_void_p, c_void_p]),
     "rf_host_row_codes": (c_int, [c_int32] + [c_void_p] * 6 + [c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 6),
     "rf_host_upload_chunks": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p,
@@ -112,7 +113,7 @@ OPTIONS = {"score_mode": 1, "score_kernel": 2, "lean_lds_kb": 4, "dp_psplit": 10
            "band_pad": 17, "dp_wide": 18, "aln_sums_host": 19,
            "aln_marks_min": 22, "sync_block": 23, "dp_nl64": 24, "dp_lat": 26,
            "score_wgs": 27, "seg_wgs": 28, "dp_pfit": 29, "dp_mc": 30, "bt_nw": 31, "pair_chunk": 32,
-           "pair_trace_mb": 33, "pair_walk": 34, "cand_device": 35}
+           "pair_trace_mb": 33, "pair_walk": 34, "cand_device": 35, "pair_wide": 36, "pair_ring_mb": 37}
 # symbolic values of the enum-like options
 OPTION_VALUES = {"score_mode": {"auto": 0, "fused": 1, "split": 2},
                  "score_kernel": {"auto": 0, "general": 1, "seg": 2, "ws": 3},
@@ -256,6 +257,25 @@ def host_score_chunks(kernel, split, nitems, max_reads, score_wgs=2048, seg_wgs=
     if rc != 0:
         raise ValueError(f"rf_host_score_chunks: bad arguments ({rc})")
     return rchunk.value, grid_y.value
+
+
+PAIR_WIDE_MAX_H = 1 << 24   # RF_PAIR_WIDE_MAX_H: the widest band of the pair calls' wide tier
+PAIR_WIDE_MODES = ("score", "trace", "count")   # rf_host_pair_wide_plan's modes, by value
+PairWidePlan = namedtuple("PairWidePlan", "nwg ring_ld ring_bytes")
+
+
+def host_pair_wide_plan(H, mode, budget):
+    """rf_host_pair_wide_plan: the workgroups, the ring's row length and its
+    bytes for a launch set's wide pairs of H[k] band rows in fill mode `mode`
+    (a PAIR_WIDE_MODES name) within `budget` bytes of ring, on the host alone
+    (no context, no GPU).  Python ints from the call's int64."""
+    H = np.ascontiguousarray(H, np.int32)
+    out = [c_int64(), c_int64(), c_int64()]
+    rc = load().rf_host_pair_wide_plan(len(H), ptr(H), PAIR_WIDE_MODES.index(mode), int(budget),
+                                       *(ctypes.byref(o) for o in out))
+    if rc != 0:
+        raise ValueError(f"rf_host_pair_wide_plan: bad arguments ({rc})")
+    return PairWidePlan(*(o.value for o in out))
 
 
 RF_CODES = 65536   # entries of the row codes' dictionary, per kind
