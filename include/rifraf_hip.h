@@ -36,6 +36,9 @@
  *                        estimate_probs  src/model.jl:385-399,499-526,737-791
  *                        (per-sequence: score_nocodon :242-285 / codon
  *                        score_proposal :302-383 / seq_score_deletion :227-236)
+ *   rf_score_dense_from <- the same left fold over the batch, continued from
+ *                        a table of earlier reads' totals
+ *                        src/model.jl:385-399
  *   rf_candidates     <- get_candidates' filter and choose_candidates over
  *                        the dense table, on the device
  *                        src/model.jl:499-526, src/proposals.jl:104-115
@@ -613,6 +616,43 @@ int rf_score_dense_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off,
 int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off,
                        const int32_t *slots, const int32_t *ref_slot, double *out);
 
+/* Dense scoring that continues a fold.  score_proposal's sum over the batch
+ * (model.jl:385-399) is a plain left fold in read order, so it can be cut
+ * anywhere and continued exactly: with init[e] the fold of reads 1..k-1,
+ *   out[e] = ((init[e] + s_k) + s_{k+1}) + ... + s_R   (folded in batch order)
+ * has the bits of the one-shot fold over reads 1..R.  A cluster of any depth
+ * can so be scored chunk by chunk with only one chunk's bands on the device.
+ * Layout, groups, slots, checks, stale-band refusals and messages are
+ * rf_score_dense's; init and out both hold sum_g (m_g + 1) * 9 doubles in
+ * that call's row layout.  out may be NULL: the totals stay on the device.
+ * A group without reads stays RF_ERR_ARG (its template, and so its row count,
+ * is not known without a slot).
+ * init == NULL starts at 0.0: the call is then rf_score_dense (ref_slot NULL
+ * or all -1) or rf_score_dense_ref, bit for bit.
+ * ref_slot may be NULL (no reference term) or hold one entry per group (-1:
+ * none); ref_slot[g] >= 0 adds s_ref last, after the reads of this call, as
+ * rf_score_dense_ref does and with its checks.  A caller that chunks a
+ * cluster passes the reference with the last chunk only.
+ * NaN: a NaN in init stays NaN.  Each read's own term is made NaN where
+ * rf_score_dense makes it NaN (Sub/Del of p = 0, a failed update, a -Inf
+ * sum) before it is added -- the rule is applied per read, never to the
+ * folded total -- so a chunked fold has NaN exactly where the one-shot fold
+ * has.
+ * A refused call changes nothing, out included.  rf_last_timing and
+ * rf_last_score_launch report the call like any dense call (the upload of
+ * init lies before the scorer's events); the launch plan is the one
+ * rf_score_dense caches, so a chunk loop over one slot list plans once.
+ * An added call: the ABI version stays 1. */
+int rf_score_dense_from(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
+                        const int32_t *ref_slot, const double *init, double *out);
+
+/* rf_score_dense_from with init and the totals in DEVICE memory of the
+ * context's device.  dev_init may be NULL (start at 0.0); dev_out must not be
+ * (RF_ERR_ARG).  The two may be the same buffer: the table then accumulates
+ * in place. */
+int rf_score_dense_from_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
+                            const int32_t *ref_slot, const double *dev_init, double *dev_out);
+
 /* Candidate selection on the device: the iteration loop's get_candidates ->
  * choose_candidates (model.jl:499-526, proposals.jl:104-115) for many groups
  * (clusters) at once, without the proposal list, the mask or the totals
@@ -929,6 +969,34 @@ int rf_last_dp_launches(const rf_ctx *ctx, int32_t cap, int32_t *launches, int32
 int rf_region_offsets(const rf_ctx *ctx, int32_t slot, int32_t which, int32_t seq, int64_t *band, int64_t *tabs,
                       int64_t *bases);
 
+/* The bytes one slot's A band plus B band take in the band arena, on the host
+ * alone: no context, no GPU.  For a read of n bases against a template of m
+ * at bandwidth bw, filled by an rf_realign call that pads its bands to whole
+ * 128-B lines (pad != 0: the call's widest band has H >= RF_OPT_BAND_PAD) or
+ * does not (pad = 0).  H = 2 bw + |n - m| + 1 band rows, row stride
+ * P = ((H + 1) >> 1) | 1 doubles (padded: (H + 1) >> 1 rounded up to 16),
+ * H + 2 m kappa rows, each band's region rounded up to 256 bytes: computed by
+ * the code the arena allocates with (csrc/rifraf_dp_plan.h), so it equals the
+ * two capacities rf_region_offsets reports after a fill into fresh slots.  A
+ * planner that cuts a deep cluster into chunks of a fixed band budget sums
+ * it.  -1: n < 1, m < 0 or bw < 0.  An added call: the ABI version stays 1.
+ * Engine-internal; no reference counterpart. */
+int64_t rf_host_band_bytes(int32_t n, int32_t m, int32_t bw, int32_t pad);
+
+/* The band arena against a budget.  rf_band_arena_bytes: the capacity in
+ * bytes of the context's band arena now (0 before the first fill or
+ * rf_reserve; it never shrinks).  rf_host_reserve_fit, on the host alone (no
+ * context, no GPU): the largest band_bytes for which rf_reserve on a context
+ * whose band arena is still empty allocates an arena of at most `budget`
+ * bytes -- rf_reserve adds the arena's guards and a growth margin of an eighth
+ * plus 1 MiB and rounds to whole MiB, and this inverts that arithmetic with
+ * the code that does it -- or -1 when even rf_reserve(0) allocates more (a
+ * budget below 2 MiB).  Bands of that many bytes (rf_host_band_bytes) then fit
+ * the reserved arena without growing it.  Added calls: the ABI version stays
+ * 1.  Engine-internal; no reference counterpart. */
+int64_t rf_band_arena_bytes(const rf_ctx *ctx);
+int64_t rf_host_reserve_fit(int64_t budget);
+
 /* The scoring planner made observable (DESIGN.md §4 "Scoring planner"), for
  * the same reason: the three scorers, fused and split mode and both item
  * widths compute the same bits.  No reference counterpart. */
@@ -937,7 +1005,8 @@ int rf_region_offsets(const rf_ctx *ctx, int32_t slot, int32_t which, int32_t se
 #define RF_SCK_WS           3   /* k_score_ws: finite tables, 256 columns per item      */
 #define RF_SCL_FIELDS       4
 /* The scorer launch of the context's last successful rf_score, rf_score_dense,
- * rf_score_dense_dev, rf_score_dense_ref or rf_qv_probs, as RF_SCL_FIELDS
+ * rf_score_dense_dev, rf_score_dense_ref, rf_score_dense_from(_dev) or
+ * rf_qv_probs, as RF_SCL_FIELDS
  * int32: kernel family (RF_SCK_*), split mode (0 / 1), work items, grid.y (0
  * items: nothing was launched, grid.y 0). */
 int rf_last_score_launch(const rf_ctx *ctx, int32_t *launch);

@@ -31,6 +31,18 @@ inline int band_stride(int H, int pad_h)
     return (pad_h > 0 && H >= pad_h) ? (((H + 1) >> 1) + 15) & ~15 : band_P(H);
 }
 RF_HD inline int64_t band_K(int H, int m) { return (int64_t)H + 2 * (int64_t)m; }
+// What a band takes in the band arena: K kappa rows of P doubles, in a region
+// rounded as every arena region is (region_ensure).  rf_realign's bookkeeping
+// and rf_host_band_bytes both come here.
+inline int64_t band_payload_bytes(int H, int m, int P) { return band_K(H, m) * P * 8; }
+inline int64_t region_bytes(int64_t bytes) { return (std::max<int64_t>(bytes, 16) + 255) / 256 * 256; }
+// One band of an (n+1) x (m+1) alignment at bandwidth bw, padded (the call's
+// RF_OPT_BAND_PAD decision) or not; A and B are alike
+inline int64_t band_region_bytes(int n, int m, int bw, bool pad)
+{
+    const int H = band_rows(n + 1, m + 1, bw);
+    return region_bytes(band_payload_bytes(H, m, band_stride(H, pad ? 1 : 0)));
+}
 
 // One DP fill task = (slot, direction).
 struct alignas(16) DPTask {

@@ -3300,6 +3300,10 @@ __device__ __forceinline__ void score_half(int p, int m, const ScoreRead &R,
 // Insertions.  grid.x = work items (group, chunk of SCORE_C positions);
 // grid.y = read index in split mode.  Fused mode folds all reads of the
 // group in batch order.  lds_elems: doubles the dynamic LDS holds per band.
+// INIT (fused launches of rf_score_dense_from): the fold continues from the
+// totals already in `dense` instead of starting at 0.0.  A compile-time
+// flag: the <false> instance has the code the kernel had without it.
+template <bool INIT>
 __global__ void __launch_bounds__(128)
 k_score(const WorkItem *__restrict__ items, const ScoreGroup *__restrict__ groups,
         const ScoreRead *__restrict__ reads, const uint8_t *__restrict__ bases,
@@ -3323,6 +3327,14 @@ k_score(const WorkItem *__restrict__ items, const ScoreGroup *__restrict__ group
 #pragma unroll
     for (int k = 0; k < 5; ++k)
         tot[k] = 0.0;
+    if (INIT && !split_mode && p <= G.m) {
+        // the lane's own slots of the resident table, once, before the reads
+        const double *src = dense + G.dense_off + (size_t)p * 9 + (half ? 5 : 0);
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            if (k < 4 || half == 0)
+                tot[k] = src[k];
+    }
     double *sA = smem;
     double *sB = smem + lds_elems;
     const int k0 = 2 * (w.p0 - 1);                    // window's first kappa row
@@ -3399,6 +3411,9 @@ k_score(const WorkItem *__restrict__ items, const ScoreGroup *__restrict__ group
 }
 
 // split mode: ordered fold over reads, one lane per (group position slot).
+// INIT (rf_score_dense_from): the fold starts from the slot's value already
+// in `dense` -- the first add is init + v[0] -- instead of 0.0.
+template <bool INIT>
 __global__ void k_reduce(const ScoreGroup *__restrict__ groups, int ngroups,
                          const int64_t *__restrict__ gstart, int64_t total,
                          const double *__restrict__ split, double *__restrict__ dense)
@@ -3422,7 +3437,7 @@ __global__ void k_reduce(const ScoreGroup *__restrict__ groups, int ngroups,
     const int nr = G.r1 - G.r0;
     // the left fold in read order (model.jl:389-393); 16 partials are loaded
     // before they are added, so each lane keeps 16 streaming loads in flight
-    double acc = 0.0;
+    double acc = INIT ? dense[G.dense_off + local] : 0.0;
     int r = 0;
     for (; r + 16 <= nr; r += 16) {
         double v[16];
@@ -3785,7 +3800,9 @@ __device__ __forceinline__ void wg_barrier()
 #define WS_CODES 1   // loaders read row-coded reads' tables through the code dictionary
 #endif
 
-template <int NPF, int Q>
+// INIT (fused launches of rf_score_dense_from): the chain waves' totals start
+// from the values already in `dense` instead of 0.0 (a compile-time flag).
+template <int NPF, int Q, bool INIT = false>
 __global__ void __launch_bounds__(2 * Q)
 k_score_ws(const WorkItem *__restrict__ items, const ScoreGroup *__restrict__ groups,
            const ScoreRead *__restrict__ reads, const uint8_t *__restrict__ bases,
@@ -3970,6 +3987,21 @@ k_score_ws(const WorkItem *__restrict__ items, const ScoreGroup *__restrict__ gr
         tI[k] = 0.0;
         tS[k] = 0.0;
     }
+    if (INIT && !(split_mode & 1) && a <= m) {
+        // the slots this lane emits (5-8 of position a, 0-4 of a + 1): one
+        // run of 9 doubles per lane, consecutive across the wave, read once
+        // before the first read's barrier
+        const double *src = dense + G.dense_off + (size_t)a * 9;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            tI[k] = src[5 + k];
+        if (a < m) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                tS[k] = src[9 + k];
+            tD = src[13];
+        }
+    }
     const double qnan = __builtin_nan("");
     // one position's 9 totals (fused: the group's fold; split: read r's
     // partial, 0.0 + its own sums, and the running values restart at 0.0)
@@ -4064,10 +4096,12 @@ struct SeglGeo {
     static constexpr int NT = S + 65;   // table rows: i - ib in [0, S + 65)
 };
 
-template <int SEGS>
 #ifndef SEGL_WPE
 #define SEGL_WPE 1
 #endif
+// INIT (fused launches of rf_score_dense_from): the lane's totals start from
+// the values already in `dense` instead of 0.0 (a compile-time flag).
+template <int SEGS, bool INIT = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SEGL_WPE)))
 k_score_segl(const WorkItem *__restrict__ items, const ScoreGroup *__restrict__ groups,
              const ScoreRead *__restrict__ reads, const uint8_t *__restrict__ bases,
@@ -4109,6 +4143,20 @@ k_score_segl(const WorkItem *__restrict__ items, const ScoreGroup *__restrict__ 
     for (int k = 0; k < 4; ++k) {
         tI[k] = 0.0;
         tS[k] = 0.0;
+    }
+    if (INIT && !(split_mode & 1) && active) {
+        // the slots this lane writes at the end (5-8 of position a, 0-4 of
+        // a + 1): 9 doubles per lane, consecutive across the wave, read once
+        const double *src = dense + G.dense_off + (size_t)a * 9;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            tI[k] = src[5 + k];
+        if (hasS) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                tS[k] = src[9 + k];
+            tD = src[13];
+        }
     }
     const bool all_act = __all(active) && wave_s;
     // aligned-row loader lane roles: row r8 + RPI j, 16-B chunk cc8 of the row piece
@@ -6351,6 +6399,15 @@ int arena_grow(rf_ctx *ctx, Arena &a, int64_t need, Region *skip)
     return e;
 }
 
+// The capacity an arena of old_cap bytes gets when `want` bytes of regions
+// must fit: the guards, half as much again as before at least, and a margin
+// of an eighth plus 1 MiB, in whole MiB.  rf_host_reserve_fit inverts it.
+static int64_t arena_capacity(int64_t want, int64_t old_cap)
+{
+    const int64_t cap = std::max<int64_t>(want + 2 * ARENA_GUARD, (int64_t)(old_cap * 1.5));
+    return align_up(cap + cap / 8 + (1 << 20), 1 << 20);
+}
+
 int arena_grow_impl(rf_ctx *ctx, Arena &a, int64_t need, Region *skip)
 {
     std::vector<Region *> regs;
@@ -6359,8 +6416,7 @@ int arena_grow_impl(rf_ctx *ctx, Arena &a, int64_t need, Region *skip)
     for (auto *r : regs)
         if (r != skip)
             live += r->cap;
-    int64_t cap = std::max<int64_t>(live + need + 2 * ARENA_GUARD, (int64_t)(a.cap * 1.5));
-    cap = align_up(cap + cap / 8 + (1 << 20), 1 << 20);
+    const int64_t cap = arena_capacity(live + need, a.cap);
     char *d = nullptr;
     HIPCHK(ctx, hipMalloc((void **)&d, cap));
     std::sort(regs.begin(), regs.end(), [](Region *x, Region *y) { return x->off < y->off; });
@@ -6400,7 +6456,7 @@ int arena_grow_impl(rf_ctx *ctx, Arena &a, int64_t need, Region *skip)
 
 int region_ensure(rf_ctx *ctx, Arena &a, Region &r, int64_t bytes)
 {
-    bytes = align_up(std::max<int64_t>(bytes, 16), 256);
+    bytes = region_bytes(bytes);
     if (r.off >= 0 && r.cap >= bytes)
         return 0;
     if (a.top + bytes + ARENA_GUARD > a.cap)
@@ -6533,9 +6589,13 @@ void load_env_opts(Opts &o)
 }
 
 // Launches the picked scorer over nitems items (split: partials of gy reads,
-// rchunk of them per workgroup); returns the launch's grid.y
+// rchunk of them per workgroup); returns the launch's grid.y.  from (fused
+// launches of rf_score_dense_from): the fold continues from the totals
+// already in `dense` (the INIT instantiations); a split launch writes
+// partials as ever and k_reduce<true> takes the initial value
 unsigned launch_scorer(rf_ctx *ctx, const ScorePick &pk, unsigned nitems, unsigned gy, const WorkItem *items,
-                   const ScoreGroup *groups, const ScoreRead *reads, double *dense, double *split)
+                   const ScoreGroup *groups, const ScoreRead *reads, double *dense, double *split,
+                   bool from = false)
 {
     const uint8_t *d_bases = (const uint8_t *)ctx->bytes_arena.d;
     const double *d_tabs = (const double *)ctx->tab_arena.d;
@@ -6546,11 +6606,25 @@ unsigned launch_scorer(rf_ctx *ctx, const ScorePick &pk, unsigned nitems, unsign
     const ScoreChunks ch = score_chunks(pk.family(), sm != 0, nitems, gy, ctx->opt.score_wgs, ctx->opt.seg_wgs);
     if (sm)
         grid.y = ch.grid_y;
+    if (from && !sm) {
+        if (pk.seg) {
+            hipLaunchKernelGGL((k_score_segl<32, true>), grid, dim3(64), 0, ctx->stream, items, groups, reads, d_bases,
+                               d_tabs, d_bands, dense, split, sm, ch.rchunk);
+        } else if (!pk.lean) {
+            hipLaunchKernelGGL(k_score<true>, grid, dim3(128), 2 * pk.lds * 8, ctx->stream, items, groups, reads,
+                               d_bases, d_tabs, d_bands, dense, split, sm, pk.lds);
+        } else {
+            hipLaunchKernelGGL((k_score_ws<WS_NPF, 256, true>), grid, dim3(512), pk.lds * 8, ctx->stream, items,
+                               groups, reads, d_bases, d_tabs, d_bands, dense, split, sm, pk.lds,
+                               WS_CODES ? (const double *)ctx->codes.lut.p : nullptr, ch.rchunk);
+        }
+        return grid.y;
+    }
     if (pk.seg) {
         hipLaunchKernelGGL(k_score_segl<32>, grid, dim3(64), 0, ctx->stream, items, groups, reads, d_bases, d_tabs,
                            d_bands, dense, split, sm, ch.rchunk);
     } else if (!pk.lean) {
-        hipLaunchKernelGGL(k_score, grid, dim3(128), 2 * pk.lds * 8, ctx->stream, items, groups, reads,
+        hipLaunchKernelGGL(k_score<false>, grid, dim3(128), 2 * pk.lds * 8, ctx->stream, items, groups, reads,
                            d_bases, d_tabs, d_bands, dense, split, sm, pk.lds);
     } else {
         hipLaunchKernelGGL((k_score_ws<WS_NPF, 256>), grid, dim3(512), pk.lds * 8, ctx->stream, items,
@@ -6700,6 +6774,8 @@ int rf_create(int device, rf_ctx **out)
     // the lean scorer may use up to the whole 160 KiB LDS of a CU, and so may
     // the block-wide DP's ring
     (void)hipFuncSetAttribute((const void *)k_score_ws<WS_NPF, 256>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void *)k_score_ws<WS_NPF, 256, true>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)k_dp<DPW_NT, false, DPW_NT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -7458,7 +7534,7 @@ static int realign_bands(rf_ctx *ctx, int32_t njobs, const int32_t *slot, const 
                              o.n == S.n && o.m == T.m && o.H == H && o.tplver == T.version &&
                              o.seqver == S.version;
         const int P = partner ? o.P : band_stride(H, pad_call ? 1 : 0);
-        if (int e = region_ensure(ctx, ctx->band_arena, b.r, band_K(H, T.m) * P * 8))
+        if (int e = region_ensure(ctx, ctx->band_arena, b.r, band_payload_bytes(H, T.m, P)))
             return e;
         moved = moved || !b.valid || b.seq != seq[k] || b.tpl != tpl[k] || b.bw != bw[k] ||
                 b.n != S.n || b.m != T.m || b.H != H || b.P != P;
@@ -8888,7 +8964,7 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
                            dev<const WorkItem>(ctx, BUF_SCORE_ITEMS), dev<const ScoreGroup>(ctx, BUF_SCORE_GROUPS),
                            dev<const ScoreRead>(ctx, BUF_READS_OR_MASK), d_dense, d_split);
         if (split && dense_total > 0)
-            hipLaunchKernelGGL(k_reduce, dim3((unsigned)((dense_total + 255) / 256)), dim3(256), 0,
+            hipLaunchKernelGGL(k_reduce<false>, dim3((unsigned)((dense_total + 255) / 256)), dim3(256), 0,
                                ctx->stream, dev<const ScoreGroup>(ctx, BUF_SCORE_GROUPS), ngroups, d_gstart,
                                dense_total, d_split, d_dense);
     }
@@ -8955,8 +9031,13 @@ int rf_score(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_
     return 0;
 }
 
+// init (rf_score_dense_from; NULL: the fold starts at 0.0): the table the
+// fold continues, in the call's row layout, host or device memory by
+// init_kind.  It is copied into BUF_DENSE_TOTALS once every check has passed,
+// and the scorers then read and write that one resident table in place.
 static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
-                            double *out, hipMemcpyKind out_kind)
+                            double *out, hipMemcpyKind out_kind, const double *init = nullptr,
+                            hipMemcpyKind init_kind = hipMemcpyHostToDevice)
 {
     if (!ctx || ngroups < 0 || (ngroups > 0 && (!slot_off || !slots)))
         return fail(ctx, RF_ERR_ARG, "rf_score_dense: bad arguments");
@@ -9012,15 +9093,23 @@ static int score_dense_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_of
                                sizeof(double) * std::max<int64_t>(P.split_total, 1)))
             return e;
     double *d_dense = dev<double>(ctx, BUF_DENSE_TOTALS);
+    const bool from = init != nullptr && P.dense_total > 0;
+    if (from)
+        HIPCHK(ctx, hipMemcpyAsync(d_dense, init, sizeof(double) * P.dense_total, init_kind, ctx->stream));
     HIPCHK(ctx, hipEventRecord(ctx->ev[EV_SCORER_BEGIN], ctx->stream));
     unsigned gy = 0;
     if (nitems) {
         gy = launch_scorer(ctx, P.pick, (unsigned)nitems, split ? (unsigned)P.max_reads : 1u,
                            dev<const WorkItem>(ctx, BUF_DENSE_ITEMS), dev<const ScoreGroup>(ctx, BUF_DENSE_GROUPS),
                            dev<const ScoreRead>(ctx, BUF_DENSE_READS), d_dense,
-                           split ? dev<double>(ctx, BUF_RING_OR_SPLIT) : nullptr);
-        if (split)
-            hipLaunchKernelGGL(k_reduce, dim3((unsigned)((P.dense_total + 255) / 256)), dim3(256), 0,
+                           split ? dev<double>(ctx, BUF_RING_OR_SPLIT) : nullptr, from);
+        if (split && from)
+            hipLaunchKernelGGL(k_reduce<true>, dim3((unsigned)((P.dense_total + 255) / 256)), dim3(256), 0,
+                               ctx->stream, dev<const ScoreGroup>(ctx, BUF_DENSE_GROUPS), ngroups,
+                               dev<const int64_t>(ctx, BUF_DENSE_GSTART), P.dense_total,
+                               dev<const double>(ctx, BUF_RING_OR_SPLIT), d_dense);
+        else if (split)
+            hipLaunchKernelGGL(k_reduce<false>, dim3((unsigned)((P.dense_total + 255) / 256)), dim3(256), 0,
                                ctx->stream, dev<const ScoreGroup>(ctx, BUF_DENSE_GROUPS), ngroups,
                                dev<const int64_t>(ctx, BUF_DENSE_GSTART), P.dense_total,
                                dev<const double>(ctx, BUF_RING_OR_SPLIT), d_dense);
@@ -9052,16 +9141,18 @@ int rf_score_dense_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
     return score_dense_impl(ctx, ngroups, slot_off, slots, dev_out, hipMemcpyDeviceToDevice);
 }
 
-int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
-                       const int32_t *ref_slot, double *out)
+// rf_score_dense_ref and the rf_score_dense_from calls: the reads' fold (from
+// init when given), then the reference term of the groups that have one.
+// ref_slot may be NULL here (no reference term).
+static int score_dense_ref_impl(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
+                                const int32_t *ref_slot, const double *init, hipMemcpyKind init_kind, double *out,
+                                hipMemcpyKind out_kind)
 {
     if (!ctx || ngroups < 0 || (ngroups > 0 && (!slot_off || !slots)))
         return fail(ctx, RF_ERR_ARG, "rf_score_dense: bad arguments");
-    if (!ref_slot)
-        return fail(ctx, RF_ERR_ARG, "rf_score_dense_ref: null ref_slot");
     // the reference slots, before anything runs
     bool any_ref = false;
-    for (int32_t g = 0; g < ngroups; ++g) {
+    for (int32_t g = 0; ref_slot && g < ngroups; ++g) {
         const int32_t rs = ref_slot[g];
         if (rs < 0)
             continue;
@@ -9080,7 +9171,7 @@ int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
         }
     }
     // the reads' fold: totals in BUF_DENSE_TOTALS
-    if (int e = score_dense_impl(ctx, ngroups, slot_off, slots, nullptr, hipMemcpyDeviceToHost))
+    if (int e = score_dense_impl(ctx, ngroups, slot_off, slots, nullptr, hipMemcpyDeviceToHost, init, init_kind))
         return e;
     const ScorePlan &P = ctx->dplan.plan;
     ctx->codon_dense_ms = 0;
@@ -9113,11 +9204,59 @@ int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, co
         ctx->score_ms += ctx->codon_dense_ms;
     }
     if (out && P.dense_total > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(out, d_dense, sizeof(double) * P.dense_total, hipMemcpyDeviceToHost,
-                                   ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(out, d_dense, sizeof(double) * P.dense_total, out_kind, ctx->stream));
         HIPCHK(ctx, stream_wait(ctx));
     }
     return 0;
+}
+
+int rf_score_dense_ref(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
+                       const int32_t *ref_slot, double *out)
+{
+    if (ctx && !ref_slot && !(ngroups < 0 || (ngroups > 0 && (!slot_off || !slots))))
+        return fail(ctx, RF_ERR_ARG, "rf_score_dense_ref: null ref_slot");
+    return score_dense_ref_impl(ctx, ngroups, slot_off, slots, ref_slot, nullptr, hipMemcpyHostToDevice, out,
+                                hipMemcpyDeviceToHost);
+}
+
+int rf_score_dense_from(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
+                        const int32_t *ref_slot, const double *init, double *out)
+{
+    return score_dense_ref_impl(ctx, ngroups, slot_off, slots, ref_slot, init, hipMemcpyHostToDevice, out,
+                                hipMemcpyDeviceToHost);
+}
+
+int rf_score_dense_from_dev(rf_ctx *ctx, int32_t ngroups, const int32_t *slot_off, const int32_t *slots,
+                            const int32_t *ref_slot, const double *dev_init, double *dev_out)
+{
+    if (!dev_out)
+        return fail(ctx, RF_ERR_ARG, "rf_score_dense_from_dev: null device buffer");
+    return score_dense_ref_impl(ctx, ngroups, slot_off, slots, ref_slot, dev_init, hipMemcpyDeviceToDevice, dev_out,
+                                hipMemcpyDeviceToDevice);
+}
+
+int64_t rf_host_reserve_fit(int64_t budget)
+{
+    if (budget < arena_capacity(0, 0))
+        return -1;
+    int64_t lo = 0, hi = budget;   // arena_capacity(lo, 0) <= budget < arena_capacity(hi + 1, 0)
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo + 1) / 2;
+        if (arena_capacity(mid, 0) <= budget)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+int64_t rf_band_arena_bytes(const rf_ctx *ctx) { return ctx ? ctx->band_arena.cap : 0; }
+
+int64_t rf_host_band_bytes(int32_t n, int32_t m, int32_t bw, int32_t pad)
+{
+    if (n < 1 || m < 0 || bw < 0)
+        return -1;
+    return 2 * band_region_bytes(n, m, bw, pad != 0);
 }
 
 int rf_last_score_launch(const rf_ctx *ctx, int32_t *launch)

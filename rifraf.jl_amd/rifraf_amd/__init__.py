@@ -36,6 +36,9 @@ def __getattr__(name):
                 "moves_to_aligned_seqs", "moves_to_indices", "band_tolerance", "forward_errors"):
         from . import align
         return getattr(align, name)
+    if name in ("plan_read_chunks", "dense_totals_chunked"):
+        from . import deep
+        return getattr(deep, name)
     if name in ("cross_scores", "choose_references"):
         from . import assign
         return getattr(assign, name)

@@ -79,6 +79,11 @@ _SIGNATURES = {
     "rf_score_dense": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "rf_score_dense_dev": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "rf_score_dense_ref": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rf_score_dense_from": (c_int, [c_void_p, c_int32] + [c_void_p] * 5),
+    "rf_score_dense_from_dev": (c_int, [c_void_p, c_int32] + [c_void_p] * 5),
+    "rf_host_band_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "rf_host_reserve_fit": (c_int64, [c_int64]),
+    "rf_band_arena_bytes": (c_int64, [c_void_p]),
     "rf_slot_geometry": (c_int, [c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32),
                                  POINTER(c_int32), POINTER(c_int32)]),
     "rf_download_band": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
@@ -244,6 +249,29 @@ def host_score_plan(n, m, bw, read_off, stride=None, finite=None, per_seq=False,
         raise ValueError(f"rf_host_score_plan: bad arguments ({rc})")
     return ScorePlan(SCORE_KERNELS[pick[0]], int(pick[1]), int(pick[2]), bool(split[0]), bool(split[1]),
                      [tuple(int(x) for x in it) for it in items[:ni.value]], dense_off.tolist(), split_off[:ng].tolist())
+
+
+def host_band_bytes(n, m, bw, pad=False):
+    """rf_host_band_bytes: the bytes one slot's A band plus B band take in the
+    band arena for a read of n bases against a template of m at bandwidth bw,
+    on the host alone (no context, no GPU).  pad: whether the realign call
+    that fills them pads its bands (its widest band has H >= the band_pad
+    option)."""
+    v = int(load().rf_host_band_bytes(int(n), int(m), int(bw), int(bool(pad))))
+    if v < 0:
+        raise ValueError("rf_host_band_bytes: bad arguments")
+    return v
+
+
+def host_reserve_fit(budget):
+    """rf_host_reserve_fit: the largest band_bytes for which rf_reserve on an
+    engine with an empty band arena allocates at most `budget` bytes (no
+    context, no GPU).  Raises ValueError for a budget below the smallest
+    arena (2 MiB)."""
+    v = int(load().rf_host_reserve_fit(int(budget)))
+    if v < 0:
+        raise ValueError("rf_host_reserve_fit: the budget is below the smallest band arena")
+    return v
 
 
 def host_score_chunks(kernel, split, nitems, max_reads, score_wgs=2048, seg_wgs=262144):

@@ -138,6 +138,10 @@ class Engine:
     def device_bytes(self) -> int:
         return int(self.lib.rf_device_bytes(self.ctx))
 
+    def band_arena_bytes(self) -> int:
+        """rf_band_arena_bytes: the band arena's capacity now."""
+        return int(self.lib.rf_band_arena_bytes(self.ctx))
+
     def code_stats(self) -> dict:
         """rf_code_stats: the row-code dictionary's size, the reads left
         uncoded because it was full, and its fresh starts."""
@@ -785,6 +789,64 @@ class Engine:
             res.append(out[at:at + r])
             at += r
         return res
+
+    def _from_args(self, groups, ref_slots):
+        pg = groups if isinstance(groups, PackedGroups) else pack_groups(groups)
+        refs = None
+        if ref_slots is not None:
+            refs = np.ascontiguousarray(ref_slots, np.int32).reshape(-1)
+            if len(refs) != pg.n:
+                raise ValueError("one reference slot per group (-1: none)")
+            if not pg.n:
+                refs = None
+        return pg, refs
+
+    def score_dense_from(self, groups, init, ref_slots=None, to_host: bool = True, rows=None):
+        """rf_score_dense_from: score_dense that continues a fold.  init: a
+        list of (m_g+1, 9) arrays, the totals of the reads folded so far (the
+        result of an earlier score_dense / score_dense_from over them), or
+        None to start at 0.0.  ref_slots: None, or one slot per group (-1:
+        none) whose reference score is added last -- pass it with a cluster's
+        last chunk only.  The result has the bits of one score_dense(_ref)
+        over all the reads in order.  Returns a list of (m_g+1, 9) arrays (or
+        None when to_host is False: totals stay in HBM)."""
+        pg, refs = self._from_args(groups, ref_slots)
+        G, slot_off, slots = pg.n, pg.slot_off, pg.slots
+        if rows is None:
+            rows = [self.geometry(int(slots[slot_off[g]]), RF_BAND_B)[1] for g in range(G)]
+        flat = None
+        if init is not None:
+            if len(init) != G or any(np.shape(t) != (r, 9) for t, r in zip(init, rows)):
+                raise ValueError("init: one (m_g + 1, 9) table per group")
+            flat = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64) for t in init])
+                                        if G else np.zeros((1, 9)), np.float64)
+        out = np.empty((int(sum(rows)), 9)) if to_host else None
+        self._check(self.lib.rf_score_dense_from(self.ctx, G, ptr(slot_off), ptr(slots), ptr(refs), ptr(flat),
+                                                 ptr(out)))
+        if not to_host:
+            return None
+        res, at = [], 0
+        for r in rows:
+            res.append(out[at:at + r])
+            at += r
+        return res
+
+    def score_dense_from_dev(self, groups, init_ptr, out_ptr: int, ref_slots=None):
+        """rf_score_dense_from_dev: score_dense_from with the initial table
+        read from device memory at init_ptr (None or 0: start at 0.0) and the
+        totals written to device memory at out_ptr (sum_g (m_g+1)*9 doubles
+        each, on this engine's device).  The two may be the same buffer: the
+        table accumulates in place."""
+        pg, refs = self._from_args(groups, ref_slots)
+        self._check(self.lib.rf_score_dense_from_dev(self.ctx, pg.n, ptr(pg.slot_off), ptr(pg.slots), ptr(refs),
+                                                     c_void_p(int(init_ptr)) if init_ptr else None,
+                                                     c_void_p(int(out_ptr)) if out_ptr else None))
+
+    @staticmethod
+    def host_band_bytes(n: int, m: int, bw: int, pad: bool = False) -> int:
+        """rf_host_band_bytes: bytes of one slot's A + B bands in the band
+        arena (no context, no GPU); see _lib.host_band_bytes."""
+        return _lib.host_band_bytes(n, m, bw, pad)
 
     def candidates(self, groups, scores, sources, min_dist, ref_slots=None, masks=None, cand_cap=None,
                    chosen_cap=None, with_counts=False):
